@@ -22,14 +22,22 @@ BASELINE configurations are reachable with flags (they are parity-test cases; th
     (fresh children, 127.0.0.1 rendezvous on a free port), passes rank 0's JSON line through and exits with the
     children's status.
 
-Prints ONE JSON line: images/sec for the whole job, plus
+A plain run times exactly --steps steps (one block, after --warmup steps) and prints ONE JSON line: images/sec for the
+whole job (`value`) and `ms_per_step`, what one timed step took.  --dump-outputs DIR then also writes what the last timed
+step computed as DIR/<name>.npy (the logits of an evaluation step; see dump_outputs()): the inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
+
+--full adds everything beside that figure, at the cost of extra runs: blocks of --steps steps repeated until they cover
+--min-region-s (`value` is then the median block), kernel events sampled inside the timed region, the one-stream block,
+the box's clocks, the KL threshold search, the cross-rank threshold check, and
   "roofline":     the kernel family with the largest share of the step: algorithmic bytes per launch / its
                   HIP-event-timed duration inside the timed region, against 8 TB/s; every family under "kernels", and the
                   whole step's algorithmic bytes over its wall time under "whole_step";
   "cpu_baseline": the same workload on the host cores — the converted net with the C++/OpenMP restatement of the
                   reference's arithmetic (oracle/libfq_host.so) doing the fake-quant on ALL cores and torch-CPU the
                   convolutions — on a bounded sample, with the fake-quant-only figures (the reference's pass-by-pass op
-                  chain and the fused form, all cores; the numpy chain on one thread) beside it.
+                  chain and the fused form, all cores; the numpy chain on one thread) beside it;
+  "headline_tensor": the stand-alone fake-quant on the 411 MB activation (headline_tensor()).
 """
 import argparse
 import json
@@ -50,6 +58,7 @@ if ROOT not in sys.path:
 
 HBM_PEAK_GBS = 8000.0       # MI355X HBM3E peak (/opt/skills/guides/MI355X_MICROARCH.md)
 DEFAULT_STEPS = 500         # ~0.6 s of timed region for the default workload (1.16-1.21 ms per step)
+DUMP_DATA_BYTES = 60 << 20  # --dump-outputs: array data written in all (under 64 MB with the .npy headers)
 
 KERNEL_NAMES = {
     "apply_online": "act_apply_kernel<ONLINE> (fake-quant apply pass, 8 B/elem)",
@@ -274,6 +283,19 @@ def cpu_baseline(args, classes, hw, budget_s=20.0):
     return out
 
 
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy in float32 (float64 stays float64).  Past DUMP_DATA_BYTES in all,
+    each array is cut to the same share of its flattened elements, at positions drawn by a fixed seed."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in sorted(arrays.items()):
+        if total > DUMP_DATA_BYTES:
+            keep = a.size * DUMP_DATA_BYTES // total
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def launch_ranks(n):
     """`python bench.py --gpus N` typed without a launcher: run N ranks of this same command under
     torch.distributed.run as CHILD processes.  Nothing in this (parent) process has touched a GPU — `import torch` and
@@ -362,14 +384,22 @@ def main():
                          "(simulate_quantization.py:317-334); calib-kl: histogram collection of the KL calibration "
                          "(:296-315, quantize/distribution_calibrate.py:50-114)")
     ap.add_argument("--rotate", type=int, default=4, help="distinct resident input batches cycled through the steps")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: repeated blocks (--min-region-s), kernel events and the "
+                         "roofline, the one-stream block, the headline tensor, the CPU baseline, the box's clocks, the KL "
+                         "search and the cross-rank threshold check.  Without it a run times exactly --steps steps, once")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy: eval - logits; "
+                         "calib-naive - logits and thresholds (every quantised block's input_max); calib-kl - histograms "
+                         "and ranges of the last collection")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--min-region-s", type=float, default=float(os.environ.get("FQ_BENCH_MIN_REGION_S", "8.0")),
-                    help="blocks of --steps steps are repeated until they cover this much time (8 s: long enough for a "
-                         "once-per-few-seconds utilisation sampler beside the run to see the GPU busy); `value` is the median "
-                         "block")
-    ap.add_argument("--max-repeats", type=int, default=4000)
+    ap.add_argument("--min-region-s", type=float, default=None,
+                    help="(--full) blocks of --steps steps are repeated until they cover this much time (default "
+                         "FQ_BENCH_MIN_REGION_S or 8 s: long enough for a once-per-few-seconds utilisation sampler beside the "
+                         "run to see the GPU busy); `value` is the median block")
+    ap.add_argument("--max-repeats", type=int, default=None, help="(--full) at most this many blocks (default 4000)")
     ap.add_argument("--event-every", type=int, default=None,
-                    help="bracket the library's kernels with HIP events in every n-th timed step (default 50 - calibration "
+                    help="(--full) bracket the library's kernels with HIP events in every n-th timed step (default 50 - calibration "
                          "phases, whose blocks are a dozen batches with a special first one: 7 -: 10 steps of the "
                          "default 500 = 130 launches per family; a bracketed step is launched eagerly and, with --streams > 1, "
                          "runs alone - at every 25th step that cost `value` 4 %%: 126 k against 132 k images/s without events).  "
@@ -400,6 +430,17 @@ def main():
                          "MobileNetV2 W4, 5 and 6 lose 8-12 %%), else 3 (fp32 tensors between the layers: 4 against 3 was +0.6 / "
                          "+0.8 %% on two boxes and -1.1 %% (sd 0.05) on a third; profiles/r5_lanes4_ab.txt)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
+    full_only = [flag for flag, v in (("--min-region-s", args.min_region_s), ("--max-repeats", args.max_repeats),
+                                      ("--event-every", args.event_every)) if v is not None]
+    if full_only and not args.full:
+        raise SystemExit("bench.py: %s only apply with --full (a plain run times exactly --steps steps, once)"
+                         % " / ".join(full_only))
+    if args.min_region_s is None:
+        args.min_region_s = float(os.environ.get("FQ_BENCH_MIN_REGION_S", "8.0"))
+    if args.max_repeats is None:
+        args.max_repeats = 4000
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args.gpus))         # decided before any GPU call; children do the work
@@ -570,6 +611,7 @@ def main():
     # launch-latency-sensitive (1.3 ms of kernels); replay removes the host from the loop.  The steps that carry the kernel
     # events of the roofline leg (every `event_every`-th) still run eagerly INSIDE the timed region.
     graphs, graph_error = None, None
+    graph_outs = [[None] * rotate for _ in range(n_streams)]      # what each graph's replay leaves its step's result in
     if args.graph and args.phase == "calib-naive" and not distributed:
         # one process: the calibration step (forward with online scales + net.update_ema()) holds no collective and no host
         # synchronisation, so it replays from a hipGraph like the evaluation step does - launching its ~100 kernels from
@@ -581,7 +623,7 @@ def main():
             for b in range(rotate):
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, pool=pool):
-                    step(b)
+                    graph_outs[0][b] = step(b)
                 graphs[0][b] = g
             for b in range(rotate):
                 graphs[0][b].replay()
@@ -600,10 +642,10 @@ def main():
                     g = torch.cuda.CUDAGraph()
                     if streams[lane] is None:
                         with torch.cuda.graph(g, pool=pool):
-                            eval_step(b, lane)
+                            graph_outs[lane][b] = eval_step(b, lane)
                     else:
                         with torch.cuda.graph(g, pool=pool, stream=streams[lane]):
-                            eval_step(b, lane)
+                            graph_outs[lane][b] = eval_step(b, lane)
                     graphs[lane][b] = g
             for lane in range(n_streams):
                 for b in range(rotate):
@@ -617,7 +659,7 @@ def main():
     # ~45 launches of a step costs ~35 % of THAT step (two marker packets per launch), and the cost is charged to its block.
     if args.event_every is None:
         args.event_every = 50 if args.phase == "eval" else 7
-    event_every = 0 if args.no_kernel_events else max(1, args.event_every)
+    event_every = 0 if args.no_kernel_events or not args.full else max(1, args.event_every)
     profiled_steps = 0
     if event_every:
         ops.profile_reset()
@@ -639,19 +681,24 @@ def main():
             profiled_steps += kl_block(first_step, args.steps, every)
         else:
             sampled = []
+            last = first_step + args.steps - 1
             for i in range(first_step, first_step + args.steps):
                 on = bool(every) and ((i - first_step) % every == 0)
+                y = None
                 if on and n_streams > 1:
                     sampled.append(i)                 # two steps in flight: the sampled steps run at the END of the block, alone
                 elif on:
                     ops.profile_enable(True)
                     profiled_steps += 1
-                    step(i)
+                    y = step(i)
                     ops.profile_enable(False)
                 elif graphs is not None:
                     replay(i % n_streams, i % rotate)
+                    y = graph_outs[i % n_streams][i % rotate]
                 else:
-                    step(i, i % n_streams)
+                    y = step(i, i % n_streams)
+                if i == last:
+                    last_out[0] = y
             if sampled:
                 # ONE drain, then the steps that carry kernel events one after the other on one stream - still inside the
                 # timed region and charged to `value` (a drain in front of and behind every sampled step cost more than the
@@ -660,7 +707,9 @@ def main():
                 ops.profile_enable(True)
                 for i in sampled:
                     profiled_steps += 1
-                    step(i, 0)
+                    y = step(i, 0)
+                    if i == last:
+                        last_out[0] = y
                 ops.profile_enable(False)
         barrier()
         dt = time.perf_counter() - t0
@@ -686,15 +735,16 @@ def main():
     def carries_events(k):
         return EVENT_BLOCK_EVERY == 1 or k % EVENT_BLOCK_EVERY == 1
 
-    box_probe = box_probe_start() if rank == 0 else None
+    last_out = [None]                                # the result of the last timed step (--dump-outputs)
+    box_probe = box_probe_start() if rank == 0 and args.full else None
     blocks = [timed_block(0, with_events=carries_events(0))]
-    while sum(blocks) < args.min_region_s and len(blocks) < args.max_repeats:
+    while args.full and sum(blocks) < args.min_region_s and len(blocks) < args.max_repeats:
         blocks.append(timed_block(len(blocks) * args.steps, with_events=carries_events(len(blocks))))
     if event_every and not any(carries_events(k) for k in range(len(blocks))):
         blocks.append(timed_block(len(blocks) * args.steps, with_events=True))
         event_idx = {len(blocks) - 1}
     else:
-        event_idx = {k for k in range(len(blocks)) if carries_events(k)}
+        event_idx = {k for k in range(len(blocks)) if carries_events(k)} if args.full else set()
     elapsed = float(np.median(blocks))
     event_blocks = [b for k, b in enumerate(blocks) if k in event_idx]
     plain_blocks = [b for k, b in enumerate(blocks) if k not in event_idx]
@@ -707,9 +757,21 @@ def main():
         all_reduce(hi, dist.ReduceOp.MAX)
         rank_ms = (float(lo.item()), float(hi.item()))
     coll = fqdist.collective_stats()
+    if args.dump_outputs and rank == 0:
+        torch.cuda.synchronize()
+        if args.phase == "calib-kl":
+            blocks_q = net.collect_quantized_blocks()
+            arrays = {"histograms": np.stack([kl_extra["hists"][b] for b in blocks_q]),
+                      "ranges": np.array([kl_extra["ranges"][b] for b in blocks_q])}
+        else:
+            arrays = {"logits": last_out[0].float().cpu().numpy()}
+            if args.phase == "calib-naive":
+                arrays["thresholds"] = torch.cat([b.input_max.data()._t.reshape(-1).float()
+                                                  for b in net.collect_quantized_blocks()]).cpu().numpy()
+        dump_outputs(args.dump_outputs, arrays)
     # the same steps on ONE stream (the figure of rounds 1-3), no kernel events: one block, reported beside `value`
     single_s = None
-    if n_streams > 1:
+    if n_streams > 1 and args.full:
         barrier()
         t0 = time.perf_counter()
         for i in range(args.steps):
@@ -724,7 +786,7 @@ def main():
             all_reduce(t, dist.ReduceOp.MAX)
             single_s = float(t.item())
     kl_search_ms, thresholds = None, None
-    if args.phase == "calib-kl":
+    if args.phase == "calib-kl" and args.full:
         # the threshold search over all layers: ONE launch (reference: ~1.4 s of Python per layer); once per calibration
         from quantization.mxnet_amd.quantize.distribution_calibrate import kl_calibrate_many
         blocks_q = net.collect_quantized_blocks()
@@ -740,7 +802,7 @@ def main():
     # calibration phases on several ranks: every rank must end with the SAME thresholds, bit for bit (the collectives exist for
     # exactly that) - a digest of each rank's vector, the minimum and maximum over the ranks compared on rank 0
     thresholds_equal = None
-    if distributed and args.phase != "eval":
+    if distributed and args.phase != "eval" and args.full:
         if args.phase == "calib-naive":
             vec = torch.cat([b.input_max.data()._t.reshape(-1).float() for b in net.collect_quantized_blocks()])
         else:
@@ -751,12 +813,14 @@ def main():
         all_reduce(lo_d, dist.ReduceOp.MIN)
         all_reduce(hi_d, dist.ReduceOp.MAX)
         thresholds_equal = bool(torch.equal(lo_d, hi_d))
-    prof = ops.profile_read()
-    ops.profile_reset()
-    # A bracketing event pair adds a fixed cost to every launch it times (two marker packets + dispatch latency): the
-    # median pair around a one-element kernel minus that kernel's own back-to-back cost, both measured NOW on this device.
-    ev_overhead_ms, null_kernel_ms = ops.profile_event_overhead_ms(dev)
-    launch_overhead_ms, spin_ms = ops.profile_launch_overhead_ms(dev)
+    prof, ev_overhead_ms, null_kernel_ms, launch_overhead_ms, spin_ms = {}, 0.0, 0.0, 0.0, 0.0
+    if args.full:
+        prof = ops.profile_read()
+        ops.profile_reset()
+        # A bracketing event pair adds a fixed cost to every launch it times (two marker packets + dispatch latency): the
+        # median pair around a one-element kernel minus that kernel's own back-to-back cost, both measured NOW on this device.
+        ev_overhead_ms, null_kernel_ms = ops.profile_event_overhead_ms(dev)
+        launch_overhead_ms, spin_ms = ops.profile_launch_overhead_ms(dev)
 
     if distributed:
         all_reduce(counters, dist.ReduceOp.SUM)              # the eval counters of simulate_quantization.py:123-147
@@ -922,7 +986,7 @@ def main():
                                         "frac_actual": round(whole_moved / HBM_PEAK_GBS, 4),
                                         "what": "sum of the algorithmic bytes of every library launch of one step / "
                                                 "ms_per_step (library convolutions and launch gaps included in the time)"},
-                         "kernels": kernels},
+                         "kernels": kernels} if args.full else None,
             "repeats": len(blocks),
             "ranks": {"world": world, "backend": backend if distributed else None,
                       "rccl_world": (dist.get_world_size() if distributed and backend == "nccl" else None),
@@ -959,14 +1023,16 @@ def main():
                                      "lanes_gain": round(line["value"] / max(images / single_s, 1e-9), 4),
                                      "what": "the same %d steps launched on ONE stream (--streams 1), one block, no kernel "
                                              "events; lanes_gain = value / this" % args.steps}
-        line["box"] = box_info(box_probe)
+        if args.full:
+            line["box"] = box_info(box_probe)
         line["consistency"]["value_what"] = ("median over ALL blocks; since round 5 only every third block carries the "
                                              "event-bracketed steps (which run alone on one stream and cost their block 1-2 %), so "
                                              "with three or more blocks `value` is a plain block's; rounds 1-4 charged that cost to "
-                                             "every block (FQ_BENCH_EVENT_BLOCK_EVERY=1 reproduces it)")
+                                             "every block (FQ_BENCH_EVENT_BLOCK_EVERY=1 reproduces it)") if args.full else \
+            "one block of exactly --steps steps, no kernel events (--full repeats blocks and samples kernel events)"
         if args.phase != "eval":
             del line["eval_counters"]
-        if args.phase == "calib-kl":
+        if args.phase == "calib-kl" and args.full:
             line["kl_search"] = {"ms": round(kl_search_ms, 3), "layers": nblocks,
                                  "what": "fq_kl_search over all layers' histograms in one launch + the read-back of "
                                          "best_bins, once per calibration (outside the per-batch figure)",
@@ -980,14 +1046,14 @@ def main():
                                      "second batch on, FQ_KL_FUSED_HIST=0 switches that off), remaining histogram passes, first-batch "
                                      "ranges, first convolution, pooling - HIP events on sampled batches; the rest of the batch: "
                                      "the fp32 convolutions of the un-quantised forward (MIOpen / rocBLAS) and launch gaps"}
-        if world == 1 and not args.no_headline and args.phase == "eval":
+        if world == 1 and args.full and not args.no_headline and args.phase == "eval":
             line["headline_tensor"] = headline_tensor(dev, ops)
             stream_gbs = line["headline_tensor"]["apply_only"]["achieved"]
             line["roofline"]["whole_step"]["frac_of_streaming_rate"] = round(line["roofline"]["whole_step"]["achieved"] / stream_gbs, 4)
             line["roofline"]["whole_step"]["streaming_rate"] = stream_gbs
             line["roofline"]["whole_step"]["streaming_rate_what"] = ("headline_tensor.apply_only of this run: the library's own "
                                                                      "read + write pass on 822 MB")
-        if world == 1:
+        if world == 1 and args.full:
             line["cpu_baseline"] = None if args.no_cpu_baseline else cpu_baseline(args, classes, hw)
         print(json.dumps(line), flush=True)
     if distributed:

@@ -49,3 +49,13 @@ def test_help_texts_format():
     for script in ("bench.py", os.path.join("examples", "simulate_quantization.py")):
         res = subprocess.run([sys.executable, os.path.join(ROOT, script), "--help"], capture_output=True, text=True, timeout=300)
         assert res.returncode == 0 and "usage" in res.stdout, res.stderr[-1500:]
+
+
+def test_measurements_beyond_the_timed_steps_ask_for_full():
+    """A plain run times exactly --steps steps, once: the options of the repeated blocks and of the kernel events belong to
+    --full and are refused without it (before anything looks for a GPU), as is an empty timed region."""
+    for extra in (["--min-region-s", "1"], ["--max-repeats", "3"], ["--event-every", "10"]):
+        res = _run(["--steps", "3"] + extra)
+        assert res.returncode != 0 and "only apply with --full" in res.stderr and extra[0] in res.stderr, res.stderr[-1500:]
+    res = _run(["--steps", "0"])
+    assert res.returncode != 0 and "--steps must be at least 1" in res.stderr, res.stderr[-1500:]

@@ -37,7 +37,7 @@ def test_bench_launches_its_own_ranks(gpu, streams):
     env = dict(os.environ, FQ_BENCH_SHARE_GPU="1", FQ_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--full",
            "--no-cpu-baseline", "--max-repeats", "4", "--streams", str(streams)]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
@@ -76,7 +76,7 @@ def test_bench_calibration_phases_report_their_collectives(gpu, phase):
                HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--phase", phase,
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--phase", phase, "--full",
            "--model", "cifar_resnet20_v1", "--batch-size", "16", "--no-cpu-baseline", "--max-repeats", "2"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
@@ -103,7 +103,7 @@ def test_eight_ranks_sharing_gpu0_through_every_phase(gpu, phase):
                HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2")
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1", "--phase", phase,
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1", "--phase", phase, "--full",
            "--model", "cifar_resnet20_v1", "--batch-size", "8", "--no-cpu-baseline", "--no-headline", "--max-repeats", "2",
            "--min-region-s", "0"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1500)

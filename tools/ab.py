@@ -33,7 +33,7 @@ def main():
     base_env.setdefault("FQ_BENCH_MIN_REGION_S", "3")
     for r in range(rounds):
         for label, env, vargs in variants:
-            res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra.split() + vargs, env=dict(base_env, **env),
+            res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full"] + extra.split() + vargs, env=dict(base_env, **env),
                                  capture_output=True, text=True, cwd=ROOT)
             try:
                 v = json.loads(res.stdout.strip().splitlines()[-1])["value"]

@@ -14,7 +14,7 @@ line() {   # name, then bench.py arguments
   local name=$1; shift
   for b in $BATCHES; do
     local steps=$(( 12800 / b )); [ $steps -lt 40 ] && steps=40
-    python3 bench.py "$@" --batch-size $b --steps $steps --warmup 10 --no-cpu-baseline --no-headline 2>> $O/sweep.err |
+    python3 bench.py --full "$@" --batch-size $b --steps $steps --warmup 10 --no-cpu-baseline --no-headline 2>> $O/sweep.err |
       python3 -c "import sys, json
 for ln in sys.stdin:
     try: d = json.loads(ln)

@@ -1,10 +1,10 @@
 #!/bin/bash
-export FQ_BENCH_MIN_REGION_S=${FQ_BENCH_MIN_REGION_S:-1}   # (tools time with 1 s regions; the driver's plain bench.py run uses its 8 s default)
+export FQ_BENCH_MIN_REGION_S=${FQ_BENCH_MIN_REGION_S:-1}   # (tools time with 1 s regions; bench.py --full defaults to 8 s)
 # A/B of library variants on the whole benchmark step inside ONE GPU call: each argument is a quoted list of VAR=VALUE
 # settings ("" = defaults); prints images/s and the per-family ms per step of every run.
 #   tools/benchvar.sh "" "FQ_PWS_AUTO=1" "FQ_PWS_AUTO=1 FQ_PWS_CW=4"
 for v in "$@"; do
-  out=$(env $v python3 bench.py --steps ${STEPS:-200} --warmup 10 --no-cpu-baseline ${BENCH_ARGS} 2>/dev/null | tail -1)
+  out=$(env $v python3 bench.py --full --steps ${STEPS:-200} --warmup 10 --no-cpu-baseline ${BENCH_ARGS} 2>/dev/null | tail -1)
   python3 - "$v" "$out" <<'P'
 import json, sys
 v, line = sys.argv[1], sys.argv[2]

@@ -1,5 +1,5 @@
 #!/bin/bash
-export FQ_BENCH_MIN_REGION_S=${FQ_BENCH_MIN_REGION_S:-1}   # (tools time with 1 s regions; the driver's plain bench.py run uses its 8 s default)
+export FQ_BENCH_MIN_REGION_S=${FQ_BENCH_MIN_REGION_S:-1}   # (tools time with 1 s regions; bench.py --full defaults to 8 s)
 # Does the CLI's evaluation (examples/simulate_quantization.py, the reference's entry point) reach bench.py's figure?  Synthetic
 # ImageNet-shaped data generated on the device; --eval-graph 2 (the default: replay only where the host would hold the GPU back),
 # 1 (always) and 0 (never) on a long pass (2000 batches of 128) and, for the default, on a 50 000-image pass (a validation set).
@@ -14,7 +14,7 @@ for cfg in "mobilenet1.0|" "mobilenetv2_1.0|--quant-type channel --weight-bits-w
     echo "CLI   $model, $1 images, eval-graph=$2 :"; echo "$out" | sed 's/^/      /'
   done
   bextra=""; [ "$model" = "mobilenetv2_1.0" ] && bextra="--quant-type channel --weight-bits 4 --offline"
-  python bench.py --model $model $bextra --steps 1000 --no-cpu-baseline --no-headline --no-kernel-events 2>/dev/null | python -c "
+  python bench.py --full --model $model $bextra --steps 1000 --no-cpu-baseline --no-headline --no-kernel-events 2>/dev/null | python -c "
 import json,sys
 l=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('BENCH $model : %.1f images/sec (%.4f ms/step), single_stream %.1f' % (l['value'], l['ms_per_step'], (l.get('single_stream') or {}).get('value', 0)))"
 done

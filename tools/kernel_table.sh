@@ -3,7 +3,7 @@
 set -u
 TAG=$1; shift
 R=$(pwd); O=$R/gpurun_out/ktab; mkdir -p $O
-( cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $O/$TAG -o bench -- python3 $R/bench.py "$@" --steps 40 --warmup 5 --streams 1 --graph 0 --no-cpu-baseline --no-headline --no-kernel-events --min-region-s 0 --max-repeats 1 > $O/$TAG.json 2> $O/$TAG.err )
+( cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $O/$TAG -o bench -- python3 $R/bench.py --full "$@" --steps 40 --warmup 5 --streams 1 --graph 0 --no-cpu-baseline --no-headline --no-kernel-events --min-region-s 0 --max-repeats 1 > $O/$TAG.json 2> $O/$TAG.err )
 python3 - $O/$TAG $O/$TAG.txt <<'PY'
 import csv, glob, re, sys
 f = glob.glob(sys.argv[1] + '/**/*kernel_stats.csv', recursive=True)[0]

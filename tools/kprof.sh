@@ -1,5 +1,5 @@
 #!/bin/bash
-export FQ_BENCH_MIN_REGION_S=${FQ_BENCH_MIN_REGION_S:-1}   # (tools time with 1 s regions; the driver's plain bench.py run uses its 8 s default)
+export FQ_BENCH_MIN_REGION_S=${FQ_BENCH_MIN_REGION_S:-1}   # (tools time with 1 s regions; bench.py --full defaults to 8 s)
 # Per-kernel averages of the benchmark step under rocprofv3 (kernel trace only), one table per variant, inside ONE GPU call:
 #   tools/kprof.sh "" "FQ_PWS_AUTO=1 FQ_PWS_CFG=44"          (each argument: VAR=VALUE settings exported for that run)
 # Dispatches are grouped by (kernel, grid size), so layers that share a kernel show up separately.  Prints calls per step,
@@ -9,7 +9,7 @@ set -u
 R=$(pwd); i=0
 for v in "$@"; do
   i=$((i+1)); O=$R/gpurun_out/kprof_$i; rm -rf $O; mkdir -p $O
-  ( cd /tmp && export TMPDIR=/tmp && export $v NOTHING=1 && rocprofv3 --kernel-trace --output-format csv -d $O -o bench -- python3 $R/bench.py --steps 30 --warmup 3 --no-cpu-baseline --no-headline --no-kernel-events ${BENCH_ARGS:-} > $O/line.json 2> $O/err.txt )
+  ( cd /tmp && export TMPDIR=/tmp && export $v NOTHING=1 && rocprofv3 --kernel-trace --output-format csv -d $O -o bench -- python3 $R/bench.py --full --steps 30 --warmup 3 --no-cpu-baseline --no-headline --no-kernel-events ${BENCH_ARGS:-} > $O/line.json 2> $O/err.txt )
   echo "== ${v:-(defaults)}   $(python3 -c "import json,sys; d=json.loads(open('$O/line.json').read().strip().splitlines()[-1]); print('%.0f img/s under rocprof' % d['value'])" 2>/dev/null)"
   python3 - $(find $O -name '*kernel_trace.csv' | head -1) "${FILTER:-}" "${MIN_US:-5}" <<'P'
 import csv, sys, re, collections

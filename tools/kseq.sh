@@ -1,11 +1,11 @@
 #!/bin/bash
-export FQ_BENCH_MIN_REGION_S=${FQ_BENCH_MIN_REGION_S:-1}   # (tools time with 1 s regions; the driver's plain bench.py run uses its 8 s default)
+export FQ_BENCH_MIN_REGION_S=${FQ_BENCH_MIN_REGION_S:-1}   # (tools time with 1 s regions; bench.py --full defaults to 8 s)
 # The kernels of ONE benchmark step in launch order, with the idle gap in front of each (rocprofv3 kernel trace):
 #   tools/kseq.sh ["VAR=VALUE ..."]        BENCH_ARGS adds bench.py flags
 # Prints the median step (by total span) of the timed steps: per kernel start-to-end us, gap to the previous kernel's end.
 set -u
 R=$(pwd); O=$R/gpurun_out/kseq; rm -rf $O; mkdir -p $O
-( cd /tmp && export TMPDIR=/tmp && export ${1:-NOTHING=1} && rocprofv3 --kernel-trace --output-format csv -d $O -o bench -- python3 $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-headline --no-kernel-events ${BENCH_ARGS:-} > $O/line.json 2> $O/err.txt )
+( cd /tmp && export TMPDIR=/tmp && export ${1:-NOTHING=1} && rocprofv3 --kernel-trace --output-format csv -d $O -o bench -- python3 $R/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-headline --no-kernel-events ${BENCH_ARGS:-} > $O/line.json 2> $O/err.txt )
 python3 - $(find $O -name '*kernel_trace.csv' | head -1) <<'P'
 import csv, sys, re
 rows = sorted(csv.DictReader(open(sys.argv[1])), key=lambda r: int(r["Start_Timestamp"]))

@@ -1,5 +1,5 @@
 #!/bin/bash
-export FQ_BENCH_MIN_REGION_S=${FQ_BENCH_MIN_REGION_S:-1}   # (tools time with 1 s regions; the driver's plain bench.py run uses its 8 s default)
+export FQ_BENCH_MIN_REGION_S=${FQ_BENCH_MIN_REGION_S:-1}   # (tools time with 1 s regions; bench.py --full defaults to 8 s)
 # Round-5 evidence in one GPU call (run from the repo root on the GPU box).  Everything tools/refresh_all.sh collects for the
 # default workload (rocprofv3 tables, PMC traffic incl. the headline tensor, events-vs-rocprof check, SQ counters, calibration
 # kernels, host baseline), then: PMC FETCH / WRITE passes for BASELINE configurations 3 and 4 under offline thresholds (written
@@ -17,8 +17,8 @@ for cfg in "resnet50_v1_channel_w8a8_offline|--model resnet50_v1 --quant-type ch
            "mobilenetv2_1.0_channel_w4a8_offline|--model mobilenetv2_1.0 --quant-type channel --weight-bits 4 --offline"; do
   key=${cfg%%|*}; args=${cfg#*|}
   ( cd /tmp && export TMPDIR=/tmp
-    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_f_$key -o bench -- python3 $R/bench.py $args --steps 3 --warmup 2 --min-region-s 0 --no-cpu-baseline --no-headline --no-kernel-events > /dev/null 2> $O/pmc_f_$key.err
-    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_w_$key -o bench -- python3 $R/bench.py $args --steps 3 --warmup 2 --min-region-s 0 --no-cpu-baseline --no-headline --no-kernel-events > /dev/null 2> $O/pmc_w_$key.err )
+    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_f_$key -o bench -- python3 $R/bench.py --full $args --steps 3 --warmup 2 --min-region-s 0 --no-cpu-baseline --no-headline --no-kernel-events > /dev/null 2> $O/pmc_f_$key.err
+    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_w_$key -o bench -- python3 $R/bench.py --full $args --steps 3 --warmup 2 --min-region-s 0 --no-cpu-baseline --no-headline --no-kernel-events > /dev/null 2> $O/pmc_w_$key.err )
   F=$(find $O/pmc_f_$key -name '*counter_collection.csv' | head -1); W=$(find $O/pmc_w_$key -name '*counter_collection.csv' | head -1)
   python3 tools/pmc_summary.py $F $W $O/pmc_traffic_$key.json "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE around bench.py $args --steps 3 --warmup 2, $TAG" > $O/${TAG}_pmc_$key.txt 2>&1
   cp $O/pmc_traffic_$key.json profiles/pmc_traffic_$key.json      # (the lines below quote it as traffic_from_profiles)
@@ -29,8 +29,8 @@ i=0
 for cfg in "--model resnet50_v1 --quant-type channel" "--model resnet50_v1 --quant-type channel --offline" \
            "--model resnet50_v1 --quant-type channel --wino F43" "--model mobilenetv2_1.0 --quant-type channel --weight-bits 4 --offline"; do
   i=$((i+1))
-  python3 bench.py $cfg --steps 100 --no-cpu-baseline --no-headline >> $O/${TAG}_other_configs.jsonl 2>> $O/other.err
-  ( cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_cfg$i -o bench -- python3 $R/bench.py $cfg --steps 30 --warmup 6 --no-cpu-baseline --no-headline --no-kernel-events > /dev/null 2>> $O/other.err )
+  python3 bench.py --full $cfg --steps 100 --no-cpu-baseline --no-headline >> $O/${TAG}_other_configs.jsonl 2>> $O/other.err
+  ( cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_cfg$i -o bench -- python3 $R/bench.py --full $cfg --steps 30 --warmup 6 --no-cpu-baseline --no-headline --no-kernel-events > /dev/null 2>> $O/other.err )
   head -31 $(find $O/trace_cfg$i -name '*kernel_stats.csv' | head -1) | cut -c1-220 > $O/${TAG}_cfg${i}_kernel_stats_top30.csv
   rm -rf $O/trace_cfg$i
 done
@@ -53,7 +53,7 @@ cp gpurun_out/pmc_sq/summary.txt $O/${TAG}_pmc_sq.txt 2>/dev/null
 bash tools/calib_lines.sh $TAG > gpurun_out/refresh_calib.log 2>&1
 cp gpurun_out/calib/${TAG}_* $O/ 2>/dev/null
 # ---- nn.Conv2D(quantized=True) MobileNet, CLI, first convolutions, pointwise forms ----------------------------------------------
-python3 bench.py --model quantized_mobilenet1.0 > $O/${TAG}_qconv_line.json 2> $O/qconv.err
+python3 bench.py --full --model quantized_mobilenet1.0 > $O/${TAG}_qconv_line.json 2> $O/qconv.err
 bash tools/cli_vs_bench.sh > $O/${TAG}_cli_vs_bench.txt 2>&1
 python3 tools/stembench.py > $O/${TAG}_stembench.txt 2>/dev/null
 ( python3 tools/pwforms.py; python3 tools/pwforms.py --resnet ) > $O/${TAG}_pwforms.txt 2>/dev/null

@@ -1,5 +1,5 @@
 #!/bin/bash
-export FQ_BENCH_MIN_REGION_S=${FQ_BENCH_MIN_REGION_S:-1}   # (tools time with 1 s regions; the driver's plain bench.py run uses its 8 s default)
+export FQ_BENCH_MIN_REGION_S=${FQ_BENCH_MIN_REGION_S:-1}   # (tools time with 1 s regions; bench.py --full defaults to 8 s)
 # Round-6 evidence in one GPU call (run from the repo root on the GPU box): everything tools/refresh_r5.sh collects (default
 # workload: rocprofv3 tables, PMC traffic, events-vs-rocprof check, the driver's line; the other BASELINE configurations with
 # PMC traffic for the offline ones; calibration phases; CLI vs bench), then round 6's own: the recompute pairs alone (kernel
@@ -46,9 +46,9 @@ bash tools/batch_sweep.sh $TAG > gpurun_out/refresh_sweep.log 2>&1
 cp gpurun_out/sweep/${TAG}_batch_sweep.txt gpurun_out/sweep/${TAG}_smi.txt $O/ 2>/dev/null
 python3 tools/sliced_effect.py 2>&1 | grep -v amdgpu > $O/${TAG}_sliced_effect.txt
 for ph in eval calib-naive calib-kl; do
-  FQ_BENCH_SHARE_GPU=1 FQ_BENCH_BACKEND=gloo FQ_DIST_BACKEND=gloo FQ_DIST_SHARE_GPU=1 python3 bench.py --gpus 8 --phase $ph --batch-size 16 --steps 10 --warmup 2 --no-cpu-baseline --no-headline --max-repeats 3 2>> $O/ranks8.err
+  FQ_BENCH_SHARE_GPU=1 FQ_BENCH_BACKEND=gloo FQ_DIST_BACKEND=gloo FQ_DIST_SHARE_GPU=1 python3 bench.py --full --gpus 8 --phase $ph --batch-size 16 --steps 10 --warmup 2 --no-cpu-baseline --no-headline --max-repeats 3 2>> $O/ranks8.err
 done > $O/${TAG}_eight_ranks_one_gpu.jsonl
 for ph in calib-naive; do
-  python3 bench.py --gpus 1 --phase $ph --batch-size 16 --steps 10 --warmup 2 --no-cpu-baseline --no-headline --max-repeats 3 2>> $O/ranks8.err
+  python3 bench.py --full --gpus 1 --phase $ph --batch-size 16 --steps 10 --warmup 2 --no-cpu-baseline --no-headline --max-repeats 3 2>> $O/ranks8.err
 done > $O/${TAG}_one_rank_same_batch.jsonl
 ls -la $O | head -90
