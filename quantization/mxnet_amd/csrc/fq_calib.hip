@@ -26,7 +26,7 @@ __global__ void ema_kernel(float* __restrict__ state, const float* __restrict__ 
 // exactly as distribution_calibrate.py:39-42; an index equal to `bins` (max >= 256: fp32 max + 1e-5 == max) is clamped
 // into the last bin (documented deviation).  Flush: one 64-bit global atomic per non-empty bin and workgroup.
 // ---------------------------------------------------------------------------------------------------------------
-template <bool VEC, bool NT, bool PIPE>
+template <bool VEC, bool NT>
 __global__ __launch_bounds__(kBlock) void histogram_kernel(const float* __restrict__ x, int64_t numel,
                                                            const float* __restrict__ max_dev, int bins,
                                                            unsigned long long* __restrict__ hist,
@@ -67,25 +67,11 @@ __global__ __launch_bounds__(kBlock) void histogram_kernel(const float* __restri
 #pragma unroll
     for (int u = 0; u < kUnroll; ++u) v[u] = ld4<NT>(p + u * kBlock);
     for (int64_t c = rg.begin; c < vend; ++c) {
-      if (PIPE) {
-        // next chunk's loads go out before this chunk's atomics (the last iteration re-reads its own chunk)
-        const f4* pn = p + (c + 1 < vend ? (kChunk / kVec) : 0);
-        f4 w[kUnroll];
+      put8(v);
+      if (c + 1 < vend) {
+        p += kChunk / kVec;
 #pragma unroll
-        for (int u = 0; u < kUnroll; ++u) w[u] = ld4<NT>(pn + u * kBlock);
-        FQ_PIN();
-        put8(v);
-        FQ_PIN();
-#pragma unroll
-        for (int u = 0; u < kUnroll; ++u) v[u] = w[u];
-        p = pn;
-      } else {
-        put8(v);
-        if (c + 1 < vend) {
-          p += kChunk / kVec;
-#pragma unroll
-          for (int u = 0; u < kUnroll; ++u) v[u] = ld4<NT>(p + u * kBlock);
-        }
+        for (int u = 0; u < kUnroll; ++u) v[u] = ld4<NT>(p + u * kBlock);
       }
     }
   }
@@ -229,18 +215,14 @@ int fq_histogram_accumulate(const float* x, int64_t numel, const float* max_dev,
   const int grid = (int)(hg < 1 ? 1 : hg);
   ProfScope prof(FQ_KERNEL_HISTOGRAM, 4.0 * (double)numel, (hipStream_t)stream);
   const size_t lds = (size_t)4 * bins * sizeof(unsigned int);
-  static const int hist_form = env_int("FQ_HIST_FORM", 1);          // bit 0: nontemporal loads, bit 1: pipelined loads
-  // measured on (128,64,112,112), 2 workgroups per CU (profiles/r2_hist_variants.txt): plain 5.28, nontemporal 5.88,
-  // pipelined 5.31, both 5.80 TB/s; 3-4 workgroups per CU are slower in every form
-#define FQ_HIST(V, N, P)                                                                                              \
-  hipLaunchKernelGGL((histogram_kernel<V, N, P>), dim3(grid), dim3(kBlock), lds, (hipStream_t)stream, x, numel,       \
-                     max_dev, bins, (unsigned long long*)hist, (unsigned int*)neg_count)
-  if (!aligned16(x)) FQ_HIST(false, false, false);
-  else if (hist_form == 0) FQ_HIST(true, false, false);
-  else if (hist_form == 1) FQ_HIST(true, true, false);
-  else if (hist_form == 2) FQ_HIST(true, false, true);
-  else FQ_HIST(true, true, true);
-#undef FQ_HIST
+  // aligned tensors: nontemporal loads.  Measured on (128,64,112,112), 2 workgroups per CU (profiles/r2_hist_variants.txt):
+  // plain 5.28, nontemporal 5.88, pipelined 5.31, both 5.80 TB/s; 3-4 workgroups per CU are slower in every form
+  if (!aligned16(x))
+    hipLaunchKernelGGL((histogram_kernel<false, false>), dim3(grid), dim3(kBlock), lds, (hipStream_t)stream, x, numel,
+                       max_dev, bins, (unsigned long long*)hist, (unsigned int*)neg_count);
+  else
+    hipLaunchKernelGGL((histogram_kernel<true, true>), dim3(grid), dim3(kBlock), lds, (hipStream_t)stream, x, numel,
+                       max_dev, bins, (unsigned long long*)hist, (unsigned int*)neg_count);
   FQ_LAUNCH_CHECK();
   return FQ_OK;
 }

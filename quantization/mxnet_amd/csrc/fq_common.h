@@ -9,7 +9,7 @@
 //                      K11 global average pool + statistic, K12 evaluation counters
 //   fq_dwconv.hip      K2c/K2d/K2e depthwise 3x3 with quantise-on-load (LDS tiles / 1 column per lane / 4 columns per lane),
 //                      K2o whole small planes in registers, K2p 14x14 / 7x7 planes as flat 16-byte ranges through an LDS transpose
-//   fq_stem.hip        K2s first convolution 3x3 s2 (3 -> 32) on the vector ALU, K2q 3x3 / 7x7 on the fp32 matrix cores
+//   fq_stem.hip        K2q / K2r first convolution 3x3 / 7x7 s2 on the fp32 matrix cores (K2r: input rows staged in LDS)
 //   fq_conv3x3.hip     K2n dense 3x3 on int8 codes (implicit GEMM over tap and channel)
 //   fq_pw_stream.hip   K2h pointwise on int8 codes, weights resident in LDS (largest planes)
 //   fq_pw_sample.hip   K2r pointwise, one block of 96..128 pixels x 256 / 512 channels per workgroup, output-stationary
@@ -135,10 +135,7 @@ constexpr int kBlock = 256;                       // 4 wavefronts
 constexpr int kVec = 4;                           // floats per lane per access (16 B)
 constexpr int kUnroll = 8;                        // independent 16 B accesses in flight per lane
 constexpr int kChunk = kBlock * kVec * kUnroll;   // 8192 floats = 32 KiB per workgroup step
-#ifndef FQ_MAX_WG_PER_CU
-#define FQ_MAX_WG_PER_CU 8
-#endif
-constexpr int kMaxBlocksPerCU = FQ_MAX_WG_PER_CU;   // grid cap of the streaming kernels (tuning: -DFQ_MAX_WG_PER_CU=6)
+constexpr int kMaxBlocksPerCU = 8;                // grid cap of the streaming kernels
 constexpr float kEps = 1e-10f;                    // ste_func.py:39,41
 
 inline int grid_for(int64_t work_items) {
@@ -209,18 +206,8 @@ __device__ __forceinline__ float block_min(float v, float* red) {
 }
 
 // Order-preserving atomics on fp32 through integer atomics (no CAS loop).
-// (-DFQ_DBG_NOSTAT: an ablation build that drops every statistic atomic.  Its statistics are all zero, hence every threshold,
-// hence every activation: kernels then run 2-6 us faster for reasons that have nothing to do with atomics - see
-// profiles/r3_atomic_probe.txt before reading anything into its timings.)
-#ifdef FQ_DBG_NOSTAT
-#define FQ_STAT_FLUSH_MAX(p, v) ((void)(p), (void)(v))
-#else
 #define FQ_STAT_FLUSH_MAX(p, v) atomicMax((p), (v))
-#endif
 __device__ __forceinline__ void atomic_max_f32(float* addr, float v) {
-#ifdef FQ_DBG_NOSTAT
-  return;
-#endif
   if (v >= 0.0f)
     atomicMax(reinterpret_cast<int*>(addr), __float_as_int(v));
   else
@@ -572,11 +559,7 @@ __device__ __forceinline__ int pack4_codes(int k0, int k1, int k2, int k3, int u
 // once per kernel (`fq_nonneg`).  clip + divide (3) + round-and-convert = 5 instructions instead of 7, and with non-negative
 // codes the four bytes of a dword merge with three shift-ors and ONE xor (mask 0x80808080 for unsigned codes stored
 // re-centred, 0 for signed ones) instead of four additions, three shift-ors and an xor: 6 instead of 9 per value.
-#ifdef FQ_NO_NONNEG                                       // A/B builds: always the general quantiser
-__device__ __forceinline__ bool fq_nonneg(const QParams&) { return false; }
-#else
 __device__ __forceinline__ bool fq_nonneg(const QParams& q) { return q.lo == 0.0f && q.denom > 0.0f; }
-#endif
 __device__ __forceinline__ unsigned fq_nonneg_xor(int ubias) { return ubias == 0 ? 0x80808080u : 0u; }
 __device__ __forceinline__ int fq_code_nonneg(float x, const QParams& q) {
   const float Q = ieee_div_by(fq_clip(x, q), q.rden);
@@ -644,26 +627,19 @@ __device__ __forceinline__ f4 buf_ld_v4f_nt(fq_rsrc r, unsigned voff, unsigned s
 // across it, and holds two wait states - the number LLVM applies on gfx940+ where it does see the hazard), or a burst of
 // `buf_st_v4f_unguarded` followed by ONE `hold_store_data(all the data)` (the asm statements of a guarded store are ordered
 // against each other, which would serialise the LDS reads feeding a burst).  tools/isa_lint.py checks the built library.
-#ifndef FQ_BUFST_NOPS
-#define FQ_BUFST_NOPS 1
-#endif
 __device__ __forceinline__ void buf_st_v4f_unguarded(fq_rsrc r, unsigned voff, unsigned soff, f4 v) {
   typedef unsigned v4u __attribute__((ext_vector_type(4)));
   __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, v), r, (int)voff, (int)soff, 0);
 }
 template <int N>
 __device__ __forceinline__ void hold_store_data(const f4 (&v)[N]) {
-#if FQ_BUFST_NOPS >= 0
 #pragma unroll
   for (int i = 0; i < N; ++i) asm volatile("" : : "v"(v[i]));
-  asm volatile("s_nop %0" : : "n"(FQ_BUFST_NOPS));
-#endif
+  asm volatile("s_nop 1");
 }
 __device__ __forceinline__ void buf_st_v4f(fq_rsrc r, unsigned voff, unsigned soff, f4 v) {
   buf_st_v4f_unguarded(r, voff, soff, v);
-#if FQ_BUFST_NOPS >= 0
-  asm volatile("s_nop %1" : : "v"(v), "n"(FQ_BUFST_NOPS));
-#endif
+  asm volatile("s_nop 1" : : "v"(v));
 }
 
 // max over the wavefront of NON-NEGATIVE floats (|x| statistics), the same in every lane: four DPP steps inside the rows

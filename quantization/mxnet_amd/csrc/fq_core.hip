@@ -103,15 +103,6 @@ const char* fq_build_id(void) {
   return id + 12;
 }
 
-// 1 when this library was built with the named optional part ("pipe": the shelved pipe form of fq_pwconv_i8, csrc/build.py --dev)
-int fq_build_has(const char* feature) {
-  if (feature == nullptr) return 0;
-#ifdef FQ_DEV_FORMS
-  if (strcmp(feature, "pipe") == 0) return 1;
-#endif
-  return 0;
-}
-
 int fq_device_info(char* arch, int arch_len, int* compute_units, int* wavefront) {
   int dev = 0;
   FQ_HIP(hipGetDevice(&dev));

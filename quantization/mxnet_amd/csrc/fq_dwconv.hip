@@ -2,21 +2,7 @@
 // (see fq_common.h for the list of translation units and the design rules)
 #include "fq_common.h"
 
-#ifndef FQ_DWFLAT_NTL
-// the flat form's activation loads carry the nontemporal hint: its input (a 26-103 MB tensor the producer left in the Infinity
-// Cache) is read once - +0.9 % images/s with three batches in flight, five alternating runs (profiles/r5_nt_sweep3.txt; 0 = off)
-#define FQ_DWFLAT_NTL 1
-#endif
-
 namespace {
-
-// Experiment hook: cap the scalar registers of the depthwise kernels (-DFQ_DW_SGPR=80).  A 256-thread workgroup is admitted
-// 8 per CU only with <= 80 SGPRs (MI355X_MICROARCH.md, residency); hipcc uses up to 106 when not told otherwise.
-#ifdef FQ_DW_SGPR
-#define FQ_DW_ATTR __attribute__((amdgpu_num_sgpr(FQ_DW_SGPR)))
-#else
-#define FQ_DW_ATTR
-#endif
 
 // ---------------------------------------------------------------------------------------------------------------
 // K2c: depthwise 3x3 (pad 1, stride S) with quantise-on-load and BN / activation / statistic epilogue.
@@ -39,7 +25,7 @@ struct DwGeom {
 };
 
 template <int S, bool QUANT, bool ONLINE>
-__global__ __launch_bounds__(kBlock) FQ_DW_ATTR void dwconv3x3_kernel(const float* __restrict__ x, const float* __restrict__ wgt,
+__global__ __launch_bounds__(kBlock) void dwconv3x3_kernel(const float* __restrict__ x, const float* __restrict__ wgt,
                                                            const float* __restrict__ bias, float* __restrict__ y,
                                                            DwGeom g, int64_t tiles, const float* __restrict__ in_stat,
                                                            int n, const float* __restrict__ in_thr, float levels,
@@ -212,7 +198,7 @@ struct DwColGeom {
 };
 
 template <int S, bool QUANT, bool ONLINE, int EPI>
-__global__ __launch_bounds__(kBlock) FQ_DW_ATTR void dwconv3x3_cols_kernel(
+__global__ __launch_bounds__(kBlock) void dwconv3x3_cols_kernel(
     const float* __restrict__ x, const float* __restrict__ wgt, const float* __restrict__ bias,
     float* __restrict__ y, DwColGeom g, int64_t total_segs, const float* __restrict__ in_stat, int n,
     const float* __restrict__ in_thr, float levels, int lo_neg_max, float eps, float* __restrict__ cur_max_out,
@@ -489,7 +475,7 @@ struct DwPlanesBlk {
 };
 
 template <int S, bool QUANT, bool ONLINE, int H, int CPL, int EPI>
-__global__ __launch_bounds__(kBlock) FQ_DW_ATTR void dwconv3x3_planes_kernel(
+__global__ __launch_bounds__(kBlock) void dwconv3x3_planes_kernel(
     const float* __restrict__ x, const float* __restrict__ wgt, const float* __restrict__ bias,
     float* __restrict__ y, DwColGeom g, int64_t total_segs, const float* __restrict__ in_stat, int n,
     const float* __restrict__ in_thr, float levels, int lo_neg_max, float eps, float* __restrict__ cur_max_out,
@@ -721,27 +707,13 @@ __global__ __launch_bounds__(kBlock) FQ_DW_ATTR void dwconv3x3_planes_kernel(
 //   C  tile -> registers -> flat 16-byte stores
 // No workgroup barrier: a wavefront only ever touches its own tile (LDS operations of a wavefront complete in order).
 // ---------------------------------------------------------------------------------------------------------------
-// Phase boundary of the flat form.  Default: compiler-level ordering only (LDS operations of one wavefront execute in
-// order).  tools/dw_race_repro.py builds the alternatives to bisect the 28x28 stride-2 irreproducibility:
-//   -DFQ_DWF_SYNC   a workgroup barrier;  -DFQ_DWF_DRAIN  s_waitcnt vmcnt(0) lgkmcnt(0) before going on
-#if defined(FQ_DWF_SYNC)
-#define FQ_DWF_PHASE() __syncthreads()
-#elif defined(FQ_DWF_DRAIN)
-#define FQ_DWF_PHASE()                                             \
-  do {                                                             \
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");         \
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");    \
-    __builtin_amdgcn_wave_barrier();                               \
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");         \
-  } while (0)
-#else
+// Phase boundary of the flat form: compiler-level ordering only (LDS operations of one wavefront execute in order).
 #define FQ_DWF_PHASE()                                             \
   do {                                                             \
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");         \
     __builtin_amdgcn_wave_barrier();                               \
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");         \
   } while (0)
-#endif
 
 struct DwFlatGeom {
   int C;
@@ -776,10 +748,6 @@ __global__ __launch_bounds__(kBlock) void dwconv3x3_flat_kernel(
   __shared__ f4 otile[kBlock / 64][DOWN ? NLO * 64 : 1];  // stride 1 writes its results over the tile rows already consumed
   __shared__ unsigned k_stat[kStatSlots];
   if (threadIdx.x < kStatSlots) k_stat[threadIdx.x] = 0u;
-#ifdef FQ_DWF_PADLDS                                      // bisect: more static LDS = fewer workgroups per CU
-  __shared__ unsigned lds_pad[FQ_DWF_PADLDS / 4];
-  if (threadIdx.x == 0 && n < 0) lds_pad[n & 15] = 1u;
-#endif
   PW_STAMP(0);
   const unsigned lane = threadIdx.x & 63u;
   const unsigned wave = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -813,10 +781,11 @@ __global__ __launch_bounds__(kBlock) void dwconv3x3_flat_kernel(
     const unsigned left = base < planes ? planes - base : 0u;
     const unsigned np = left < (unsigned)P ? left : (unsigned)P;
     const unsigned lim = TAIL_OK ? np * (IN / 4) : (np == (unsigned)P ? (unsigned)NFI : 0u);   // 16-byte groups that exist
+    // nontemporal: the input (a 26-103 MB tensor the producer left in the Infinity Cache) is read once - +0.9 % images/s with
+    // three batches in flight, five alternating runs (profiles/r5_nt_sweep3.txt)
 #pragma unroll
     for (int i = 0; i < NLI; ++i)
-      k.raw[i] = FQ_DWFLAT_NTL ? buf_ld_v4f_nt(rx, (lane + 64u * i) < lim ? lane * 16u : kOob, base * (IN * 4u) + 1024u * i)
-                               : buf_ld_v4f(rx, (lane + 64u * i) < lim ? lane * 16u : kOob, base * (IN * 4u) + 1024u * i);
+      k.raw[i] = buf_ld_v4f_nt(rx, (lane + 64u * i) < lim ? lane * 16u : kOob, base * (IN * 4u) + 1024u * i);
     const unsigned ch = (b_lane && j < left) ? fast_mod(base + j, g.by_c) : 0u;
     k.w03 = buf_ld_v4f(rw, ch * 36u, 0);
     k.w47 = buf_ld_v4f(rw, ch * 36u, 16);
@@ -845,15 +814,9 @@ __global__ __launch_bounds__(kBlock) void dwconv3x3_flat_kernel(
   __syncthreads();                                        // statistic table zeroed
   for (unsigned blk = blk_begin; blk < blk_end; ++blk) {
     if (blk == blk_begin + 1) PW_STAMP(2);
-#ifdef FQ_DWF_NOPREFETCH                                  // bisect: no block requested ahead
-    if (blk != blk_begin) issue(blk, nxt);
-    FQ_PIN();
-    Blk cur = nxt;
-#else
     Blk cur = nxt;
     FQ_PIN();
     if (blk + 1 < blk_end) issue(blk + 1, nxt);
-#endif
     FQ_PIN();
     const unsigned base = (blk * (kBlock / 64) + wave) * P;
     const unsigned left = base < planes ? planes - base : 0u;
@@ -871,16 +834,6 @@ __global__ __launch_bounds__(kBlock) void dwconv3x3_flat_kernel(
     float m = 0.0f;
     const bool is_out = b_lane && j < left;
     if (b_lane) {
-#ifdef FQ_DWF_NODPP                                       // bisect: ds_bpermute shuffles instead of DPP wave shifts
-      auto left_of = [&](float v) -> float {
-        const float t = __shfl_up(v, 1);
-        return first ? 0.0f : t;
-      };
-      auto right_of = [&](float v) -> float {
-        const float t = __shfl_down(v, 1);
-        return last ? 0.0f : t;
-      };
-#else
       auto left_of = [&](float v) -> float {              // (every lane takes the shift; the edge lanes drop it afterwards)
         const float t = lane_prev(v);
         return first ? 0.0f : t;
@@ -889,7 +842,6 @@ __global__ __launch_bounds__(kBlock) void dwconv3x3_flat_kernel(
         const float t = lane_next(v);
         return last ? 0.0f : t;
       };
-#endif
       if (PAIR) {
         float* lp = my_tile + j * IN + pos * 2;
         const f2 w0 = splat2(cur.w03.x), w1 = splat2(cur.w03.y), w2 = splat2(cur.w03.z), w3 = splat2(cur.w03.w),
@@ -1012,11 +964,7 @@ __global__ __launch_bounds__(kBlock) void dwconv3x3_flat_kernel(
         else atomic_max_f32(stat_out + sample, m);
       }
     }
-#if defined(FQ_DWF_SYNC) || defined(FQ_DWF_DRAIN)
-    FQ_DWF_PHASE();
-#else
     __builtin_amdgcn_wave_barrier();                      // (the next block's phase A overwrites the tile)
-#endif
   }
   PW_STAMP(3);
   if (has_stat) {
@@ -1038,7 +986,7 @@ __global__ __launch_bounds__(kBlock) void dwconv3x3_flat_kernel(
 // output, which the consumer does find there (measured in the model: 64 @112x112 stride 2, 411 MB in / 103 MB out, 110 -> 99 us;
 // with nontemporal stores too, or on the 205 MB inputs of the stride-1 layers, the step gets slower)
 template <int S, bool QUANT, bool ONLINE, bool NT, int EPI>
-__global__ __launch_bounds__(kBlock) FQ_DW_ATTR void dwconv3x3_cols4_kernel(
+__global__ __launch_bounds__(kBlock) void dwconv3x3_cols4_kernel(
     const float* __restrict__ x, const float* __restrict__ wgt, const float* __restrict__ bias,
     float* __restrict__ y, DwColGeom g, int64_t total_segs, const float* __restrict__ in_stat, int n,
     const float* __restrict__ in_thr, float levels, int lo_neg_max, float eps, float* __restrict__ cur_max_out,
@@ -1046,11 +994,7 @@ __global__ __launch_bounds__(kBlock) FQ_DW_ATTR void dwconv3x3_cols4_kernel(
   // Input rows are fetched in BURSTS of D rows (double buffered): the D loads of a burst leave the wave back to back
   // and hit the same DRAM pages; one load per step (a ring) spreads them ~700 cycles apart, and with thousands of
   // waves each streaming its own plane every access then opens a new page.
-#ifndef FQ_DW4_D1
-#define FQ_DW4_D1 4
-#define FQ_DW4_D2 2
-#endif
-  constexpr int D = (S == 1) ? FQ_DW4_D1 : FQ_DW4_D2;
+  constexpr int D = (S == 1) ? 4 : 2;
   constexpr int kStatSlots = 16;
   __shared__ unsigned k_stat[kStatSlots];
   if (threadIdx.x < kStatSlots) k_stat[threadIdx.x] = 0u;
@@ -1302,7 +1246,7 @@ static int dwconv3x3_impl(const float* x, const float* w, const float* bias, flo
   // (28x28: 40.1 -> 34.6 us stride 1.  Stride 2 on 28x28 was dropped in round 2 because 0.05 % of its outputs changed from run
   // to run at full size; round 3 found the cause - NOT a data race: a VALU write of a 16-byte buffer store's data register
   // right behind the store, a hazard hipcc does not guard when soffset is a register (fq_common.h at buf_st_v4f,
-  // profiles/r3_dw_flat_race.txt, tools/dw_race_repro.py, tools/isa_lint.py) - every instantiation of this kernel had the
+  // profiles/r3_dw_flat_race.txt, tools/isa_lint.py) - every instantiation of this kernel had the
   // pattern one instruction further away.  With the stores guarded the form is exact at every occupancy.  Through round 4 it
   // was built and tested but not chosen by shape - one batch at a time it was no faster than the four-columns-per-lane form
   // (28.3 us against ~25; whole step 1.1967 against 1.1919 ms, profiles/r3_dw_flat_race.txt); with three batches in flight and
@@ -1439,7 +1383,7 @@ static int dwconv3x3_impl(const float* x, const float* w, const float* bias, flo
     // every workgroup resident at once, each walking a contiguous range of blocks.  6 per CU: the kernels use ~100 scalar
     // registers, and a CU admits 256-thread workgroups 8 at a time only up to 80 (MI355X_MICROARCH.md, residency) - with
     // 8 per CU asked for, a quarter of the grid ran as a second, thin round (14x14 layers: 31.7 -> 28.0 us; capping the
-    // scalar registers with -DFQ_DW_SGPR=80 instead makes all 8 resident and is no faster)
+    // scalar registers at 80 instead makes all 8 resident and is no faster)
     static const int dw_wg_per_cu = env_int("FQ_DW_WG_PER_CU", 6);
     const int grid = (int)(nblk < (int64_t)num_cu() * dw_wg_per_cu ? nblk : (int64_t)num_cu() * dw_wg_per_cu);
     const float levels = act_levels(in_width, in_flags);
@@ -1504,7 +1448,7 @@ static int dwconv3x3_impl(const float* x, const float* w, const float* bias, flo
     // every workgroup resident at once, each walking a contiguous range of blocks.  6 per CU: the kernels use ~100 scalar
     // registers, and a CU admits 256-thread workgroups 8 at a time only up to 80 (MI355X_MICROARCH.md, residency) - with
     // 8 per CU asked for, a quarter of the grid ran as a second, thin round (14x14 layers: 31.7 -> 28.0 us; capping the
-    // scalar registers with -DFQ_DW_SGPR=80 instead makes all 8 resident and is no faster)
+    // scalar registers at 80 instead makes all 8 resident and is no faster)
     static const int dw_wg_per_cu = env_int("FQ_DW_WG_PER_CU", 6);
     const int grid = (int)(nblk < (int64_t)num_cu() * dw_wg_per_cu ? nblk : (int64_t)num_cu() * dw_wg_per_cu);
     const float levels = act_levels(in_width, in_flags);

@@ -4,25 +4,16 @@
 // rules; the C16 layout: include/fakequant.h at fq_pwconv_i8_c16)
 #include "fq_common.h"
 
-// tuning builds: -DFQ_DW16_V=3 (the general output quantiser everywhere; bit 4 = the short one for values that cannot be
-// negative), -DFQ_DW16_RING=<3|4|5> / -DFQ_DW16_RING2=<2|3>: input rows (stride 2: row pairs) in flight per lane.
-#ifndef FQ_DW16_V
-#define FQ_DW16_V 7
-#endif
+namespace {
+
+using namespace fqi;
+
 // input rows in flight per lane, stride 1 / row PAIRS, stride 2: ordinary buffer loads the compiler waits for.  (Issued and
 // awaited by hand - inline assembly and hand-counted s_waitcnt, because hipcc drains the ring where the paths into the
 // unrolled walk meet - six rows were another +0.4 % images/s, but the compiler does not know that such registers are pending:
 // it spilled and copied them, and full-size repeats beside a competing stream differed - tests/test_gpu_determinism.py.)
-#ifndef FQ_DW16_RING
-#define FQ_DW16_RING 4
-#endif
-#ifndef FQ_DW16_RING2                  // (3 pairs: 124-128 registers, -0.2 % images/s)
-#define FQ_DW16_RING2 2
-#endif
-
-namespace {
-
-using namespace fqi;
+constexpr int kDw16Ring = 4;
+constexpr int kDw16Ring2 = 2;          // (3 pairs: 124-128 registers, -0.2 % images/s)
 
 // The arithmetic is that of fq_dwconv3x3 under an offline threshold, bit for bit: x^ = code * sx (one fp32 rounding, the
 // value LinearQuantizeSTE returns), acc = fmaf chain over (ky, kx) in row-major order from 0, + bias, * bn_scale + bn_shift,
@@ -145,7 +136,7 @@ __global__ __launch_bounds__(256, 4) void dwconv3x3_c16_kernel(
   // S == 1: entry j <-> input row j - 1 (output row t cooks entry t + 2);  S == 2: row -1 (zeros), then pairs: entry t <-> input
   // rows 2t, 2t + 1
   // (the run-time epilogue keeps bias and activation selectors alive: a shorter ring there, or it spills)
-  constexpr int NR = S == 1 ? (EPI == kEpiRuntime ? 3 : FQ_DW16_RING) : FQ_DW16_RING2;
+  constexpr int NR = S == 1 ? (EPI == kEpiRuntime ? 3 : kDw16Ring) : kDw16Ring2;
   Raw ring[NR], ring_b[S == 1 ? 1 : NR], first;
   if (S == 1) {
 #pragma unroll
@@ -282,7 +273,7 @@ __global__ __launch_bounds__(256, 4) void dwconv3x3_c16_kernel(
       }
     }
   };
-  if ((FQ_DW16_V & 4) && fq_nonneg(qc)) walk(std::true_type{});      // (behind a ReLU every clipped value is >= 0, whatever the consumer's range)
+  if (fq_nonneg(qc)) walk(std::true_type{});      // (behind a ReLU every clipped value is >= 0, whatever the consumer's range)
   else walk(std::false_type{});
   if (EPI == kEpiBnRelu6) m = fminf(m, 6.0f);
   if (stat_out != nullptr) {

@@ -24,22 +24,12 @@ namespace {
 // the vector ALU (the quantiser is ~8.5 instructions per value at ~4.3 cycles each, tools/valu_probe.hip) and the matrix
 // pipe work at the same time.
 constexpr int kSmpPanelWords = 2 * 128 * 4;             // 2 channel halves x 128 pixels x 16 codes
-// tools/pw_ablate.py: -DFQ_PWSMP_ABL=<bits> removes one ingredient at a time (results are then WRONG; timing only):
-// 1 MFMAs, 2 quantiser arithmetic, 4 barrier per chunk, 8 activation loads, 16 output stores, 32 A-fragment loads, 64 whole loop
-#ifndef FQ_PWSMP_ABL
-#define FQ_PWSMP_ABL 0
-#endif
-#ifndef FQ_PWSMP_NTL
-#define FQ_PWSMP_NTL 0       // A/B builds: 1 = activation loads with the nontemporal hint (profiles/r5_nt_sweep3.txt)
-#endif
-#ifndef FQ_PWSMP_LB4
-#define FQ_PWSMP_LB4 1
-#endif
-
-#ifndef FQ_PWSMP_RESLDS
-#define FQ_PWSMP_RESLDS 1    // A/B builds: 0 = the residual operand through registers on every shape
-#endif
-// one LDS-DMA wave-instruction (fq_pw_pipe.hip, tools/ldsdma_probe.hip): lane l's 16 bytes at (rsrc base + voff + soff) land at LDS
+// vector instructions issued before the first MFMA of a chunk and between two MFMAs (the quantiser's: ~80 per chunk, ~56 with
+// the short quantiser of non-negative quotients, suffix NN)
+constexpr int kSmpHead = 40, kSmpSlice = 5, kSmpHeadNN = 24, kSmpSliceNN = 4;
+constexpr int kSmpPF = 4;             // chunks of activations requested ahead (two channel tiles per wavefront)
+constexpr int kSmpRA = 2;             // groups of residual values in flight (two channel tiles x four pixel tiles: 2 x 16 registers)
+// one LDS-DMA wave-instruction (tools/ldsdma_probe.hip): lane l's 16 bytes at (rsrc base + voff + soff) land at LDS
 // byte address lds_base + 16 l; a lane whose offset is out of the resource's range gets zeros
 __device__ __forceinline__ void smp_dma16(v4i rsrc, unsigned voff, unsigned soff, unsigned lds_base) {
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
@@ -65,12 +55,12 @@ struct PwSampleGeom {
 // PT: 32-pixel tiles of an ITEM - 4 (96..128 pixels) or 2 (up to 64 pixels).  A chunk is always 4096 values, 8 per thread:
 //     PT = 4: 32 channels x 128 pixels, one K-step of 32 per chunk;  PT = 2: 64 channels x 64 pixels, KS = 2 K-steps per chunk.
 // NI: items per workgroup (round 3).  The form is output-stationary: an item's outputs leave at its end, and with one item
-//     per workgroup and one workgroup per CU the whole chip first only loads and then only stores (tools/pw_ablate.py,
+//     per workgroup and one workgroup per CU the whole chip first only loads and then only stores (ablation builds,
 //     profiles/r3_pw_ablate.txt: 512 -> 512 @14x14 25.1 us; without the stores 18.1, without the loads 20.6, without both 14.2,
 //     without MFMAs AND quantiser 23.0 - loads and stores do not overlap).  With NI = 2 the workgroup's block is cut into two
 //     items of <= 64 pixels so that the stores of the first are in flight while the second loads - built, bit-exact, and
 //     measured SLOWER on every layer (31.1 against 24.8 us on 512 -> 512 @14x14: twice the A fragments from L2, an epilogue
-//     in the middle of the MFMA stream): kept as a tuning build only (-DFQ_PWSMP_BUILD_NI2, FQ_PWSMP_NI=2).
+//     in the middle of the MFMA stream): removed; every instantiation has NI = 1.
 //     Planes of fewer than 64 pixels taken whole (7x7; the plane is not a multiple of four pixels: its last pixel is requested
 //     by a 4-byte load of its own) are one item of PT = 2.
 // RES: a residual operand of y's shape is added after BatchNorm, before the activation (the shortcut of a ResNet unit).
@@ -79,7 +69,7 @@ struct PwSampleGeom {
 //     values go to an LDS tile [channel][pixel]; thread t then adds up channel t's pixels in the order and the precision
 //     fq_global_avg_pool_stat adds them (0 .. HW - 1, fp64) and stores the mean: y is (n, Cout), stat_out the per-sample max|mean|.
 template <int KT, int CTW, int PT, bool RES, int NI, bool GAP = false>
-__global__ __launch_bounds__(512, (CTW == 1 && FQ_PWSMP_LB4) ? 4 : ((CTW == 1 || PT == 2) ? 2 : 1)) void pwconv_sample_kernel(
+__global__ __launch_bounds__(512, CTW == 1 ? 4 : (PT == 2 ? 2 : 1)) void pwconv_sample_kernel(
     const float* __restrict__ x, const int8_t* __restrict__ wfrag, const float* __restrict__ wscale,
     const int* __restrict__ wsum, const float* __restrict__ bias, float* __restrict__ y, PwSampleGeom g,
     const float* __restrict__ in_stat, int n, const float* __restrict__ in_thr, float levels, int lo_neg_max, float eps,
@@ -92,7 +82,7 @@ __global__ __launch_bounds__(512, (CTW == 1 && FQ_PWSMP_LB4) ? 4 : ((CTW == 1 ||
   constexpr int NCH = NW * CTW * 32;                                    // output channels of one workgroup (256 or 512)
   // RL: the residual operand arrives by LDS-DMA (two channel tiles x four pixel tiles only: 128 accumulator registers leave room
   // for two groups of residual values, i.e. four exposed memory latencies per item - see the epilogue)
-  constexpr bool RL = RES && PT == 4 && CTW == 2 && NI == 1 && FQ_PWSMP_RESLDS;
+  constexpr bool RL = RES && PT == 4 && CTW == 2 && NI == 1;
   static_assert(!GAP || (PT == 2 && NI == 1 && !RL), "the pooling epilogue takes whole planes (one item of two pixel tiles)");
   extern __shared__ __attribute__((aligned(16))) unsigned char smp_dyn[];   // RL: 8 x 16 KB, [wavefront][32 channels][128 pixels]
   constexpr int KS = 4 / PT;                                            // K-steps of 32 channels per chunk
@@ -100,24 +90,10 @@ __global__ __launch_bounds__(512, (CTW == 1 && FQ_PWSMP_LB4) ? 4 : ((CTW == 1 ||
   constexpr int TI = NI * KI;                                           // chunk iterations of the workgroup
   static_assert(PT == 4 || PT == 2, "pixel tiles per item");
   static_assert(KT % KS == 0, "K / 32 must be a multiple of the K-steps per chunk");
-#ifndef FQ_PWSMP_HEAD
-#define FQ_PWSMP_HEAD 40
-#define FQ_PWSMP_SLICE 5
-#endif
-#ifndef FQ_PWSMP_HEAD_NN
-#define FQ_PWSMP_HEAD_NN 24
-#define FQ_PWSMP_SLICE_NN 4
-#endif
-#ifndef FQ_PWSMP_PF
-#define FQ_PWSMP_PF 4
-#endif
-#ifndef FQ_PWSMP_RA
-#define FQ_PWSMP_RA 2                  // groups of residual values in flight (two channel tiles x four pixel tiles: 2 x 16 registers)
-#endif
   // chunks requested ahead (8 registers each); fewer with one channel tile per wavefront, which then fits 128 registers
   // = TWO workgroups per CU, whose load and store phases overlap (256 -> 256 @28x28 43.9 -> 39.3 us; K / 32 >= 16 only fits
   // them with two chunks ahead)
-  constexpr int PF_ = CTW == 1 ? ((KT >= 16 || NI == 2) ? FQ_PWSMP_PF - 2 : FQ_PWSMP_PF - 1) : FQ_PWSMP_PF;
+  constexpr int PF_ = CTW == 1 ? (KT >= 16 ? kSmpPF - 2 : kSmpPF - 1) : kSmpPF;
   constexpr int PF = PF_ < TI ? PF_ : TI;
   __shared__ __attribute__((aligned(16))) unsigned panel[2][kSmpPanelWords];
   __shared__ __attribute__((aligned(16))) float c_sxw[NCH], c_bsc[NCH], c_bsh[NCH], c_bias[NCH];
@@ -199,16 +175,11 @@ __global__ __launch_bounds__(512, (CTW == 1 && FQ_PWSMP_LB4) ? 4 : ((CTW == 1 ||
   };
   constexpr bool RAGGED = PT == 2 && NI == 1;
   auto issue = [&](int it, Chunk& c) __attribute__((always_inline)) {  // `it`: chunk iteration = item * KI + chunk of the item
+    (void)lane;      // (lane stays in this closure and a_frag's: without it the optimiser assigns the CTW = 2 kernels' registers anew)
     const int item = it / KI, ki = it % KI;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      if (FQ_PWSMP_ABL & 8) {
-        c.v[j] = (f4){(float)it, (float)lane, 1.0f, 2.0f};
-        if (RAGGED) c.r[j] = 0.0f;
-        continue;
-      }
-      c.v[j] = FQ_PWSMP_NTL ? buf_ld_v4f_nt(xr, xo[item], (unsigned)(ki * KS * 32 + j) * plane4 + (ipix0[item] - pix0) * 4u)
-                            : buf_ld_v4f(xr, xo[item], (unsigned)(ki * KS * 32 + j) * plane4 + (ipix0[item] - pix0) * 4u);
+      c.v[j] = buf_ld_v4f(xr, xo[item], (unsigned)(ki * KS * 32 + j) * plane4 + (ipix0[item] - pix0) * 4u);
       if (RAGGED) c.r[j] = buf_ld_f32(xr, xo1, (unsigned)(ki * KS * 32 + j) * plane4);
     }
   };
@@ -223,7 +194,7 @@ __global__ __launch_bounds__(512, (CTW == 1 && FQ_PWSMP_LB4) ? 4 : ((CTW == 1 ||
   const fq_rsrc wr = make_rsrc(wfrag + (((int64_t)ctg0 * KT) << 10), (int64_t)ct_here * KT * 1024);
   const unsigned loff = (unsigned)lane * 16u;
   auto a_frag = [&](int c, int kt) __attribute__((always_inline)) {
-    if (FQ_PWSMP_ABL & 32) return (v4i){c + kt, lane, 3, 4};
+    (void)lane;
     return buf_ld_v4i(wr, loff, (unsigned)((c * KT + kt) << 10));
   };
   constexpr int AD = 2;                                                 // A fragments requested ahead (chunks)
@@ -281,7 +252,6 @@ __global__ __launch_bounds__(512, (CTW == 1 && FQ_PWSMP_LB4) ? 4 : ((CTW == 1 ||
     }
     unsigned char* dst = reinterpret_cast<unsigned char*>(panel[it & 1]) + pw_off;
     auto pair = [&](float a, float b2) -> unsigned short {
-      if (FQ_PWSMP_ABL & 2) return (unsigned short)(__float_as_uint(a) ^ (__float_as_uint(b2) >> 7));
       if (decltype(nn_c)::value) {                                      // 5-instruction quantiser of non-negative quotients
         const unsigned u = (unsigned)fq_code_nonneg(a, q) | ((unsigned)fq_code_nonneg(b2, q) << 8);
         return (unsigned short)(u ^ nn_xor16);
@@ -330,7 +300,7 @@ __global__ __launch_bounds__(512, (CTW == 1 && FQ_PWSMP_LB4) ? 4 : ((CTW == 1 ||
     // requests that are all in flight while tile 0 is stored.  vmcnt counts loads and stores in issue order: before group gq of
     // tile 1 is read, what may still be outstanding is everything issued after its request - counted below.
     constexpr int NG = CTW * 4;                                         // groups of four channels per wavefront
-    constexpr int RA = (!RES || RL) ? 1 : (16 * PT * NG <= 64 ? NG : (PT == 4 ? FQ_PWSMP_RA : NG));
+    constexpr int RA = (!RES || RL) ? 1 : (16 * PT * NG <= 64 ? NG : (PT == 4 ? kSmpRA : NG));
     const float* const rl_rd = reinterpret_cast<const float*>(smp_dyn + 16384u * (unsigned)wave) + (4 * h) * 128 + pl;
     float resv[RES ? RA * 4 * PT : 1];
     auto res_issue = [&](int g_) __attribute__((always_inline)) {
@@ -406,10 +376,6 @@ __global__ __launch_bounds__(512, (CTW == 1 && FQ_PWSMP_LB4) ? 4 : ((CTW == 1 ||
               v.y = act_rt(v.y, act);
             }
             const unsigned so = (unsigned)(c * 32 + 8 * gq + r) * plane4;
-            if (FQ_PWSMP_ABL & 16) {
-              m = fmaxf(fmaxf(m, fabsf(v.x)), fabsf(v.y));
-              continue;
-            }
             if (GAP) {                               // (PT = 2: pixel tiles 0 and 1; the tile keeps [channel][pixel])
               float* const tp = reinterpret_cast<float*>(smp_dyn) + ((ctl0 + c) * 32 + 8 * gq + 4 * h + r) * g.HW + pl;
               tp[0] = v.x;
@@ -451,8 +417,7 @@ __global__ __launch_bounds__(512, (CTW == 1 && FQ_PWSMP_LB4) ? 4 : ((CTW == 1 ||
   // PF chunks earlier, and item i's epilogue sits between the two iterations.
   auto chunk_loop = [&](auto nn_c) __attribute__((always_inline)) {
     constexpr bool NN = decltype(nn_c)::value;
-    // vector instructions per chunk: ~56 with the short quantiser, ~80 with the general one
-    constexpr int HEAD = NN ? FQ_PWSMP_HEAD_NN : FQ_PWSMP_HEAD, SLICE = NN ? FQ_PWSMP_SLICE_NN : FQ_PWSMP_SLICE;
+    constexpr int HEAD = NN ? kSmpHeadNN : kSmpHead, SLICE = NN ? kSmpSliceNN : kSmpSlice;
     quant_to_panel(0, buf[0], nn_c);
     if (PF < TI) issue(PF, buf[0]);
     FQ_PIN();
@@ -468,8 +433,7 @@ __global__ __launch_bounds__(512, (CTW == 1 && FQ_PWSMP_LB4) ? 4 : ((CTW == 1 ||
 #pragma unroll
     for (int ki = 0; ki < KI; ++ki) {
       const int it = item * KI + ki;
-      if (!(FQ_PWSMP_ABL & 4) || it == 0)
-        __syncthreads();                                                // panel[it & 1] complete (and, first time, the constants)
+      __syncthreads();                                                  // panel[it & 1] complete (and, first time, the constants)
       if (it == 0) PW_STAMP(6);
       if (it == TI / 2) PW_STAMP(7);
       const unsigned* pb = &panel[it & 1][bq_off];
@@ -484,8 +448,7 @@ __global__ __launch_bounds__(512, (CTW == 1 && FQ_PWSMP_LB4) ? 4 : ((CTW == 1 ||
         for (int pt = 0; pt < PT; ++pt)
 #pragma unroll
           for (int c = 0; c < CTW; ++c) {
-            if (FQ_PWSMP_ABL & 1) acc[pt][c][it & 15] += bfrag[ks][pt][it & 3] ^ ring[it % (AD + 1)][ks][c][it & 3];
-            else acc[pt][c] = __builtin_amdgcn_mfma_i32_32x32x32_i8(ring[it % (AD + 1)][ks][c], bfrag[ks][pt], acc[pt][c], 0, 0, 0);
+            acc[pt][c] = __builtin_amdgcn_mfma_i32_32x32x32_i8(ring[it % (AD + 1)][ks][c], bfrag[ks][pt], acc[pt][c], 0, 0, 0);
           }
       if (it + 1 < TI) {
         quant_to_panel(it + 1, buf[(it + 1) % PF], nn_c);
@@ -504,8 +467,7 @@ __global__ __launch_bounds__(512, (CTW == 1 && FQ_PWSMP_LB4) ? 4 : ((CTW == 1 ||
     }
     }
   };
-  if (FQ_PWSMP_ABL & 64) __syncthreads();
-  else if (fq_nonneg(q)) chunk_loop(std::true_type{});
+  if (fq_nonneg(q)) chunk_loop(std::true_type{});
   else chunk_loop(std::false_type{});
   PW_STAMP(2);
   finish_item(NI - 1);
@@ -600,56 +562,48 @@ int pw_try_sample(const PwCall& a, bool* taken) {
   t.qbase = (int)(quads / nb);
   t.qextra = (int)(quads % nb);
   const bool res = a.residual != nullptr;
-  // items per workgroup: blocked planes are cut into two items of two pixel tiles each (NI = 2, PT = 2: the first item's
-  // stores overlap the second item's loads) or taken as one item of four (NI = 1, PT = 4; round 2)
-  // MEASURED (profiles/r3_pw_experiments.txt): two items are SLOWER everywhere - 512 -> 512 @14x14 31.1 us against 24.8,
-  // 256 -> 256 @28x28 46.8 against 40.5, 128 -> 256 @28x28 36.7 against 34.3, 256 -> 512 @14x14 21.0 against 18.6 - so one item
-  // is what the shape-based choice takes; the two-item instantiations are only built with -DFQ_PWSMP_BUILD_NI2 (tuning).
-  static const int ni_tune = env_int("FQ_PWSMP_NI", 0);                 // tuning: 2 = two items (needs FQ_PWSMP_BUILD_NI2)
-  const int ni = (!small && ni_tune == 2 && !res) ? 2 : 1;
-  const int pt = (small || ni == 2) ? 2 : 4;
+  // one item per workgroup: blocked planes as four pixel tiles (PT = 4; round 2), whole small planes as two.  Two items of two
+  // pixel tiles each (the first item's stores overlapping the second item's loads) were MEASURED SLOWER everywhere
+  // (profiles/r3_pw_experiments.txt): 512 -> 512 @14x14 31.1 us against 24.8, 256 -> 256 @28x28 46.8 against 40.5,
+  // 128 -> 256 @28x28 36.7 against 34.3, 256 -> 512 @14x14 21.0 against 18.6.
+  const int pt = small ? 2 : 4;
   const int64_t grid = (a.n + 7) / 8 * t.CS * nb * 8;
   FQ_REQUIRE(grid < (1ll << 31), "fq_pwconv_i8: too many workgroups for the sample form");
   const int8_t* wfrag = a.wcodes + rows_pad * a.cin_pad;                // second half of fq_weight_codes' buffer
   if (int rc = pw_zero_stat(a)) return rc;
   bool launched = false;
-#define FQ_PWSMP_CASE_R(KT_, CTW_, PT_, RES_, NI_)                                                                     \
-  if (!a.gap && kt == KT_ && ctw == CTW_ && pt == PT_ && res == RES_ && ni == NI_) {                                   \
+#define FQ_PWSMP_CASE_R(KT_, CTW_, PT_, RES_)                                                                          \
+  if (!a.gap && kt == KT_ && ctw == CTW_ && pt == PT_ && res == RES_) {                                                \
     /* (the residual operand staged in LDS: 8 wavefronts x 16 KB beside the 18 KB of panels and constants) */          \
-    constexpr size_t dyn_ = (RES_ && PT_ == 4 && CTW_ == 2 && NI_ == 1 && FQ_PWSMP_RESLDS) ? 8 * 16384 : 0;             \
+    constexpr size_t dyn_ = (RES_ && PT_ == 4 && CTW_ == 2) ? 8 * 16384 : 0;                                           \
     if (dyn_ != 0) {                                                                                                   \
       static const bool attr_ok =                                                                                      \
-          hipFuncSetAttribute(reinterpret_cast<const void*>(&pwconv_sample_kernel<KT_, CTW_, PT_, RES_, NI_>),         \
+          hipFuncSetAttribute(reinterpret_cast<const void*>(&pwconv_sample_kernel<KT_, CTW_, PT_, RES_, 1>),           \
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_) == hipSuccess;                    \
       FQ_REQUIRE(attr_ok, "fq_pwconv_i8: cannot raise the dynamic LDS limit of the sample kernel");                    \
     }                                                                                                                  \
-    hipLaunchKernelGGL((pwconv_sample_kernel<KT_, CTW_, PT_, RES_, NI_>), dim3((unsigned)grid), dim3(512), dyn_, a.st,  \
+    hipLaunchKernelGGL((pwconv_sample_kernel<KT_, CTW_, PT_, RES_, 1>), dim3((unsigned)grid), dim3(512), dyn_, a.st,    \
                        a.x, wfrag, a.wscale, (const int*)a.wsum, a.bias, a.y, t, a.in_stat, (int)a.n, a.in_thr,         \
                        a.levels, a.lo_neg, kEps, a.out_current_max, a.bn_scale, a.bn_shift, a.act, a.stat_out,          \
                        a.residual);                                                                                    \
     launched = true;                                                                                                   \
   }
-#define FQ_PWSMP_CASE(KT_, CTW_, PT_, NI_) FQ_PWSMP_CASE_R(KT_, CTW_, PT_, false, NI_)
+#define FQ_PWSMP_CASE(KT_, CTW_, PT_) FQ_PWSMP_CASE_R(KT_, CTW_, PT_, false)
   // one item of four pixel tiles (round 2)
-  FQ_PWSMP_CASE(4, 1, 4, 1) FQ_PWSMP_CASE(4, 2, 4, 1) FQ_PWSMP_CASE(8, 1, 4, 1) FQ_PWSMP_CASE(8, 2, 4, 1)
-  FQ_PWSMP_CASE(16, 1, 4, 1) FQ_PWSMP_CASE(16, 2, 4, 1) FQ_PWSMP_CASE(32, 1, 4, 1) FQ_PWSMP_CASE(32, 2, 4, 1)
-#ifdef FQ_PWSMP_BUILD_NI2
-  // two items of two pixel tiles
-  FQ_PWSMP_CASE(4, 1, 2, 2) FQ_PWSMP_CASE(4, 2, 2, 2) FQ_PWSMP_CASE(8, 1, 2, 2) FQ_PWSMP_CASE(8, 2, 2, 2)
-  FQ_PWSMP_CASE(16, 1, 2, 2) FQ_PWSMP_CASE(16, 2, 2, 2) FQ_PWSMP_CASE(32, 1, 2, 2) FQ_PWSMP_CASE(32, 2, 2, 2)
-#endif
+  FQ_PWSMP_CASE(4, 1, 4) FQ_PWSMP_CASE(4, 2, 4) FQ_PWSMP_CASE(8, 1, 4) FQ_PWSMP_CASE(8, 2, 4)
+  FQ_PWSMP_CASE(16, 1, 4) FQ_PWSMP_CASE(16, 2, 4) FQ_PWSMP_CASE(32, 1, 4) FQ_PWSMP_CASE(32, 2, 4)
   // whole small planes
-  FQ_PWSMP_CASE(16, 1, 2, 1) FQ_PWSMP_CASE(16, 2, 2, 1) FQ_PWSMP_CASE(32, 1, 2, 1) FQ_PWSMP_CASE(32, 2, 2, 1)
-  FQ_PWSMP_CASE(64, 1, 2, 1) FQ_PWSMP_CASE(64, 2, 2, 1)                 // (2048 -> 512 @7x7, ResNet-50's last stage)
+  FQ_PWSMP_CASE(16, 1, 2) FQ_PWSMP_CASE(16, 2, 2) FQ_PWSMP_CASE(32, 1, 2) FQ_PWSMP_CASE(32, 2, 2)
+  FQ_PWSMP_CASE(64, 1, 2) FQ_PWSMP_CASE(64, 2, 2)                       // (2048 -> 512 @7x7, ResNet-50's last stage)
   // with a residual operand: the last 1x1 convolutions of the ResNet bottlenecks (128 -> 512 @28x28, 256 -> 1024 @14x14)
-  FQ_PWSMP_CASE_R(4, 2, 4, true, 1) FQ_PWSMP_CASE_R(8, 2, 4, true, 1) FQ_PWSMP_CASE_R(16, 2, 4, true, 1)
+  FQ_PWSMP_CASE_R(4, 2, 4, true) FQ_PWSMP_CASE_R(8, 2, 4, true) FQ_PWSMP_CASE_R(16, 2, 4, true)
   // ... and 512 -> 2048 @7x7 (a whole small plane)
-  FQ_PWSMP_CASE_R(16, 2, 2, true, 1)
+  FQ_PWSMP_CASE_R(16, 2, 2, true)
 #undef FQ_PWSMP_CASE
 #undef FQ_PWSMP_CASE_R
   // ... with the global average pooling behind them in the same launch (fq_pwconv_i8_gap): an LDS tile of NCH x HW floats
 #define FQ_PWSMP_GAP(KT_, CTW_, RES_)                                                                                  \
-  if (a.gap && kt == KT_ && ctw == CTW_ && pt == 2 && res == RES_ && ni == 1) {                                        \
+  if (a.gap && kt == KT_ && ctw == CTW_ && pt == 2 && res == RES_) {                                                   \
     static const bool attr_ok =                                                                                        \
         hipFuncSetAttribute(reinterpret_cast<const void*>(&pwconv_sample_kernel<KT_, CTW_, 2, RES_, 1, true>),         \
                             hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) == hipSuccess;                     \

@@ -36,19 +36,14 @@ int pw_split16_launch(const PwCall& a, const void* geom, int kt, int cw, int64_t
   FQ_PWS16_BOTH(8) FQ_PWS16_BOTH(16) FQ_PWS16_BOTH(32) FQ_PWS16_BOTH(64)
 #undef FQ_PWS16_BOTH
   // codes in, fp32 out AND a code copy of it (the closing 1x1 of a ResNet unit: K = 64 ... 512, Cout = 256 ... 2048)
-#ifndef FQ_PWS16_DUAL_D                 // tuning: ring depth and wavefronts per SIMD of the two-tile dual-output instantiations
-#define FQ_PWS16_DUAL_D 2
-#endif
-#ifndef FQ_PWS16_DUAL_LB
-#define FQ_PWS16_DUAL_LB 4
-#endif
+  constexpr int kDualD = 2, kDualLB = 4;   // ring depth and wavefronts per SIMD of the two-tile dual-output instantiations
 #define FQ_PWS16_DUAL(KT_) FQ_PWS16_CASE_D(KT_, 1, (KT_ < 7 ? KT_ : 7), 4, true, false, true) \
-  FQ_PWS16_CASE_D(KT_, 2, (KT_ < FQ_PWS16_DUAL_D ? KT_ : FQ_PWS16_DUAL_D), FQ_PWS16_DUAL_LB, true, false, true)
+  FQ_PWS16_CASE_D(KT_, 2, (KT_ < kDualD ? KT_ : kDualD), kDualLB, true, false, true)
   FQ_PWS16_DUAL(2) FQ_PWS16_DUAL(4) FQ_PWS16_DUAL(8) FQ_PWS16_DUAL(16)
 #undef FQ_PWS16_DUAL
   // ... both outputs subsampled (fq_pwconv_i8_c16_dual_sub2: the last unit of a ResNet-v1 stage, two channel tiles per wavefront)
 #define FQ_PWS16_DUAL_SUB(KT_) \
-  FQ_PWS16_CASE_S(KT_, 2, (KT_ < FQ_PWS16_DUAL_D ? KT_ : FQ_PWS16_DUAL_D), FQ_PWS16_DUAL_LB, true, false, true, true)
+  FQ_PWS16_CASE_S(KT_, 2, (KT_ < kDualD ? KT_ : kDualD), kDualLB, true, false, true, true)
   FQ_PWS16_DUAL_SUB(2) FQ_PWS16_DUAL_SUB(4) FQ_PWS16_DUAL_SUB(8) FQ_PWS16_DUAL_SUB(16)
 #undef FQ_PWS16_DUAL_SUB
 #undef FQ_PWS16_CASE_S
@@ -56,10 +51,10 @@ int pw_split16_launch(const PwCall& a, const void* geom, int kt, int cw, int64_t
 #define FQ_PWS16_DUAL8(KT_)                                                                                            \
   if (nw == 8 && kt == KT_ && cw == 2 && in16 && !out16 && dual && !sub) {                                             \
     static const bool attr_ok =                                                                                        \
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&pwconv_split_kernel<KT_, 2, FQ_PWS16_DUAL_D, FQ_PWS16_DUAL_LB, 8, true, false, true>), \
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&pwconv_split_kernel<KT_, 2, kDualD, kDualLB, 8, true, false, true>), \
                             hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) == hipSuccess;                      \
     FQ_REQUIRE(attr_ok, "fq_pwconv_i8_c16_dual: cannot raise the dynamic LDS limit of the split kernel");              \
-    hipLaunchKernelGGL((pwconv_split_kernel<KT_, 2, FQ_PWS16_DUAL_D, FQ_PWS16_DUAL_LB, 8, true, false, true>), dim3((unsigned)grid), \
+    hipLaunchKernelGGL((pwconv_split_kernel<KT_, 2, kDualD, kDualLB, 8, true, false, true>), dim3((unsigned)grid), \
                        dim3(512), lds, a.st, a.x, wfrag, a.wscale, (const int*)a.wsum, a.bias, a.y, t, a.in_stat, (int)a.n, \
                        a.in_thr, a.levels, a.lo_neg, kEps, a.out_current_max, a.bn_scale, a.bn_shift, a.act, a.stat_out, \
                        a.residual, a.out_thr);                                                                         \

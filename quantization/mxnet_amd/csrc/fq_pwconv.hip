@@ -132,7 +132,7 @@ static int pwconv_dispatch(const float* x, const int8_t* wcodes, const float* ws
   c.eval_labels = eval_labels; c.eval_counters = eval_counters; c.eval_ws = eval_ws;
   c.sub = sub;
   c.gap = gap;
-  static const int pw_form = env_int("FQ_PW_FORM", 0);      // 0 auto, 1 two kernels, 3 stream, 6 split, 7 sample, 8 rows, 9 pipe
+  static const int pw_form = env_int("FQ_PW_FORM", 0);      // 0 auto, 1 two kernels, 3 stream, 6 split, 7 sample, 8 rows
   c.form = (in_c16 || c.out_thr) ? 6 : (eval_labels ? 8 : (forced_form ? forced_form : pw_form));
   // tuning: FQ_PW_FORM_AT="<pixels per plane>:<form>[,...]" names a form for the layers of one plane size (A/Bs of a form choice
   // inside a model, where a kernel's time alone is not what decides - DESIGN.md 3.6); parsed once
@@ -159,10 +159,10 @@ static int pwconv_dispatch(const float* x, const int8_t* wcodes, const float* ws
       for (int k = 0; k < at.n; ++k)
         if (at.hw[k] == (int)hw) c.form = at.form[k];
   }
-  FQ_REQUIRE(c.form == 0 || c.form == 1 || c.form == 3 || c.form == 6 || c.form == 7 || c.form == 8 || c.form == 9,
+  FQ_REQUIRE(c.form == 0 || c.form == 1 || c.form == 3 || c.form == 6 || c.form == 7 || c.form == 8,
              "fq_pwconv_i8: unknown "
-             "form %d (1 two kernels, 3 stream, 6 split, 7 sample, 8 rows, 9 pipe; the panel / chunk / tile forms 2, 4, 5 were retired "
-             "in favour of the split form)", c.form);
+             "form %d (1 two kernels, 3 stream, 6 split, 7 sample, 8 rows; the panel / chunk / tile forms 2, 4, 5 were retired "
+             "in favour of the split form, the pipe form 9 in favour of the sample form)", c.form);
   FQ_REQUIRE(stride == 1 || c.form == 0 || c.form == 6, "fq_pwconv_i8_strided: only the split form reads strided inputs");
   FQ_REQUIRE(residual == nullptr || c.form != 1, "fq_pwconv_i8_strided: the two-kernel form takes no residual operand");
   // algorithmic bytes: the input pixels the outputs need, the outputs, and the residual operand when there is one
@@ -200,15 +200,6 @@ static int pwconv_dispatch(const float* x, const int8_t* wcodes, const float* ws
   }
   FQ_REQUIRE(c.form != 8, "fq_pwconv_i8: the rows form takes planes of one pixel");
   if (!(in_c16 || out_thr)) {
-#ifdef FQ_DEV_FORMS
-    if (int rc = pw_try_pipe(c, &taken)) return rc;
-    if (taken) return FQ_OK;
-    FQ_REQUIRE(c.form != 9, "fq_pwconv_i8: the pipe form takes stride 1, no residual, fp32 in and out, Cin = 256 or 512, Cout a "
-               "multiple of 512 and planes of a multiple of four pixels (16..1024)");
-#else
-    FQ_REQUIRE(c.form != 9, "fq_pwconv_i8: the pipe form (9) was measured and shelved (DESIGN.md 3.3): this library was built "
-               "without it - `python -m quantization.mxnet_amd.csrc.build --dev` builds libfakequant_dev.so with it");
-#endif
     if (int rc = pw_try_sample(c, &taken)) return rc;
     if (taken) return FQ_OK;
   } else if (out_thr && !in_c16) {                      // C16 output on the largest planes: the streaming form writes it too

@@ -41,18 +41,12 @@ constexpr int kRowSlack = 8;          // floats in front of each row buffer (a s
 
 // slabs in flight per lane: a ring of NB buffers of 16 values, the loads of slab q + NB - 1 issued before slab q is quantised
 // (stride 1 keeps 32 more partial sums per channel tile: two buffers there)
-#ifdef FQ_PWDW_OCC3      // tuning build: three wavefronts per SIMD (at most 168 registers), two buffers
-#define FQ_PWDW_OCC __attribute__((amdgpu_waves_per_eu(3, 3)))
-template <int KT, int S> struct PwDwRing { static constexpr int NB = 2; };
-#else
-#define FQ_PWDW_OCC
 template <int KT, int S> struct PwDwRing { static constexpr int NB = S == 1 ? 2 : (KT <= 2 ? 3 : 4); };
-#endif
 
 // FAST 0: every epilogue decided at run time, general quantisers; 1: the fused-inference case - no bias, BatchNorm and ReLU
 // (ReLU6 when `relu6`) behind both convolutions, unsigned activations (both clip ranges start at 0)
 template <int KT, int CW, int S, int LZ, int FAST>
-__global__ __launch_bounds__(512) FQ_PWDW_OCC void pwdw_kernel(
+__global__ __launch_bounds__(512) void pwdw_kernel(
     const float* __restrict__ x, const int8_t* __restrict__ wfrag, const float* __restrict__ wscale,
     const int* __restrict__ wsum, const float* __restrict__ bias1, PwDwGeom g, const float* __restrict__ in_stat, int n,
     const float* __restrict__ in_thr, float levels1, int lo_neg1, float eps, const float* __restrict__ bn1_scale,
@@ -284,31 +278,8 @@ __global__ __launch_bounds__(512) FQ_PWDW_OCC void pwdw_kernel(
 #pragma unroll
           for (int kt = 0; kt < KT; ++kt)
             acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(afrag[kt], ldsW[((ct * KT + kt) << 6) + wl], acc, 0, 0, 0);
-#ifdef FQ_PWDW_PK        // measured and left out: 64 packed instead of 128 plain instructions per channel tile and row, 2 % SLOWER
-                         // (pair 1: 98.0 against 95.9 us, the step -0.36 %: profiles/r6_pwdw_packed_ab.txt)
-          if constexpr (FAST != 0 && NN) {
-            // the fused-inference chain two pixels at a time as packed fp32 instructions (two IEEE operations each: the same
-            // values)
-            typedef float f2 __attribute__((ext_vector_type(2)));
-#pragma unroll
-            for (int k = 0; k < 16; k += 2) {
-              f2 v = (f2){(float)(acc[k] + k_zs[j]), (float)(acc[k + 1] + k_zs[j])};
-              v = v * (f2){k_sxw[j], k_sxw[j]};
-              v = v * (f2){k_bsc1[j], k_bsc1[j]};
-              v = v + (f2){k_bsh1[j], k_bsh1[j]};
-              f2 c = (f2){fq_clip(v.x, qc), fq_clip(v.y, qc)};
-              f2 q = c * (f2){fq2.y, fq2.y};
-              const f2 nd = (f2){-fq2.d, -fq2.d};
-              const f2 r = __builtin_elementwise_fma(q, nd, c);          // fma(-q, d, c) = fma(q, -d, c)
-              q = __builtin_elementwise_fma(r, (f2){fq2.y, fq2.y}, q);
-              q = q + (f2){0.49999997f, 0.49999997f};
-              q = (f2){truncf(q.x), truncf(q.y)};
-              q = q * (f2){q2.scale, q2.scale};
-              e[k + 1] = q.x;
-              e[k + 2] = q.y;
-            }
-          } else
-#endif
+          // (the fused-inference chain two pixels at a time as packed fp32 instructions - 64 instead of 128 per channel tile and
+          // row - was measured 2 % SLOWER: pair 1 98.0 against 95.9 us, the step -0.36 %, profiles/r6_pwdw_packed_ab.txt)
 #pragma unroll
           for (int k = 0; k < 16; ++k) {
             float v = (float)(acc[k] + k_zs[j]) * k_sxw[j];
@@ -664,28 +635,9 @@ __global__ __launch_bounds__(kBlock, 3) void pw_stat_kernel(
       const int qn = kt + NB - 1;
       issue(t + qn / KT, qn % KT, raw[(PH * KT + kt + NB - 1) % NB]);
       FQ_PIN();
-#if defined(FQ_PST_ABLATE) && FQ_PST_ABLATE == 1       // ablation build: the loads alone (values folded so that they stay alive)
-      {
-        float (&mine)[16] = raw[(PH * KT + kt) % NB];
-        float mm = 0.0f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) mm = fmaxf(mm, mine[i]);
-        afrag[kt] = (v4i){__float_as_int(mm), 0, 0, 0};
-      }
-#else
       quant(kt, raw[(PH * KT + kt) % NB], nn_c);
-#endif
       FQ_PIN();
     }
-#if defined(FQ_PST_ABLATE)                             // ... 2: loads + quantiser, no matrix cores, no reduction
-    {
-      int keep = 0;
-#pragma unroll
-      for (int kt = 0; kt < KT; ++kt) keep |= afrag[kt][0] | afrag[kt][1] | afrag[kt][2] | afrag[kt][3];
-      if (keep == 0x7fffffff) my[lane] = keep;
-      return;
-    }
-#endif
     const unsigned j0 = (unsigned)t * 32u, j1 = j0 + 31u < cols ? j0 + 31u : cols - 1;
     const unsigned s0 = fast_div(j0, g.hw), s1 = fast_div(j1, g.hw);
     if (s0 != cur) {
@@ -906,16 +858,8 @@ int fq_pwdw_fused(const float* x, const int8_t* wcodes, const float* wscale, con
   const double in_elems = (double)n * cin * h * w, mid_elems = (double)n * cout * h * w, out_elems = (double)n * cout * ho * wo;
   ProfScope prof(FQ_KERNEL_DWCONV, 4.0 * (mid_elems + out_elems), st, 4.0 * (in_elems + out_elems));
   const unsigned grid = (unsigned)(n * p.bands);
-// (-DFQ_PWDW_DEV: a tuning build with two instantiations - the first two pairs of MobileNet1.0 - instead of 48)
-#ifdef FQ_PWDW_DEV
-#define FQ_PWDW_INST(KT_, CW_, S_, LZ_, F_) ((F_) == 1 && (LZ_) == 0 && (CW_) == 2 && (((KT_) == 1 && (S_) == 2) || ((KT_) == 2 && (S_) == 1)))
-#else
-#define FQ_PWDW_INST(KT_, CW_, S_, LZ_, F_) true
-#endif
 #define FQ_PWDW_GO(KT_, CW_, S_, LZ_, F_)                                                                                   \
-  if constexpr (!FQ_PWDW_INST(KT_, CW_, S_, LZ_, F_)) {                                                                    \
-    return fail(FQ_ERR_INVALID, "fq_pwdw_fused: not instantiated in this (FQ_PWDW_DEV) build");                            \
-  } else {                                                                                                                 \
+  {                                                                                                                        \
     static const bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&pwdw_kernel<KT_, CW_, S_, LZ_, F_>),    \
                                                     hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) == hipSuccess; \
     FQ_REQUIRE(attr_ok, "fq_pwdw_fused: cannot raise the dynamic LDS limit");                                              \

@@ -1,114 +1,18 @@
-// libfakequant — K2s first convolution 3x3 stride 2 (3 -> 32)
+// libfakequant — K2q / K2r first convolution 3x3 / 7x7 stride 2 (3 -> 32 / 64) on the fp32 matrix cores
 // (see fq_common.h for the list of translation units and the design rules)
 #include "fq_common.h"
 
 namespace {
 
 // ---------------------------------------------------------------------------------------------------------------
-// K2s: the first ("stem") convolution of the ImageNet nets: dense 3x3, stride 2, pad 1, 3 input channels -> COUT,
-// fp32 (the reference excludes the first convolution from quantisation), with BatchNorm/activation folded into the store
-// and the per-sample max|y| the next (quantised) layer needs.  A lane owns one output pixel: it gathers its 27 inputs
-// (zero padding by clamped address + select), then for every tap multiplies by the COUT weights of that tap, read from
-// an LDS copy of the tap-major weights with broadcast ds_read_b128 (4 weights per read).  (Feeding the weights through
-// SGPRs looked cheaper but hipcc hoists all 864 scalar loads and spills them to VGPR lanes: a v_readlane per FMA.)
-// Stores are contiguous along the lanes for every channel.  MIOpen needed 0.14 ms + a separate 0.08 ms BatchNorm/ReLU/statistic
-// pass for this layer at batch 128; the layer moves 77 MB in + 205 MB out.
-// ---------------------------------------------------------------------------------------------------------------
-template <int CIN, int COUT>
-__global__ __launch_bounds__(kBlock) void stem_conv3x3s2_kernel(
-    const float* __restrict__ x, const float* __restrict__ wt /*[CIN][3][3][COUT]*/, const float* __restrict__ bias,
-    float* __restrict__ y, int H, int W, int Ho, int Wo, int tiles_per_wg, const float* __restrict__ bn_scale,
-    const float* __restrict__ bn_shift, int act, float* __restrict__ stat_out) {
-  __shared__ float red[4];
-  __shared__ __attribute__((aligned(16))) float wl[CIN * 9 * COUT];
-  for (int i = threadIdx.x; i < CIN * 9 * COUT; i += kBlock) wl[i] = wt[i];
-  __syncthreads();
-  const int smp = blockIdx.y;
-  const int HWo = Ho * Wo;
-  const float* xs = x + (int64_t)smp * CIN * H * W;
-  float* ys = y + (int64_t)smp * COUT * HWo;
-  const bool has_bn = bn_scale != nullptr;
-  float m = 0.0f;
-  for (int t = 0; t < tiles_per_wg; ++t) {
-    const int pix = (blockIdx.x * tiles_per_wg + t) * kBlock + threadIdx.x;
-    if ((blockIdx.x * tiles_per_wg + t) * kBlock >= HWo) break;          // uniform
-    const bool valid = pix < HWo;
-    const int pc = valid ? pix : HWo - 1;
-    const int oy = pc / Wo, ox = pc - oy * Wo;
-    float in[CIN][3][3];
-#pragma unroll
-    for (int ky = 0; ky < 3; ++ky) {
-      const int iy = 2 * oy - 1 + ky;
-      const bool yin = iy >= 0 && iy < H;
-      const int iyc = iy < 0 ? 0 : (iy < H ? iy : H - 1);
-#pragma unroll
-      for (int kx = 0; kx < 3; ++kx) {
-        const int ix = 2 * ox - 1 + kx;
-        const bool inb = yin && ix >= 0 && ix < W;
-        const int ixc = ix < 0 ? 0 : (ix < W ? ix : W - 1);
-#pragma unroll
-        for (int ci = 0; ci < CIN; ++ci) {
-          const float v = xs[((int64_t)ci * H + iyc) * W + ixc];
-          in[ci][ky][kx] = inb ? v : 0.0f;
-        }
-      }
-    }
-    float acc[COUT];
-#pragma unroll
-    for (int co = 0; co < COUT; ++co) acc[co] = 0.0f;
-#pragma unroll
-    for (int ci = 0; ci < CIN; ++ci)
-#pragma unroll
-      for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx) {
-          const float v = in[ci][ky][kx];
-          const f4* wtap = reinterpret_cast<const f4*>(wl + ((ci * 3 + ky) * 3 + kx) * COUT);
-          FQ_PIN();                              // one tap's weights at a time (else all 216 reads are hoisted: spills)
-#pragma unroll
-          for (int c4 = 0; c4 < COUT / 4; ++c4) {
-            const f4 wv = wtap[c4];
-            acc[4 * c4 + 0] = __builtin_fmaf(wv.x, v, acc[4 * c4 + 0]);
-            acc[4 * c4 + 1] = __builtin_fmaf(wv.y, v, acc[4 * c4 + 1]);
-            acc[4 * c4 + 2] = __builtin_fmaf(wv.z, v, acc[4 * c4 + 2]);
-            acc[4 * c4 + 3] = __builtin_fmaf(wv.w, v, acc[4 * c4 + 3]);
-          }
-          // ... and the accumulators pinned per tap: otherwise the optimiser sinks every channel's 27 FMAs down to that
-          // channel's store and keeps all 864 weights live instead
-#pragma unroll
-          for (int c8 = 0; c8 < COUT / 8; ++c8)
-            asm volatile("" : "+v"(acc[8 * c8]), "+v"(acc[8 * c8 + 1]), "+v"(acc[8 * c8 + 2]), "+v"(acc[8 * c8 + 3]),
-                              "+v"(acc[8 * c8 + 4]), "+v"(acc[8 * c8 + 5]), "+v"(acc[8 * c8 + 6]), "+v"(acc[8 * c8 + 7]));
-        }
-#pragma unroll
-    for (int co = 0; co < COUT; ++co) {
-      float v = acc[co];
-      if (bias != nullptr) v = v + bias[co];
-      if (has_bn) {
-        v = v * bn_scale[co];
-        v = v + bn_shift[co];
-      }
-      v = act_rt(v, act);
-      if (valid) {
-        ys[(int64_t)co * HWo + pix] = v;
-        m = fmaxf(m, fabsf(v));
-      }
-    }
-  }
-  if (stat_out != nullptr) {
-    m = block_max(m, red);
-    if (threadIdx.x == 0) atomic_max_f32(stat_out + smp, m);
-  }
-}
-
-
-// ---------------------------------------------------------------------------------------------------------------
-// K2q: the same first convolution (K x K, stride 2, padding K/2, 3 input channels) on the fp32 MATRIX cores, for 3x3 -> 32
-// (MobileNets) and 7x7 -> 64 (ResNets).  v_mfma_f32_32x32x2_f32 runs at the fp32 vector rate, so this buys no FLOPs - it buys
-// instruction slots: one MFMA replaces 64 v_fma per lane-pair and the VALU is left with addresses and the epilogue (the VALU
-// form above issues 864 FMAs + 216 LDS reads per pixel-wave and reaches ~35 % of the vector peak).  It is BIT-IDENTICAL to the
-// VALU form and its oracle: the instruction accumulates as an fmaf chain in ascending k (tools/mfma_f32_probe.hip: 1024 of
-// 1024 outputs bit-equal), and k runs over (ci, ky, kx) exactly as the chain above; padded taps multiply a zero.
+// K2q: the first ("stem") convolution of the ImageNet nets (K x K, stride 2, padding K/2, 3 input channels, fp32: the
+// reference excludes it from quantisation) on the fp32 MATRIX cores, for 3x3 -> 32 (MobileNets) and 7x7 -> 64 (ResNets), with
+// BatchNorm / activation folded into the store and the per-sample max|y| the next (quantised) layer needs.
+// v_mfma_f32_32x32x2_f32 runs at the fp32 vector rate, so this buys no FLOPs - it buys instruction slots: one MFMA replaces 64
+// v_fma per lane-pair and the VALU is left with addresses and the epilogue (an fmaf form on the vector ALU issued 864 FMAs + 216
+// LDS reads per pixel-wave and reached ~35 % of the vector peak).  It is BIT-IDENTICAL to the fmaf chain over k = (ci, ky, kx)
+// in ascending order that its host twin computes: the instruction accumulates as such a chain (tools/mfma_f32_probe.hip: 1024
+// of 1024 outputs bit-equal), and padded taps multiply a zero.
 // GEMM view: D[co][pixel] += W[co][k] * X[k][pixel].  A tile is 32 consecutive output pixels; lane l supplies, per step s,
 // W[co = l % 32][k = 2 s + l / 32] (3x3: 14 registers per wavefront for good; 7x7: LDS) and X[k][pixel l % 32]: ONE 4-byte
 // buffer load per lane and step, gathered straight from NCHW (each input pixel is used by ~K^2 / 4 outputs: L1 / L2 serve the
@@ -116,27 +20,13 @@ __global__ __launch_bounds__(kBlock) void stem_conv3x3s2_kernel(
 // channel - the layout of the pointwise kernels: BatchNorm / activation / statistic on store, 128-byte lines per channel.
 // ---------------------------------------------------------------------------------------------------------------
 typedef float v16f __attribute__((ext_vector_type(16)));
-#ifndef FQ_STEM_CH
-#define FQ_STEM_CH 16
-#endif
-#ifndef FQ_STEM_NTS
-// nontemporal stores of the first convolution's fp32 output (205 MB at batch 128, read once by the first depthwise layer): +1.5 %
-// images/s with three batches in flight in two alternating A/Bs of 5-6 rounds (profiles/r5_nt_sweep4.txt, r5_nt_sweep5.txt; 0 = off)
-#define FQ_STEM_NTS 1
-#endif
-#ifndef FQ_STEM_NTL
-#define FQ_STEM_NTL 0        // A/B builds: 1 = the gather of the input image with the nontemporal hint
-#endif
-#ifndef FQ_STEM_INTERLEAVE
+constexpr int kStemCh = 16;                // steps of the 7x7 form whose loads are in flight together
+// The fp32 output (205 MB at batch 128, read once by the first depthwise layer) is stored with the nontemporal hint: +1.5 %
+// images/s with three batches in flight in two alternating A/Bs of 5-6 rounds (profiles/r5_nt_sweep4.txt, r5_nt_sweep5.txt).
 // The four wavefronts of a workgroup take the workgroup's tiles in turn (tile T0 + wave, + 4, ...) instead of a quarter of the
 // range each: they then walk the same output rows at the same time and their input rows meet in the L1 / L2 - a wavefront on
 // its own 14 output rows keeps 78 KB of input alive, the 16-32 wavefronts of a CU together far more than the caches hold
-// (PMC: 106.6 MB fetched for the 77 MB input).  0: the round-4 assignment (A/B builds).
-#define FQ_STEM_INTERLEAVE 1
-#endif
-#ifndef FQ_STEM_NOSTORE      // tuning only (tools/stembench.py): the statistic without the stores - what a recomputation would cost
-#define FQ_STEM_NOSTORE 0
-#endif
+// (PMC: 106.6 MB fetched for the 77 MB input).
 
 // Tile bookkeeping is 32-bit and incremental (host: fewer than 2^31 tiles; the wavefront's range, the divisions by the
 // tiles per image and by the output width arrive as per / rem and multiplicative inverses).  With 64-bit tile indices hipcc
@@ -165,7 +55,7 @@ __global__ __launch_bounds__(kBlock) void stem_mfma_kernel(
   const int H = g.H, W = g.W, Ho = g.Ho, Wo = g.Wo;
   constexpr int K = 3 * KS * KS, NS = (K + 1) / 2, CT = COUT / 32, PAD = KS / 2;
   constexpr bool WREG = NS * CT <= 16;                                  // weights in registers (3x3 -> 32), else LDS
-  constexpr int CH = NS < 16 ? NS : FQ_STEM_CH;                         // steps whose loads are in flight together
+  constexpr int CH = NS < 16 ? NS : kStemCh;                            // steps whose loads are in flight together
   constexpr int kSlots = 8;
   __shared__ __attribute__((aligned(16))) float wl[NS * 2 * COUT];      // [k][co], zero row for the padded k
   __shared__ __attribute__((aligned(16))) float c_bias[COUT], c_bsc[COUT], c_bsh[COUT];   // per-channel epilogue constants
@@ -185,13 +75,13 @@ __global__ __launch_bounds__(kBlock) void stem_mfma_kernel(
   const int h = lane >> 5, pl = lane & 31;
   const int HWo = Ho * Wo;
   const bool has_bn = bn_scale != nullptr, has_stat = stat_out != nullptr;
-  const unsigned wid = blockIdx.x * 4u + (unsigned)wave, wid0 = blockIdx.x * 4u;
+  const unsigned wid0 = blockIdx.x * 4u;
   // the workgroup's tiles [wg_begin, wg_end) = those of its four wavefronts; a wavefront takes every TSTEP-th of them
-  constexpr unsigned TSTEP = FQ_STEM_INTERLEAVE ? 4u : 1u;
+  constexpr unsigned TSTEP = 4u;
   const unsigned wg_begin = wid0 * g.per + (wid0 < g.rem ? wid0 : g.rem);
   const unsigned wid1 = wid0 + 4u, wg_end = wid1 * g.per + (wid1 < g.rem ? wid1 : g.rem);
-  const unsigned t_begin = FQ_STEM_INTERLEAVE ? wg_begin + (unsigned)wave : wid * g.per + (wid < g.rem ? wid : g.rem);
-  const unsigned t_end = FQ_STEM_INTERLEAVE ? wg_end : t_begin + g.per + (wid < g.rem ? 1u : 0u);
+  const unsigned t_begin = wg_begin + (unsigned)wave;
+  const unsigned t_end = wg_end;
   const unsigned s_base = fast_div(wid0 * g.per + (wid0 < g.rem ? wid0 : g.rem), g.by_tpi);
   float areg[WREG ? NS * CT : 1];
   if (WREG) {
@@ -247,7 +137,7 @@ __global__ __launch_bounds__(kBlock) void stem_mfma_kernel(
     const bool v1 = k1 < K && ((px.ym >> ky1) & (px.xm >> kx1) & 1u) != 0u;
     const bool v = h ? v1 : v0;
     const unsigned off = (unsigned)px.pixoff + (h ? t1 : t0);
-    return FQ_STEM_NTL ? buf_ld_f32_nt(xr, v ? off : 0x80000000u, 0u) : buf_ld_f32(xr, v ? off : 0x80000000u, 0u);
+    return buf_ld_f32(xr, v ? off : 0x80000000u, 0u);
   };
   auto rsrc_of = [&](const Pix& px) __attribute__((always_inline)) {
     return make_rsrc(reinterpret_cast<const char*>(x) + (int64_t)px.smp * x_img, x_img);
@@ -340,10 +230,7 @@ __global__ __launch_bounds__(kBlock) void stem_mfma_kernel(
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           float v = dw_finish<EPI, !FOLD>(acc[ct][4 * gq + r], bias != nullptr, bch[r], has_bn, bsc[r], bsh[r], act);
-          if (!OUT16 && !FQ_STEM_NOSTORE) {
-            if (FQ_STEM_NTS) buf_st_f32_nt(yr, yo, (unsigned)(ct * 32 + 8 * gq + r) * HWo4, v);
-            else buf_st_f32(yr, yo, (unsigned)(ct * 32 + 8 * gq + r) * HWo4, v);
-          }
+          if (!OUT16) buf_st_f32_nt(yr, yo, (unsigned)(ct * 32 + 8 * gq + r) * HWo4, v);
           vq[r] = v;
           m = FOLD ? fmaxf(m, v) : fmaxf(m, fabsf(v));
         }
@@ -385,7 +272,7 @@ __global__ __launch_bounds__(kBlock) void stem_mfma_kernel(
 // ---------------------------------------------------------------------------------------------------------------
 // K2r (round 6, last hours): the 3x3 -> 32 first convolution with its INPUT staged in LDS.  K2q gathers its B operand from global
 // memory - 14 four-byte loads per lane and tile with an 8-byte lane stride - and without its stores it still takes 53 us for an
-// 18 us matrix chain (tools/stembench.py, -DFQ_STEM_NOSTORE): the texture path bounds it, as it bounded the 7x7 head until
+// 18 us matrix chain (measured with the stores left out): the texture path bounds it, as it bounded the 7x7 head until
 // its input rows were staged (fq_stem_pool.hip, profiles/r6_stem_pool_lds_ab.txt).  Here a workgroup of eight wavefronts walks
 // down a band of output rows of ONE image, four rows (Wo / 8 tiles of 32 consecutive pixels: whole 128-byte lines per channel,
 // as before) per step; the nine input rows 8 q - 1 .. 8 q + 7 of step q live in LDS ([slot = (iy + 1) mod 17][ci][4 zeros | W |
@@ -521,8 +408,7 @@ __global__ __launch_bounds__(512, EPI == kEpiRuntime ? 2 : 4) void stem3_rows_ke
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const float v = dw_finish<EPI>(acc[4 * gq + r], bias != nullptr, bch[r], has_bn, bsc[r], bsh[r], act);
-          if (FQ_STEM_NTS) buf_st_f32_nt(yr, yo, (unsigned)(8 * gq + r) * HWo4, v);
-          else buf_st_f32(yr, yo, (unsigned)(8 * gq + r) * HWo4, v);
+          buf_st_f32_nt(yr, yo, (unsigned)(8 * gq + r) * HWo4, v);
           m = fmaxf(m, fabsf(v));
         }
       }
@@ -573,7 +459,6 @@ static int stem_launch(const float* x, const float* w_tap_major, const float* bi
   if (stat_out && !prezeroed) FQ_HIP(hipMemsetAsync(stat_out, 0, n * sizeof(float), st));
   ProfScope prof(FQ_KERNEL_STEM, 4.0 * ((double)n * cin * h * w + (double)n * cout * hwo), st,
                  4.0 * (double)n * cin * h * w + (out_thr != nullptr ? 1.0 : 4.0) * (double)n * cout * hwo);
-  static const int form = env_int("FQ_STEM_FORM", 0);                   // tuning: 0 auto, 1 VALU form (3x3 only), 2 MFMA form
   StemCodes oc;
   oc.thr = out_thr; oc.levels = 0.0f; oc.lo_neg = 0; oc.zoff = 0; oc.CBo = (int)((cout + 15) / 16);
   if (out_thr != nullptr) {
@@ -584,21 +469,10 @@ static int stem_launch(const float* x, const float* w_tap_major, const float* bi
     oc.lo_neg = (out_flags & FQ_ACT_LO_NEG_MAX) ? 1 : 0;
     oc.zoff = (out_flags & FQ_ACT_SIGNED) ? 0 : 128;
   }
-  if (ksize == 3 && form == 1 && out_thr == nullptr) {
-    const int tiles = (int)((hwo + kBlock - 1) / kBlock);
-    // enough workgroups to fill the chip, as few statistic atomics per sample as that allows
-    int tiles_per_wg = 1;
-    while (tiles_per_wg < 8 && n * ((tiles + 2 * tiles_per_wg - 1) / (2 * tiles_per_wg)) >= (int64_t)num_cu() * 8) tiles_per_wg *= 2;
-    const dim3 grid((unsigned)((tiles + tiles_per_wg - 1) / tiles_per_wg), (unsigned)n);
-    hipLaunchKernelGGL((stem_conv3x3s2_kernel<3, 32>), grid, dim3(kBlock), 0, st, x, w_tap_major, bias, y, (int)h, (int)w,
-                       Ho, Wo, tiles_per_wg, bn_scale, bn_shift, act, stat_out);
-    FQ_LAUNCH_CHECK();
-    return FQ_OK;
-  }
   // K2r: the 3x3 form with its input rows staged in LDS (fp32 output; rows of a multiple of eight output columns so that a
   // step of four rows is whole tiles; FQ_STEM_ROWS=0: never)
   static const int use_rows = env_int("FQ_STEM_ROWS", 1);
-  if (ksize == 3 && out_thr == nullptr && form == 0 && use_rows != 0 && (w & 3) == 0 && (Wo & 7) == 0 && 6 * w <= 512 * kR3ST &&
+  if (ksize == 3 && out_thr == nullptr && use_rows != 0 && (w & 3) == 0 && (Wo & 7) == 0 && 6 * w <= 512 * kR3ST &&
       ((reinterpret_cast<size_t>(x) | reinterpret_cast<size_t>(y)) & 15) == 0 && (int64_t)cout * hwo * 4 < (1ll << 31)) {
     Stem3Geom g3;
     g3.H = (int)h; g3.W = (int)w; g3.Ho = Ho; g3.Wo = Wo;
@@ -633,8 +507,8 @@ static int stem_launch(const float* x, const float* w_tap_major, const float* bi
   }
   const int tiles_per_img = (int)((hwo + 31) / 32);
   const int64_t total = (int64_t)tiles_per_img * n;
-  // persistent workgroups, all resident: four per CU for the 3x3 form (86 -> 77 us against the VALU form's 86 in the
-  // MobileNet step; six: 89), two for the 7x7 form (208 registers + 38 KB of weights in LDS)
+  // persistent workgroups, all resident: four per CU for the 3x3 form (77 us in the MobileNet step; six: 89), two for the
+  // 7x7 form (208 registers + 38 KB of weights in LDS)
   static const int wg_tune = env_int("FQ_STEM_WG_PER_CU", 0);
   const int wg_per_cu = wg_tune > 0 ? wg_tune : (ksize == 3 ? 4 : 2);
   int64_t grid = (int64_t)num_cu() * wg_per_cu;

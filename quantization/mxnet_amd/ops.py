@@ -767,7 +767,7 @@ class Codes16(object):
             (self.flags & 3) == (int(flags) & 3)
 
 
-PW_FORMS = {None: 0, "auto": 0, "two_kernels": 1, "stream": 3, "split": 6, "sample": 7, "rows": 8, "pipe": 9}
+PW_FORMS = {None: 0, "auto": 0, "two_kernels": 1, "stream": 3, "split": 6, "sample": 7, "rows": 8}
 
 
 SPLIT_KT = (2, 4, 6, 8, 10, 12, 16, 18, 30, 32, 64)     # padded Cin / 32 the split form of fq_pwconv_i8 is built for

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """fq_dwconv3x3_c16 alone on MobileNetV2's depthwise layers (batch 128): median of 60 launches each, HIP events.
-FQ_LIB_PATH selects a variant library (csrc/build.py --only fq_dwconv16 -DFQ_DW16_V=<bits>); DW16_BATCH another batch size
+FQ_LIB_PATH selects another library; DW16_BATCH another batch size
 (how much of a layer's time is its last, partly filled round of workgroups), DW16_LAYERS="2,3" a subset of the layers."""
 import os
 import sys
