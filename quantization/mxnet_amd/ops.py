@@ -778,6 +778,13 @@ def pwconv_strided_supported(cin):
     return ((int(cin) + 63) // 64 * 64) // 32 in SPLIT_KT
 
 
+def pwconv_residual_supported(cin):
+    """A residual operand of `pwconv_i8` is added by the split and the streaming form only (fq_pwconv_i8_strided refuses it
+    otherwise): taken for the input channel counts the split form is built for - every unit of MobileNetV2 1.0 / 0.5 / 0.25 and of
+    the ResNets; MobileNetV2 0.75's 432 -> 72 and 720 -> 120 projections (padded Cin / 32 = 14, 24) are not among them."""
+    return ((int(cin) + 63) // 64 * 64) // 32 in SPLIT_KT
+
+
 def pwconv_shortcut_supported(cin, cin2, cout):
     """Shapes `pwconv_i8_shortcut` takes (fq_pwconv_i8_shortcut_supported): the stage heads of the v1 bottleneck ResNets."""
     return bool(_lib_().fq_pwconv_i8_shortcut_supported(int(cin), int(cin2), int(cout)))

@@ -572,8 +572,9 @@ def pointwise_fused(block, F, x, weight_raw, weight_q, bias, plan, weights_quant
                     return folded
                 res["t"] = materialise_shortcut_record(d)
                 res["short"] = None
+            # (a channel count no residual-adding form is built for - MobileNetV2 0.75's 432 and 720: the unit adds the shortcut itself)
             if res is not None and block._kwargs["stride"][0] == 1 and tuple(res["t"].shape[2:]) == tuple(xshape[2:]) \
-                    and res["t"].shape[1] == block._kwargs["num_filter"]:
+                    and res["t"].shape[1] == block._kwargs["num_filter"] and ops.pwconv_residual_supported(xshape[1]):
                 extra = dict(residual=res["t"])
                 res["used"] = True
                 side_blk = side_target(block, c16_in)

@@ -326,7 +326,7 @@ def test_dense3x3_with_codes_on_both_sides(dev, ops, case, signed):
         assert torch.equal(st, want_stat), what
 
 
-def test_mobilenetv2_units_without_shortcut_hand_codes_to_the_next_block(gpu):
+def test_mobilenetv2_units_without_shortcut_hand_codes_to_the_next_block(gpu, rand_bn=None):
     """quantize/fuse.py: visit_unit_links - the 16-channel tensor between MobileNetV2's first two units (no shortcut on either
     side) crosses their containers as codes: at a batch whose 112 x 112 planes make more than 4096 pixel tiles the 16 -> 96
     convolution READS codes (and writes codes); logits and every batch statistic equal those of the
@@ -340,7 +340,7 @@ def test_mobilenetv2_units_without_shortcut_hand_codes_to_the_next_block(gpu):
         outs, stats, seen = {}, {}, {}
         for links in (True, False):
             fuse.UNIT_LINKS = links
-            net = _build("mobilenetv2_1.0", 1000, gpu, quant_type="channel", wt=4)
+            net = _build("mobilenetv2_1.0", 1000, gpu, quant_type="channel", wt=4, rand_bn=rand_bn)
             rng = np.random.default_rng(5)
             xs = [mx.nd.array(rng.standard_normal((11, 3, 224, 224)).astype(np.float32), ctx=gpu) for _ in range(3)]
             net.quantize_input(enable=True, online=True)
@@ -375,7 +375,7 @@ def test_mobilenetv2_units_without_shortcut_hand_codes_to_the_next_block(gpu):
 @pytest.mark.parametrize("model,kw", [("resnet50_v1", dict(quant_type="channel")), ("cifar_resnet20_v1", dict()),
                                       ("mobilenetv2_1.0", dict(quant_type="channel", wt=4))],
                          ids=["resnet50_v1", "cifar_resnet20_v1", "mobilenetv2_1.0-w4"])
-def test_net_with_hand_overs_equals_net_without(gpu, model, kw):
+def test_net_with_hand_overs_equals_net_without(gpu, model, kw, rand_bn=None):
     """Offline input quantisation, fused producers: every 1x1 -> 3x3 -> 1x1 chain of the units hands int8 codes over.  The
     logits equal those of the same net with the hand-over switched off BIT FOR BIT, every block's `current_input_max`
     included; under online quantisation nothing is handed over.  (MobileNetV2's classifier is excluded from quantisation, i.e.
@@ -389,7 +389,7 @@ def test_net_with_hand_overs_equals_net_without(gpu, model, kw):
     torch.backends.cudnn.deterministic = True
     classes, hw, batch = (10, 32, 8) if model.startswith("cifar") else ((1000, 224, 2) if model.startswith("mobilenetv2")
                                                                        else (1000, 64, 4))
-    net = _build(model, classes, gpu, **kw)
+    net = _build(model, classes, gpu, rand_bn=rand_bn, **kw)
     rng = np.random.default_rng(3)
     xs = [mx.nd.array(rng.standard_normal((batch, 3, hw, hw)).astype(np.float32), ctx=gpu) for _ in range(3)]
     net.quantize_input(enable=True, online=True)
@@ -467,6 +467,18 @@ def test_net_with_hand_overs_equals_net_without(gpu, model, kw):
     assert n_in == n_out + shared and n_out >= {"resnet50_v1": 32, "mobilenetv2_1.0": 32}.get(model, 1), (n_out, n_in)
     assert np.array_equal(with_codes, without), "logits with int8 hand-overs differ from the fp32 hand-over"
     assert cur_with == cur_without
+
+
+@pytest.mark.parametrize("model,kw", [("resnet50_v1", dict(quant_type="channel")), ("mobilenetv2_1.0", dict(quant_type="channel", wt=4))],
+                         ids=["resnet50_v1", "mobilenetv2_1.0-w4"])
+def test_net_with_randomised_batchnorm_and_hand_overs_equals_net_without(gpu, model, kw):
+    """... with the BatchNorm statistics of a trained checkpoint (tests/unit_reference.py) instead of the zoo's identity."""
+    test_net_with_hand_overs_equals_net_without(gpu, model, kw, rand_bn=5)
+
+
+def test_mobilenetv2_with_randomised_batchnorm_hands_codes_to_the_next_block(gpu):
+    """... with the BatchNorm statistics of a trained checkpoint (tests/unit_reference.py) instead of the zoo's identity."""
+    test_mobilenetv2_units_without_shortcut_hand_codes_to_the_next_block(gpu, rand_bn=5)
 
 
 def test_hooked_blocks_are_never_handed_codes(gpu):

@@ -104,7 +104,7 @@ def test_gap_producer_refuses_what_it_is_not_built_for(dev, ops):
 
 
 @pytest.mark.parametrize("model,kw", [("mobilenet1.0", dict()), ("resnet50_v1", dict(quant_type="channel")), ("mobilenet0.5", dict())])
-def test_a_net_with_the_pooled_producer_equals_the_same_net_without(dev, ops, model, kw):
+def test_a_net_with_the_pooled_producer_equals_the_same_net_without(dev, ops, model, kw, rand_bn=None):
     from quantization.mxnet_amd import mx
     from quantization.mxnet_amd.quantize import fuse
     from test_gpu_net import _build as build
@@ -112,7 +112,7 @@ def test_a_net_with_the_pooled_producer_equals_the_same_net_without(dev, ops, mo
     X = mx.nd.array(rng.standard_normal((6, 3, 224, 224)).astype(np.float32), ctx=mx.gpu(0))
     outs = {}
     for on in (False, True):
-        net = build(model, 1000, mx.gpu(0), **kw)
+        net = build(model, 1000, mx.gpu(0), rand_bn=rand_bn, **kw)
         net.fix_params()
         net.quantize_input(enable=True, online=True)
         net(mx.nd.NDArray(X._t[:2].contiguous()))
@@ -135,7 +135,7 @@ def test_a_net_with_the_pooled_producer_equals_the_same_net_without(dev, ops, mo
     _eq(outs[True][1], outs[False][1], "current_input_max of every block")
     _eq(outs[True][2], outs[False][2], "thresholds after one naive-EMA step")
     # a hook on the pooling block keeps the two launches (it is shown the planes)
-    net = build(model, 1000, mx.gpu(0), **kw)
+    net = build(model, 1000, mx.gpu(0), rand_bn=rand_bn, **kw)
     net.fix_params()
     net.quantize_input(enable=True, online=True)
     net(mx.nd.NDArray(X._t[:2].contiguous()))
@@ -149,6 +149,12 @@ def test_a_net_with_the_pooled_producer_equals_the_same_net_without(dev, ops, mo
         hk.detach()
     assert len(shapes) == 1 and shapes[0][2:] == (7, 7)
     _eq(got, outs[True][0], "logits with a hook on the pooling block")
+
+
+@pytest.mark.parametrize("model,kw", [("mobilenet1.0", dict()), ("resnet50_v1", dict(quant_type="channel"))])
+def test_a_net_with_randomised_batchnorm_and_the_pooled_producer_equals_the_same_net_without(dev, ops, model, kw):
+    """... with the BatchNorm statistics of a trained checkpoint (tests/unit_reference.py) instead of the zoo's identity."""
+    test_a_net_with_the_pooled_producer_equals_the_same_net_without(dev, ops, model, kw, rand_bn=5)
 
 
 def test_mobilenetv2_offline_with_the_pooled_producer_equals_the_same_net_without(dev, ops):

@@ -14,7 +14,9 @@ from oracle import fq_oracle as O
 pytestmark = pytest.mark.gpu
 
 
-def _build(model, classes, ctx, quant_type="layer", wt=8, in_w=8, signed=False, wino="none"):
+def _build(model, classes, ctx, quant_type="layer", wt=8, in_w=8, signed=False, wino="none", rand_bn=None):
+    """`rand_bn`: a seed - the BatchNorm statistics of a trained checkpoint instead of the zoo's identity (gamma 1, beta 0, mean 0,
+    variance 1), under which every folded BatchNorm is the same `scale = 1 / sqrt(1 + 1e-5)`, `shift = 0`."""
     from quantization.mxnet_amd.mx.gluon import nn
     from quantization.mxnet_amd.mx.gluon.model_zoo import get_model
     from quantization.mxnet_amd.quantize import convert
@@ -34,6 +36,9 @@ def _build(model, classes, ctx, quant_type="layer", wt=8, in_w=8, signed=False, 
     convert.convert_model(net, exclude=exclude, convert_fn=convert_fn)
     qparams_init(net)
     net.collect_params().reset_ctx(ctx)
+    if rand_bn is not None:
+        from unit_reference import randomise_batchnorm
+        randomise_batchnorm(net, rand_bn)
     if model.startswith("vgg"):
         # (the first Dense layer's input width follows from the image size - deferred initialisation, as in gluon; the Spy's
         # pre-hooks read the weights before the block's own forward would materialise them)

@@ -222,7 +222,7 @@ def test_fast_quotient_is_the_ieee_quotient_where_a_code_depends_on_it(dev, ops)
 
 
 @pytest.mark.parametrize("model", ["mobilenet1.0", "mobilenet0.5"])
-def test_a_net_with_recompute_pairs_equals_the_same_net_without(dev, ops, model):
+def test_a_net_with_recompute_pairs_equals_the_same_net_without(dev, ops, model, rand_bn=None):
     """quantize.fuse's recompute pairs (online input quantisation) change no value: logits, every block's current_input_max and
     the naive-EMA thresholds after a calibration step are bit-equal with FQ_RECOMPUTE on and off."""
     from quantization.mxnet_amd import mx
@@ -232,7 +232,7 @@ def test_a_net_with_recompute_pairs_equals_the_same_net_without(dev, ops, model)
     X = mx.nd.array(rng.standard_normal((6, 3, 224, 224)).astype(np.float32), ctx=mx.gpu(0))
     outs = {}
     for on in (False, True):
-        net = build(model, 1000, mx.gpu(0))
+        net = build(model, 1000, mx.gpu(0), rand_bn=rand_bn)
         net.fix_params()
         net.quantize_input(enable=True, online=True)
         net(mx.nd.NDArray(X._t[:2].contiguous()))
@@ -255,6 +255,13 @@ def test_a_net_with_recompute_pairs_equals_the_same_net_without(dev, ops, model)
     _eq(outs[True][0], outs[False][0], "logits")
     _eq(outs[True][1], outs[False][1], "current_input_max of every block")
     _eq(outs[True][2], outs[False][2], "thresholds after one naive-EMA step")
+
+
+@pytest.mark.parametrize("model", ["mobilenet1.0", "mobilenet0.5"])
+def test_a_net_with_recompute_pairs_and_randomised_batchnorm_equals_the_same_net_without(dev, ops, model):
+    """... with the BatchNorm statistics of a trained checkpoint (tests/unit_reference.py): under the zoo's identity BatchNorm the
+    two folds the pair's launch is handed (`pw_bn_*`, `dw_bn_*`) are the same vector and exchanging them changes nothing."""
+    test_a_net_with_recompute_pairs_equals_the_same_net_without(dev, ops, model, rand_bn=5)
 
 
 def test_a_block_called_on_its_own_returns_a_tensor_and_a_stray_deferred_array_is_materialised(dev, ops):

@@ -125,7 +125,7 @@ def test_folded_shortcut_refuses_what_it_is_not_built_for(dev, ops):
 
 
 @pytest.mark.parametrize("wino", ["none", "F43"])
-def test_resnet50_with_folded_shortcuts_equals_the_same_net_without(dev, ops, wino):
+def test_resnet50_with_folded_shortcuts_equals_the_same_net_without(dev, ops, wino, rand_bn=None):
     """Four launches compute their unit's shortcut convolution themselves (stage 1 on the pooled input, stages 2 to 4 on the
     subsampled trunk): logits, every block's current_input_max and the thresholds after a naive-EMA step are bit-equal."""
     from quantization.mxnet_amd import mx
@@ -135,7 +135,7 @@ def test_resnet50_with_folded_shortcuts_equals_the_same_net_without(dev, ops, wi
     X = mx.nd.array(rng.standard_normal((4, 3, 224, 224)).astype(np.float32), ctx=mx.gpu(0))
     outs = {}
     for on in (False, True):
-        net = build("resnet50_v1", 1000, mx.gpu(0), quant_type="channel", wino=wino)
+        net = build("resnet50_v1", 1000, mx.gpu(0), quant_type="channel", wino=wino, rand_bn=rand_bn)
         net.fix_params()
         net.quantize_input(enable=True, online=True)
         net(mx.nd.NDArray(X._t[:2].contiguous()))
@@ -158,6 +158,13 @@ def test_resnet50_with_folded_shortcuts_equals_the_same_net_without(dev, ops, wi
     _eq(outs[True][0], outs[False][0], "logits")
     _eq(outs[True][1], outs[False][1], "current_input_max of every block")
     _eq(outs[True][2], outs[False][2], "thresholds after one naive-EMA step")
+
+
+def test_resnet50_with_randomised_batchnorm_and_folded_shortcuts_equals_the_same_net_without(dev, ops):
+    """... with the BatchNorm statistics of a trained checkpoint (tests/unit_reference.py): under the zoo's identity BatchNorm the
+    two folds of the launch (`bn_scale` / `bn_scale2`, `bn_shift` / `bn_shift2`) are the same vector and exchanging them changes
+    nothing."""
+    test_resnet50_with_folded_shortcuts_equals_the_same_net_without(dev, ops, "none", rand_bn=5)
 
 
 def test_a_deferred_shortcut_nobody_folds_is_materialised(dev, ops):
@@ -243,7 +250,7 @@ def test_folded_shortcut_under_stored_thresholds_equals_the_two_launches(dev, op
     _eq(N(cur[3]), N(cur[1]), "current_input_max of the closing convolution")
 
 
-def test_resnet50_offline_with_folded_shortcuts_equals_the_same_net_without(dev, ops):
+def test_resnet50_offline_with_folded_shortcuts_equals_the_same_net_without(dev, ops, rand_bn=None):
     """BASELINE configuration 3's evaluation (stored thresholds, codes between the layers): the three stage heads fold their shortcut
     convolution (fq_pwconv_i8_shortcut_c16: codes in, fp32 + code copy out); logits and every current_input_max bit-equal."""
     from quantization.mxnet_amd import mx
@@ -256,7 +263,7 @@ def test_resnet50_offline_with_folded_shortcuts_equals_the_same_net_without(dev,
         xs = [mx.nd.array(rng.standard_normal((4, 3, 224, 224)).astype(np.float32), ctx=mx.gpu(0)) for _ in range(3)]
         outs = {}
         for on in (False, True):
-            net = _build("resnet50_v1", 1000, mx.gpu(0), quant_type="channel")
+            net = _build("resnet50_v1", 1000, mx.gpu(0), quant_type="channel", rand_bn=rand_bn)
             net.quantize_input(enable=True, online=True)
             for x in xs[:2]:
                 net(x)
@@ -286,3 +293,8 @@ def test_resnet50_offline_with_folded_shortcuts_equals_the_same_net_without(dev,
         _eq(outs[True][1], outs[False][1], "current_input_max of every block")
     finally:
         torch.backends.cudnn.deterministic = was
+
+
+def test_resnet50_offline_with_randomised_batchnorm_and_folded_shortcuts_equals_the_same_net_without(dev, ops):
+    """... with the BatchNorm statistics of a trained checkpoint (tests/unit_reference.py) instead of the zoo's identity."""
+    test_resnet50_offline_with_folded_shortcuts_equals_the_same_net_without(dev, ops, rand_bn=5)

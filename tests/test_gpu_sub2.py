@@ -128,16 +128,16 @@ def test_sub2_refuses_what_it_is_not_built_for(dev, ops):
                       in_stat=torch.ones(2, device=dev), subsample=True, stride=2)
 
 
-def _resnet(model, quant_type, ctx):
+def _resnet(model, quant_type, ctx, rand_bn=None):
     from test_gpu_net import _build as build
-    net = build(model, 1000, ctx, quant_type=quant_type) if quant_type else build(model, 1000, ctx)
+    net = build(model, 1000, ctx, quant_type=quant_type, rand_bn=rand_bn) if quant_type else build(model, 1000, ctx, rand_bn=rand_bn)
     net.fix_params()
     net.quantize_input(enable=True, online=True)
     return net
 
 
 @pytest.mark.parametrize("size", [224, 200])
-def test_resnet50_with_subsampled_stage_boundaries_equals_the_same_net_without(dev, ops, size):
+def test_resnet50_with_subsampled_stage_boundaries_equals_the_same_net_without(dev, ops, size, rand_bn=None):
     """Three launches store a quarter of their output and six stride-2 convolutions read it with stride 1: no value changes
     (size 200: 50 x 50, 25 x 25 and 13 x 13 planes - odd rows and columns at two of the three boundaries)."""
     from quantization.mxnet_amd import mx
@@ -146,7 +146,7 @@ def test_resnet50_with_subsampled_stage_boundaries_equals_the_same_net_without(d
     X = mx.nd.array(rng.standard_normal((4, 3, size, size)).astype(np.float32), ctx=mx.gpu(0))
     outs = {}
     for on in (False, True):
-        net = _resnet("resnet50_v1", "channel", mx.gpu(0))
+        net = _resnet("resnet50_v1", "channel", mx.gpu(0), rand_bn=rand_bn)
         net(mx.nd.NDArray(X._t[:2].contiguous()))
         fuse.fuse_inference(net)
         old = fuse.SUBSAMPLE
@@ -172,6 +172,11 @@ def test_resnet50_with_subsampled_stage_boundaries_equals_the_same_net_without(d
     _eq(outs[True][0], outs[False][0], "logits")
     _eq(outs[True][1], outs[False][1], "current_input_max of every block")
     _eq(outs[True][2], outs[False][2], "thresholds after one naive-EMA step")
+
+
+def test_resnet50_with_randomised_batchnorm_and_subsampled_stage_boundaries_equals_the_same_net_without(dev, ops):
+    """... with the BatchNorm statistics of a trained checkpoint (tests/unit_reference.py) instead of the zoo's identity."""
+    test_resnet50_with_subsampled_stage_boundaries_equals_the_same_net_without(dev, ops, 224, rand_bn=5)
 
 
 def test_a_hook_between_producer_and_readers_keeps_the_whole_trunk_and_a_stray_reader_fails_loudly(dev, ops):
@@ -241,7 +246,7 @@ def test_dual_sub2_stores_both_outputs_subsampled(dev, ops, case):
         assert N(got_stat)[n - 1] >= 80.0
 
 
-def test_resnet50_offline_with_subsampled_stage_boundaries_equals_the_same_net_without(dev, ops):
+def test_resnet50_offline_with_subsampled_stage_boundaries_equals_the_same_net_without(dev, ops, rand_bn=None):
     """Offline thresholds: the last unit of a stage stores trunk and code copy subsampled (fq_pwconv_i8_c16_dual_sub2), the two
     readers take the codes (or the fp32 quarter) with stride 1: logits and every block's current_input_max bit-equal."""
     from quantization.mxnet_amd import mx
@@ -254,7 +259,7 @@ def test_resnet50_offline_with_subsampled_stage_boundaries_equals_the_same_net_w
         xs = [mx.nd.array(rng.standard_normal((4, 3, 224, 224)).astype(np.float32), ctx=mx.gpu(0)) for _ in range(3)]
         outs = {}
         for on in (False, True):
-            net = _build("resnet50_v1", 1000, mx.gpu(0), quant_type="channel")
+            net = _build("resnet50_v1", 1000, mx.gpu(0), quant_type="channel", rand_bn=rand_bn)
             net.quantize_input(enable=True, online=True)
             for x in xs[:2]:
                 net(x)
@@ -302,3 +307,8 @@ def test_resnet50_offline_with_subsampled_stage_boundaries_equals_the_same_net_w
         _eq(outs[True][1], outs[False][1], "current_input_max of every block")
     finally:
         torch.backends.cudnn.deterministic = was
+
+
+def test_resnet50_offline_with_randomised_batchnorm_and_subsampled_stage_boundaries_equals_the_same_net_without(dev, ops):
+    """... with the BatchNorm statistics of a trained checkpoint (tests/unit_reference.py) instead of the zoo's identity."""
+    test_resnet50_offline_with_subsampled_stage_boundaries_equals_the_same_net_without(dev, ops, rand_bn=5)

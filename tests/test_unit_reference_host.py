@@ -1,0 +1,105 @@
+"""Every fused unit of the zoo's nets against the fp64 composition of the reference (tests/unit_reference.py), on the CPU with
+the oracle standing in for the kernels (oracle/patch.py: the same arithmetic) - what quantize/fuse.py and quantize/convert/* TELL
+each launch to compute: which BatchNorm is folded where, its constants from gamma / beta / mean / var / eps, the activation, the
+shortcut.  BatchNorm statistics are randomised (negative and zero gammas included): with the zoo's identity BatchNorm every fold
+is `scale = 1 / sqrt(1 + 1e-5)`, `shift = 0`, and a swapped, dropped or mis-folded BatchNorm changes nothing."""
+import numpy as np
+import pytest
+
+import unit_reference as U
+from oracle.patch import oracle_ops
+from quantization.mxnet_amd import mx
+
+MOBILENETS = ["mobilenet1.0", "mobilenet0.75", "mobilenet0.5", "mobilenet0.25",
+              "mobilenetv2_1.0", "mobilenetv2_0.75", "mobilenetv2_0.5", "mobilenetv2_0.25"]
+RESNETS = ["resnet18_v1", "resnet34_v1", "resnet50_v1"]
+SMALL = ["cifar_resnet20_v1", "vgg11_bn"]
+CASES = [(m, q, False) for m in MOBILENETS + RESNETS + SMALL for q in ("layer", "channel")] + \
+    [("mobilenet1.0", "group", False), ("resnet50_v1", "channel", True), ("resnet50_v1", "channel-F43", False)]
+
+
+def _size(model):
+    return 64 if model.startswith("mobilenet") else 40 if model.startswith("resnet") else 32
+
+
+@pytest.fixture
+def plain_forms(monkeypatch):
+    """(the oracle's first convolution does not pool and its launches hand no codes over: every unit is one storing launch)"""
+    from quantization.mxnet_amd.quantize import fuse
+    monkeypatch.setattr(fuse, "STEM_POOL", False)
+    monkeypatch.setattr(fuse, "HANDOVER", False)
+    return fuse
+
+
+@pytest.mark.parametrize("model,quant_type,last_gamma", CASES,
+                         ids=["%s-%s%s" % (m, q, "-last_gamma" if g else "") for m, q, g in CASES])
+def test_every_fused_unit_is_the_reference_composition_of_its_raw_parameters(plain_forms, model, quant_type, last_gamma):
+    """Online thresholds, then the stored ones after one naive-EMA step, on the same net and input: every bound launch within
+    4 * max(e_fp32, 2^-23) of the fp64 unit, every statistic and `current_input_max` bit-exact; with `last_gamma=True` every
+    residual unit is relu(shortcut)."""
+    fuse = plain_forms
+    hw = _size(model)
+    with oracle_ops():
+        quant_type, _, wino = quant_type.partition("-")
+        net = U.build(model, 10, quant_type=quant_type, wino=wino or "none", rand_bn=3, last_gamma=last_gamma)
+        X = mx.nd.array(np.random.default_rng(5).standard_normal((2, 3, hw, hw)).astype(np.float32))
+        if model.startswith("vgg"):
+            net(X)                                  # (the first Dense layer's input width follows from the image size)
+        units = U.describe(net)
+        if last_gamma:
+            tails = [u for u in units if u.shortcut is not None]
+            assert len(tails) == 16 and all(not bool((u.bn.gamma.data()._t != 0).any()) for u in tails)
+        net.fix_params()
+        net.quantize_input(enable=True, online=True)
+        assert fuse.fuse_inference(net) > 0
+        for offline in (False, True):
+            with U.Recorder() as rec:
+                out = net(X)
+            bound = U.bind(units, rec.launches, out._t)
+            assert sum(1 for b in bound if b.unit.quantised) == len(net.collect_quantized_blocks())
+            report = []
+            worst = U.check_units(bound, offline, report, last_gamma=last_gamma)
+            print("%s %s %s: %d units, worst ratio %.2f" % (model, quant_type, "offline" if offline else "online", len(bound), worst))
+            assert U.check_statistics(rec.launches) > 0
+            net.update_ema()
+            net.quantize_input(enable=True, online=False)
+        fuse.unfuse(net)
+
+
+def test_randomised_batchnorm_has_the_values_the_identity_hides():
+    net = U.build("mobilenet0.25", 10, rand_bn=1)
+    from quantization.mxnet_amd.mx.gluon import nn
+    bns = []
+    net.apply(lambda b: bns.append(b) if type(b) is nn.BatchNorm else None)
+    g = np.concatenate([b.gamma.data().asnumpy() for b in bns])
+    v = np.concatenate([b.running_var.data().asnumpy() for b in bns])
+    m = np.concatenate([b.running_mean.data().asnumpy() for b in bns])
+    assert len(bns) == 27 and v.min() >= 0.5 and v.max() <= 2.0 and np.abs(m).max() > 0.3
+    assert 0.1 < (g < 0).mean() < 0.3 and 0.01 < (g == 0).mean() < 0.1 and np.abs(g[g != 0]).min() >= 0.5 and np.abs(g).max() <= 1.5
+
+
+def test_the_gate_notices_a_shift_that_is_two_percent_off(plain_forms, monkeypatch):
+    """The separation the gate lives on: one unit's folded shift multiplied by 1.02 - invisible under the end-to-end bounds of the
+    whole-net tests - puts that unit, and no other, outside the gate."""
+    fuse = plain_forms
+    with oracle_ops():
+        net = U.build("mobilenet1.0", 10, rand_bn=3)
+        X = mx.nd.array(np.random.default_rng(5).standard_normal((2, 3, 64, 64)).astype(np.float32))
+        units = U.describe(net)
+        net.fix_params()
+        net.quantize_input(enable=True, online=True)
+        fuse.fuse_inference(net)
+        victim = units[9].bn
+        real = fuse._bn_constants
+
+        def off(bn):
+            scale, shift, key = real(bn)
+            return (scale, shift * 1.02 if bn is victim else shift, key)
+        monkeypatch.setattr(fuse, "_bn_constants", off)
+        with U.Recorder() as rec:
+            out = net(X)
+        bound = U.bind(units, rec.launches, out._t)
+        with pytest.raises(AssertionError, match="units outside") as err:
+            U.check_units(bound, False)
+        lines = str(err.value).splitlines()[1:]
+        assert len(lines) == 1 and lines[0].startswith(units[9].name + " ")
