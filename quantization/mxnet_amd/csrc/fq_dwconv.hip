@@ -4,6 +4,135 @@
 
 namespace {
 
+typedef float f2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f2 splat2(float v) { return (f2){v, v}; }
+
+// ---------------------------------------------------------------------------------------------------------------
+// What the five kernel forms below share.  Each thing is written here once.
+// ---------------------------------------------------------------------------------------------------------------
+// The 3x3 sum of one output: rows a, b, c (above, centre, below), each as left / centre / right.  The order of these nine
+// operations is the numerical contract of the unit (the oracle emulates exactly this chain).
+__device__ __forceinline__ float dw_taps(float w00, float w01, float w02, float w10, float w11, float w12, float w20,
+                                         float w21, float w22, float a0, float a1, float a2, float b0, float b1, float b2,
+                                         float c0, float c1, float c2) {
+  float acc = 0.0f;
+  acc = fmaf(w00, a0, acc);
+  acc = fmaf(w01, a1, acc);
+  acc = fmaf(w02, a2, acc);
+  acc = fmaf(w10, b0, acc);
+  acc = fmaf(w11, b1, acc);
+  acc = fmaf(w12, b2, acc);
+  acc = fmaf(w20, c0, acc);
+  acc = fmaf(w21, c1, acc);
+  acc = fmaf(w22, c2, acc);
+  return acc;
+}
+// Two outputs as ONE chain of packed fp32 FMAs (v_pk_fma_f32: two IEEE FMAs per lane per instruction, same order)
+__device__ __forceinline__ f2 dw_taps2(float w00, float w01, float w02, float w10, float w11, float w12, float w20, float w21,
+                                       float w22, f2 a0, f2 a1, f2 a2, f2 b0, f2 b1, f2 b2, f2 c0, f2 c1, f2 c2) {
+  f2 acc = {0.f, 0.f};
+  acc = __builtin_elementwise_fma(splat2(w00), a0, acc);
+  acc = __builtin_elementwise_fma(splat2(w01), a1, acc);
+  acc = __builtin_elementwise_fma(splat2(w02), a2, acc);
+  acc = __builtin_elementwise_fma(splat2(w10), b0, acc);
+  acc = __builtin_elementwise_fma(splat2(w11), b1, acc);
+  acc = __builtin_elementwise_fma(splat2(w12), b2, acc);
+  acc = __builtin_elementwise_fma(splat2(w20), c0, acc);
+  acc = __builtin_elementwise_fma(splat2(w21), c1, acc);
+  acc = __builtin_elementwise_fma(splat2(w22), c2, acc);
+  return acc;
+}
+
+// The input quantiser of a launch (a kernel without one keeps `QParams q = {}`).  dw_qparams loads the threshold where it
+// stands; dw_qparams_finish turns the loads that threshold_request issued earlier into the same parameters.
+template <bool ONLINE>
+__device__ __forceinline__ QParams dw_qparams(const float* in_stat, int n, const float* in_thr,
+                                              float levels, int lo_neg_max, float eps, float* cur_max_out) {
+  const float max_ = input_threshold(in_stat, n, ONLINE ? nullptr : in_thr, cur_max_out, blockIdx.x == 0);
+  return make_qparams_rt(max_, levels, lo_neg_max, eps, in_thr);
+}
+template <bool ONLINE>
+__device__ __forceinline__ QParams dw_qparams_finish(const ThresholdReq& treq, const float* in_stat, int n,
+                                                     const float* in_thr, float levels, int lo_neg_max, float eps,
+                                                     float* cur_max_out) {
+  const float max_ = threshold_finish(treq, in_stat, n, ONLINE ? nullptr : in_thr, cur_max_out, blockIdx.x == 0);
+  return make_qparams_rt(max_, levels, lo_neg_max, eps, in_thr);
+}
+
+// A workgroup takes a CONTIGUOUS range of blocks (few samples -> a small LDS statistic table, one flush) and its
+// wavefronts run through them without barriers.  Index arithmetic is unsigned 32-bit (host: total_segs < 2^31): the
+// 64-bit divisions it replaces cost each block 2.3 us (tools/dw_trace.py).
+struct DwBlkRange {
+  unsigned begin, end;      // blocks of this workgroup
+  unsigned n_samples;
+  unsigned s_base;          // sample of the first block: slot 0 of the statistic table
+};
+__device__ __forceinline__ DwBlkRange dw_block_range(unsigned nblk, unsigned tsegs, unsigned segs_per_block, unsigned nsegx,
+                                                     unsigned C) {
+  DwBlkRange r;
+  r.begin = (unsigned)((uint64_t)nblk * blockIdx.x / gridDim.x);
+  r.end = (unsigned)((uint64_t)nblk * (blockIdx.x + 1) / gridDim.x);
+  r.n_samples = tsegs / nsegx / C;
+  const unsigned seg0 = r.begin * segs_per_block;
+  r.s_base = (seg0 < tsegs ? seg0 : tsegs - 1) / nsegx / C;
+  return r;
+}
+
+// Per-sample statistic: the workgroup's LDS table k_stat[kStatSlots] holds the maxima of samples s_base .. s_base + 15 as
+// bit patterns (|x| >= 0 orders like an unsigned int); samples beyond it go to memory at once.  dw_stat_update is called per
+// wavefront and block without a barrier (m: the lane's maximum, counted where is_out), dw_stat_flush once at the end.
+// (SampleT: int or unsigned, as the form holds its sample index - the one-type version widens the index differently and costs
+// the stride-2 four-columns-per-lane kernels two vector registers)
+constexpr int kStatSlots = 16;
+template <class SampleT>
+__device__ __forceinline__ void dw_stat_update(unsigned* k_stat, unsigned s_base, SampleT sample, bool is_out, float m,
+                                               int lane, float* stat_out) {
+  const unsigned s0 = (unsigned)__builtin_amdgcn_readfirstlane((int)sample);
+  const bool wave_uniform = __all(!is_out || (unsigned)sample == s0);
+  if (wave_uniform) {
+    const float wm = wave_max_nonneg(is_out ? m : 0.0f);
+    if (lane == 0 && __float_as_uint(wm) != 0u) {
+      const unsigned slot = s0 - s_base;
+      if (slot < (unsigned)kStatSlots) atomicMax(&k_stat[slot], __float_as_uint(wm));
+      else atomic_max_f32(stat_out + s0, wm);
+    }
+  } else if (is_out) {
+    const unsigned slot = (unsigned)sample - s_base;
+    if (slot < (unsigned)kStatSlots) atomicMax(&k_stat[slot], __float_as_uint(m));
+    else atomic_max_f32(stat_out + sample, m);
+  }
+}
+__device__ __forceinline__ void dw_stat_flush(const unsigned* k_stat, unsigned s_base, unsigned n_samples,
+                                              float* stat_out) {
+  __syncthreads();
+  if (threadIdx.x < kStatSlots && k_stat[threadIdx.x] != 0u && s_base + threadIdx.x < n_samples)
+    FQ_STAT_FLUSH_MAX(reinterpret_cast<unsigned*>(stat_out) + s_base + threadIdx.x, k_stat[threadIdx.x]);
+}
+
+// Loads are UNCONDITIONAL from clamped (always valid) addresses and masked afterwards with a bitwise AND — a
+// `cond ? load : 0` select is turned back into a predicated load by hipcc (CodeGenPrepare sinks the load under a
+// branch), which then waits vmcnt(0) right behind it and the prefetch ring is gone.
+__device__ __forceinline__ float keep(float v, bool ok) { return __uint_as_float(__float_as_uint(v) & (ok ? 0xFFFFFFFFu : 0u)); }
+__device__ __forceinline__ f4 keep4(f4 v, bool ok) {
+  const unsigned mk = ok ? 0xFFFFFFFFu : 0u;
+  f4 r;
+  r.x = __uint_as_float(__float_as_uint(v.x) & mk);
+  r.y = __uint_as_float(__float_as_uint(v.y) & mk);
+  r.z = __uint_as_float(__float_as_uint(v.z) & mk);
+  r.w = __uint_as_float(__float_as_uint(v.w) & mk);
+  return r;
+}
+// The value the lane on the left / right holds, 0 for the edge lane of a plane.  The shift is taken by EVERY lane and masked
+// afterwards: under a branch the edge lanes would be switched off, and a DPP read from a switched-off lane returns 0
+__device__ __forceinline__ float left_of(float v, bool first) {
+  const float t = lane_prev(v);
+  return first ? 0.0f : t;
+}
+__device__ __forceinline__ float right_of(float v, bool last) {
+  const float t = lane_next(v);
+  return last ? 0.0f : t;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // K2c: depthwise 3x3 (pad 1, stride S) with quantise-on-load and BN / activation / statistic epilogue.
 // A workgroup step ("tile") is P whole planes (small planes) or a strip of output rows of one plane (large planes).
@@ -36,13 +165,8 @@ __global__ __launch_bounds__(kBlock) void dwconv3x3_kernel(const float* __restri
                                                            float* __restrict__ stat_out) {
   extern __shared__ __attribute__((aligned(16))) float tile[];
   __shared__ float red[4];
-  QParams q;
-  q.lo = q.hi = q.denom = q.scale = 0.0f;
-  q.rden = 0.0;
-  if (QUANT) {
-    const float max_ = input_threshold(in_stat, n, ONLINE ? nullptr : in_thr, cur_max_out, blockIdx.x == 0);
-    q = make_qparams_rt(max_, levels, lo_neg_max, eps, in_thr);
-  }
+  QParams q = {};
+  if (QUANT) q = dw_qparams<ONLINE>(in_stat, n, in_thr, levels, lo_neg_max, eps, cur_max_out);
   const int lds_elems = g.P * g.IR * g.WS;
   const int plane_in = g.H * g.W, plane_out = g.Ho * g.Wo;
   const bool has_bn = bn_scale != nullptr;
@@ -146,16 +270,7 @@ __global__ __launch_bounds__(kBlock) void dwconv3x3_kernel(const float* __restri
           const float* lc = lb + g.WS;
           c0 = lc[0]; c1 = lc[1]; c2 = lc[2];
         }
-        float acc = 0.0f;
-        acc = fmaf(w00, a0, acc);
-        acc = fmaf(w01, a1, acc);
-        acc = fmaf(w02, a2, acc);
-        acc = fmaf(w10, b0, acc);
-        acc = fmaf(w11, b1, acc);
-        acc = fmaf(w12, b2, acc);
-        acc = fmaf(w20, c0, acc);
-        acc = fmaf(w21, c1, acc);
-        acc = fmaf(w22, c2, acc);
+        float acc = dw_taps(w00, w01, w02, w10, w11, w12, w20, w21, w22, a0, a1, a2, b0, b1, b2, c0, c1, c2);
         if (bias != nullptr) acc = (act & kActBiasMul) ? acc * bch : acc + bch;
         if (has_bn) {
           acc = acc * bsc;
@@ -206,21 +321,17 @@ __global__ __launch_bounds__(kBlock) void dwconv3x3_cols_kernel(
   // output rows of input kept in flight (S=2: 4 loads per row).  (16 / 8 - every row of a 14x14 plane in flight at
   // once - measured SLOWER on the same box: 38 vs 36 us per 512x14x14 layer.)
   constexpr int D = (S == 1) ? 8 : 4;
-  constexpr int kStatSlots = 16;
   __shared__ unsigned k_stat[kStatSlots];
   if (threadIdx.x < kStatSlots) k_stat[threadIdx.x] = 0u;
   PW_STAMP(0);
   // The quantisation parameters are derived AFTER the first block's loads have been issued (ensure_q below): the batch
   // statistic is a dependent chain of two cold loads + an fp64 tree (~2.8 us per workgroup, tools/dw_trace.py) that
   // otherwise sits in front of the first useful load of every workgroup.
-  QParams q;
-  q.lo = q.hi = q.denom = q.scale = 0.0f;
-  q.rden = 0.0;
+  QParams q = {};
   bool q_ready = !QUANT;
   auto ensure_q = [&]() __attribute__((always_inline)) {
     if (QUANT && !q_ready) {
-      const float max_ = input_threshold(in_stat, n, ONLINE ? nullptr : in_thr, cur_max_out, blockIdx.x == 0);
-      q = make_qparams_rt(max_, levels, lo_neg_max, eps, in_thr);
+      q = dw_qparams<ONLINE>(in_stat, n, in_thr, levels, lo_neg_max, eps, cur_max_out);
       q_ready = true;
     }
   };
@@ -235,20 +346,10 @@ __global__ __launch_bounds__(kBlock) void dwconv3x3_cols_kernel(
   const int plane_in = g.H * g.W, plane_out = g.Ho * g.Wo;
 
   // (Row strips per plane were tried for load balance and measured slower: every strip restarts the prefetch ring.)
-  // A workgroup takes a CONTIGUOUS range of blocks (few samples -> a small LDS statistic table, one flush) and its
-  // wavefronts run through them without barriers.  Index arithmetic is unsigned 32-bit (host: total_segs < 2^31): the
-  // 64-bit divisions it replaces cost each block 2.3 us (tools/dw_trace.py).
-  const unsigned nblk_u = (unsigned)nblk, tsegs = (unsigned)total_segs, nsegx = (unsigned)g.nsegx, C_u = (unsigned)g.C;
-  const unsigned blk_begin = (unsigned)((uint64_t)nblk_u * blockIdx.x / gridDim.x);
-  const unsigned blk_end = (unsigned)((uint64_t)nblk_u * (blockIdx.x + 1) / gridDim.x);
-  const unsigned n_samples = tsegs / nsegx / C_u;
-  unsigned s_base;
-  {
-    const unsigned seg0 = blk_begin * (unsigned)segs_per_block;
-    s_base = (seg0 < tsegs ? seg0 : tsegs - 1) / nsegx / C_u;
-  }
+  const unsigned tsegs = (unsigned)total_segs, nsegx = (unsigned)g.nsegx, C_u = (unsigned)g.C;
+  const DwBlkRange rg = dw_block_range((unsigned)nblk, tsegs, (unsigned)segs_per_block, nsegx, C_u);
   __syncthreads();                                       // statistic table zeroed
-  for (unsigned blk = blk_begin; blk < blk_end; ++blk) {
+  for (unsigned blk = rg.begin; blk < rg.end; ++blk) {
     const unsigned seg = blk * (unsigned)segs_per_block + (unsigned)wave * (unsigned)g.segs + (unsigned)seg_in_wave;
     const bool seg_ok = lane_used && seg < tsegs;
     const unsigned plane = seg_ok ? seg / nsegx : 0u;
@@ -278,13 +379,9 @@ __global__ __launch_bounds__(kBlock) void dwconv3x3_cols_kernel(
     const float bch = bias != nullptr ? bias[ch] : 0.0f;
     const float bsc = has_bn ? bn_scale[ch] : 1.0f, bsh = has_bn ? bn_shift[ch] : 0.0f;
     float m = 0.0f;
-    if (blk == blk_begin) PW_STAMP(2);
+    if (blk == rg.begin) PW_STAMP(2);
 
-    // Loads are UNCONDITIONAL from clamped (always valid) addresses and masked afterwards with a bitwise AND — a
-    // `cond ? load : 0` select is turned back into a predicated load by hipcc (CodeGenPrepare sinks the load under a
-    // branch), which then waits vmcnt(0) right behind it and the prefetch ring is gone.
-    const int last_row = g.H - 1;
-    auto keep = [](float v, bool ok) -> float { return __uint_as_float(__float_as_uint(v) & (ok ? 0xFFFFFFFFu : 0u)); };
+    const int last_row = g.H - 1;                          // (loads: unconditional from a clamped row, masked by keep)
     if (S == 1) {
       // rows: a = input row r-1, b = row r, c = row r+1 (each as left / centre / right)
       const float* xs = ld0 ? xp : x;                      // lanes with nothing to load read element 0
@@ -295,16 +392,7 @@ __global__ __launch_bounds__(kBlock) void dwconv3x3_cols_kernel(
       auto emit = [&](int r, float c1, float& a0, float& a1, float& a2, float& b0, float& b1, float& b2) {
         if (QUANT) c1 = fq_code(c1, q) * q.scale;
         const float c0 = lane_prev(c1), c2 = lane_next(c1);
-        float acc = 0.0f;
-        acc = fmaf(w00, a0, acc);
-        acc = fmaf(w01, a1, acc);
-        acc = fmaf(w02, a2, acc);
-        acc = fmaf(w10, b0, acc);
-        acc = fmaf(w11, b1, acc);
-        acc = fmaf(w12, b2, acc);
-        acc = fmaf(w20, c0, acc);
-        acc = fmaf(w21, c1, acc);
-        acc = fmaf(w22, c2, acc);
+        float acc = dw_taps(w00, w01, w02, w10, w11, w12, w20, w21, w22, a0, a1, a2, b0, b1, b2, c0, c1, c2);
         acc = dw_finish<EPI>(acc, bias != nullptr, bch, has_bn, bsc, bsh, act);
         m = fmaxf(m, keep(fabsf(acc), is_out));
         if (is_out) yp[(int64_t)r * g.Wo] = acc;
@@ -354,16 +442,7 @@ __global__ __launch_bounds__(kBlock) void dwconv3x3_cols_kernel(
           c2 = fq_code(c2, q) * q.scale;
         }
         const float b0 = lane_prev(b2), c0 = lane_prev(c2);
-        float acc = 0.0f;
-        acc = fmaf(w00, a0, acc);
-        acc = fmaf(w01, a1, acc);
-        acc = fmaf(w02, a2, acc);
-        acc = fmaf(w10, b0, acc);
-        acc = fmaf(w11, b1, acc);
-        acc = fmaf(w12, b2, acc);
-        acc = fmaf(w20, c0, acc);
-        acc = fmaf(w21, c1, acc);
-        acc = fmaf(w22, c2, acc);
+        float acc = dw_taps(w00, w01, w02, w10, w11, w12, w20, w21, w22, a0, a1, a2, b0, b1, b2, c0, c1, c2);
         acc = dw_finish<EPI>(acc, bias != nullptr, bch, has_bn, bsc, bsh, act);
         m = fmaxf(m, keep(fabsf(acc), is_out));
         if (is_out) yp[(int64_t)r * g.Wo] = acc;
@@ -398,30 +477,10 @@ __global__ __launch_bounds__(kBlock) void dwconv3x3_cols_kernel(
       for (int k = 0; k < D; ++k)
         if (r0 + k < rend) emit2(r0 + k, rb0[k], rb1[k], rc0[k], rc1[k], a0, a1, a2);
     }
-    if (blk == blk_begin) PW_STAMP(3);
-    if (has_stat) {
-      // per-wave update of the workgroup's LDS table (no barrier inside the block loop); flushed once at the end
-      const unsigned s0 = (unsigned)__builtin_amdgcn_readfirstlane(sample);
-      const bool wave_uniform = __all(!is_out || (unsigned)sample == s0);
-      if (wave_uniform) {
-        const float wm = wave_max_nonneg(is_out ? m : 0.0f);
-        if (lane == 0 && __float_as_uint(wm) != 0u) {
-          const unsigned slot = s0 - s_base;
-          if (slot < (unsigned)kStatSlots) atomicMax(&k_stat[slot], __float_as_uint(wm));
-          else atomic_max_f32(stat_out + s0, wm);
-        }
-      } else if (is_out) {
-        const unsigned slot = (unsigned)sample - s_base;
-        if (slot < (unsigned)kStatSlots) atomicMax(&k_stat[slot], __float_as_uint(m));
-        else atomic_max_f32(stat_out + sample, m);
-      }
-    }
+    if (blk == rg.begin) PW_STAMP(3);
+    if (has_stat) dw_stat_update(k_stat, rg.s_base, sample, is_out, m, lane, stat_out);
   }
-  if (has_stat) {
-    __syncthreads();
-    if (threadIdx.x < kStatSlots && k_stat[threadIdx.x] != 0u && s_base + threadIdx.x < (unsigned)n_samples)
-      FQ_STAT_FLUSH_MAX(reinterpret_cast<unsigned*>(stat_out) + s_base + threadIdx.x, k_stat[threadIdx.x]);
-  }
+  if (has_stat) dw_stat_flush(k_stat, rg.s_base, rg.n_samples, stat_out);
   PW_STAMP(5);
 }
 
@@ -438,7 +497,6 @@ __global__ __launch_bounds__(kBlock) void dwconv3x3_cols_kernel(
 // Buffer addressing: idle lanes and the tail read 0 and store nothing through an out-of-range offset, row strides sit in
 // scalar registers.
 // ---------------------------------------------------------------------------------------------------------------
-typedef float f2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f2 buf_ld_2f32(fq_rsrc r, unsigned voff, unsigned soff) {
   return __builtin_bit_cast(f2, __builtin_amdgcn_raw_buffer_load_b64(r, (int)voff, (int)soff, 0));
 }
@@ -446,7 +504,6 @@ __device__ __forceinline__ void buf_st_2f32(fq_rsrc r, unsigned voff, unsigned s
   typedef unsigned v2u __attribute__((ext_vector_type(2)));
   __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u, v), r, (int)voff, (int)soff, 0);
 }
-__device__ __forceinline__ f2 splat2(float v) { return (f2){v, v}; }
 
 template <int EPI>
 __device__ __forceinline__ f2 dw_finish2(f2 acc, bool has_bias, float bch, bool has_bn, float bsc, float bsh, int act) {
@@ -484,7 +541,6 @@ __global__ __launch_bounds__(kBlock) void dwconv3x3_planes_kernel(
   typedef DwPlanesBlk<S, H, CPL> Blk;
   constexpr int KIN = Blk::kIn;
   constexpr int HO = (H - 1) / S + 1;
-  constexpr int kStatSlots = 16;
   constexpr unsigned kOob = 0x80000000u;                 // beyond every resource of this kernel (host: tensors < 2 GiB)
   __shared__ unsigned k_stat[kStatSlots];
   if (threadIdx.x < kStatSlots) k_stat[threadIdx.x] = 0u;
@@ -497,15 +553,8 @@ __global__ __launch_bounds__(kBlock) void dwconv3x3_planes_kernel(
   const bool first = pos == 0, last = pos == g.SEG - 1;   // edge lanes of a plane: no left / right neighbour
   const unsigned segs_per_block = (unsigned)g.segs * (kBlock / 64);
   const unsigned tsegs = (unsigned)total_segs, C_u = (unsigned)g.C;           // one segment per plane: tsegs planes
-  const unsigned nblk = (tsegs + segs_per_block - 1) / segs_per_block;
-  const unsigned blk_begin = (unsigned)((uint64_t)nblk * blockIdx.x / gridDim.x);
-  const unsigned blk_end = (unsigned)((uint64_t)nblk * (blockIdx.x + 1) / gridDim.x);
-  const unsigned n_samples = tsegs / C_u;
-  unsigned s_base;
-  {
-    const unsigned seg0 = blk_begin * segs_per_block;
-    s_base = (seg0 < tsegs ? seg0 : tsegs - 1) / C_u;
-  }
+  const DwBlkRange rg = dw_block_range((tsegs + segs_per_block - 1) / segs_per_block, tsegs, segs_per_block, 1u, C_u);
+  const unsigned blk_begin = rg.begin, blk_end = rg.end;
   const bool has_bn = bn_scale != nullptr, has_stat = stat_out != nullptr, has_bias = bias != nullptr;
   const unsigned plane_in = (unsigned)(H * g.W), plane_out = (unsigned)(HO * g.Wo);
   const unsigned row_in = (unsigned)g.W * 4u, row_out = (unsigned)g.Wo * 4u;
@@ -542,13 +591,9 @@ __global__ __launch_bounds__(kBlock) void dwconv3x3_planes_kernel(
   FQ_PIN();
   if (blk_begin < blk_end) issue(blk_begin, nxt);
   FQ_PIN();
-  QParams q;
-  q.lo = q.hi = q.denom = q.scale = 0.0f;
-  q.rden = 0.0;
-  if (QUANT) {                                            // while the first block is on its way
-    const float max_ = threshold_finish(treq, in_stat, n, ONLINE ? nullptr : in_thr, cur_max_out, blockIdx.x == 0);
-    q = make_qparams_rt(max_, levels, lo_neg_max, eps, in_thr);
-  }
+  QParams q = {};
+  if (QUANT)                                              // while the first block is on its way
+    q = dw_qparams_finish<ONLINE>(treq, in_stat, n, in_thr, levels, lo_neg_max, eps, cur_max_out);
   PW_STAMP(1);
   __syncthreads();                                        // statistic table zeroed
   for (unsigned blk = blk_begin; blk < blk_end; ++blk) {
@@ -569,45 +614,27 @@ __global__ __launch_bounds__(kBlock) void dwconv3x3_planes_kernel(
     const unsigned sample = (seg < tsegs ? seg : tsegs - 1) / C_u;
     float m = 0.0f;
     auto fq = [&](float v) -> float { return QUANT ? fq_code(v, q) * q.scale : v; };
-    // the value the lane on the left / right holds.  The shift is taken by EVERY lane and masked afterwards: under a
-    // branch the edge lanes would be switched off, and a DPP read from a switched-off lane returns 0
-    auto left_of = [&](float v) -> float {
-      const float t = lane_prev(v);
-      return first ? 0.0f : t;
-    };
-    auto right_of = [&](float v) -> float {
-      const float t = lane_next(v);
-      return last ? 0.0f : t;
-    };
+    const float* w = cur.w;
     if (S == 1 && CPL == 2) {
       // two outputs per lane: (L, q0, q1) and (q0, q1, R) per input row, summed as one packed chain
       f2 aL = {0.f, 0.f}, aC = {0.f, 0.f}, aR = {0.f, 0.f};     // row r-1: (L, q0), (q0, q1), (q1, R)
       f2 bL, bC, bR;
       {
         const float q0 = fq(cur.raw[0]), q1 = fq(cur.raw[1]);
-        bL = (f2){left_of(q1), q0};
+        bL = (f2){left_of(q1, first), q0};
         bC = (f2){q0, q1};
-        bR = (f2){q1, right_of(q0)};
+        bR = (f2){q1, right_of(q0, last)};
       }
 #pragma unroll
       for (int r = 0; r < H; ++r) {
         f2 cL = {0.f, 0.f}, cC = {0.f, 0.f}, cR = {0.f, 0.f};
         if (r + 1 < H) {
           const float q0 = fq(cur.raw[2 * r + 2]), q1 = fq(cur.raw[2 * r + 3]);
-          cL = (f2){left_of(q1), q0};
+          cL = (f2){left_of(q1, first), q0};
           cC = (f2){q0, q1};
-          cR = (f2){q1, right_of(q0)};
+          cR = (f2){q1, right_of(q0, last)};
         }
-        f2 acc = {0.f, 0.f};
-        acc = __builtin_elementwise_fma(splat2(cur.w[0]), aL, acc);
-        acc = __builtin_elementwise_fma(splat2(cur.w[1]), aC, acc);
-        acc = __builtin_elementwise_fma(splat2(cur.w[2]), aR, acc);
-        acc = __builtin_elementwise_fma(splat2(cur.w[3]), bL, acc);
-        acc = __builtin_elementwise_fma(splat2(cur.w[4]), bC, acc);
-        acc = __builtin_elementwise_fma(splat2(cur.w[5]), bR, acc);
-        acc = __builtin_elementwise_fma(splat2(cur.w[6]), cL, acc);
-        acc = __builtin_elementwise_fma(splat2(cur.w[7]), cC, acc);
-        acc = __builtin_elementwise_fma(splat2(cur.w[8]), cR, acc);
+        f2 acc = dw_taps2(w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7], w[8], aL, aC, aR, bL, bC, bR, cL, cC, cR);
         acc = dw_finish2<EPI>(acc, has_bias, cur.bch, has_bn, cur.bsc, cur.bsh, act);
         m = fmaxf(m, fmaxf(fabsf(acc.x), fabsf(acc.y)));
         buf_st_2f32(ry, yoff, (unsigned)r * row_out, acc);
@@ -621,29 +648,19 @@ __global__ __launch_bounds__(kBlock) void dwconv3x3_planes_kernel(
         buf_st_f32(ry, yoff, (unsigned)r * row_out, acc);
       };
       auto window = [&](float a0, float a1, float a2, float b0, float b1, float b2, float c0, float c1, float c2) -> float {
-        float acc = 0.0f;
-        acc = fmaf(cur.w[0], a0, acc);
-        acc = fmaf(cur.w[1], a1, acc);
-        acc = fmaf(cur.w[2], a2, acc);
-        acc = fmaf(cur.w[3], b0, acc);
-        acc = fmaf(cur.w[4], b1, acc);
-        acc = fmaf(cur.w[5], b2, acc);
-        acc = fmaf(cur.w[6], c0, acc);
-        acc = fmaf(cur.w[7], c1, acc);
-        acc = fmaf(cur.w[8], c2, acc);
-        return acc;
+        return dw_taps(w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7], w[8], a0, a1, a2, b0, b1, b2, c0, c1, c2);
       };
       if (S == 1) {
         float a0 = 0.f, a1 = 0.f, a2 = 0.f;
         float b1 = fq(cur.raw[0]);
-        float b0 = left_of(b1), b2 = right_of(b1);
+        float b0 = left_of(b1, first), b2 = right_of(b1, last);
 #pragma unroll
         for (int r = 0; r < H; ++r) {
           float c0 = 0.f, c1 = 0.f, c2 = 0.f;
           if (r + 1 < H) {
             c1 = fq(cur.raw[r + 1]);
-            c0 = left_of(c1);
-            c2 = right_of(c1);
+            c0 = left_of(c1, first);
+            c2 = right_of(c1, last);
           }
           finish(r, window(a0, a1, a2, b0, b1, b2, c0, c1, c2));
           a0 = b0; a1 = b1; a2 = b2;
@@ -655,42 +672,22 @@ __global__ __launch_bounds__(kBlock) void dwconv3x3_planes_kernel(
 #pragma unroll
         for (int r = 0; r < HO; ++r) {
           const float b1 = fq(cur.raw[4 * r]), b2 = fq(cur.raw[4 * r + 1]);
-          const float b0 = left_of(b2);
+          const float b0 = left_of(b2, first);
           float c0 = 0.f, c1 = 0.f, c2 = 0.f;
           if (2 * r + 1 < H) {
             c1 = fq(cur.raw[4 * r + 2]);
             c2 = fq(cur.raw[4 * r + 3]);
-            c0 = left_of(c2);
+            c0 = left_of(c2, first);
           }
           finish(r, window(a0, a1, a2, b0, b1, b2, c0, c1, c2));
           a0 = c0; a1 = c1; a2 = c2;
         }
       }
     }
-    if (has_stat) {
-      m = is_out ? m : 0.0f;
-      const unsigned s0 = (unsigned)__builtin_amdgcn_readfirstlane((int)sample);
-      const bool wave_uniform = __all(!is_out || sample == s0);
-      if (wave_uniform) {
-        const float wm = wave_max_nonneg(m);
-        if (lane == 0 && __float_as_uint(wm) != 0u) {
-          const unsigned slot = s0 - s_base;
-          if (slot < (unsigned)kStatSlots) atomicMax(&k_stat[slot], __float_as_uint(wm));
-          else atomic_max_f32(stat_out + s0, wm);
-        }
-      } else if (is_out) {
-        const unsigned slot = sample - s_base;
-        if (slot < (unsigned)kStatSlots) atomicMax(&k_stat[slot], __float_as_uint(m));
-        else atomic_max_f32(stat_out + sample, m);
-      }
-    }
+    if (has_stat) dw_stat_update(k_stat, rg.s_base, sample, is_out, m, lane, stat_out);
   }
   PW_STAMP(3);
-  if (has_stat) {
-    __syncthreads();
-    if (threadIdx.x < kStatSlots && k_stat[threadIdx.x] != 0u && s_base + threadIdx.x < n_samples)
-      FQ_STAT_FLUSH_MAX(reinterpret_cast<unsigned*>(stat_out) + s_base + threadIdx.x, k_stat[threadIdx.x]);
-  }
+  if (has_stat) dw_stat_flush(k_stat, rg.s_base, rg.n_samples, stat_out);
   PW_STAMP(5);
 }
 
@@ -742,7 +739,6 @@ __global__ __launch_bounds__(kBlock) void dwconv3x3_flat_kernel(
   constexpr bool TAIL_OK = IN % 4 == 0 && OUT % 4 == 0;  // else the host only takes tensors of whole blocks (planes % P == 0)
   constexpr int NFI = P * IN / 4, NFO = P * OUT / 4;   // 16-byte groups per wavefront and block, in / out
   constexpr int NLI = (NFI + 63) / 64, NLO = (NFO + 63) / 64;
-  constexpr int kStatSlots = 16;
   constexpr unsigned kOob = 0x80000000u;   // beyond every resource of this kernel (host: tensors < 2 GiB)
   __shared__ f4 tile[kBlock / 64][NLI * 64];
   __shared__ f4 otile[kBlock / 64][DOWN ? NLO * 64 : 1];  // stride 1 writes its results over the tile rows already consumed
@@ -803,13 +799,9 @@ __global__ __launch_bounds__(kBlock) void dwconv3x3_flat_kernel(
   if (blk_begin < blk_end) issue(blk_begin, nxt);
   FQ_PIN();
   PW_STAMP(7);
-  QParams q;
-  q.lo = q.hi = q.denom = q.scale = 0.0f;
-  q.rden = 0.0;
-  if (QUANT) {                                            // while the first block is on its way
-    const float max_ = threshold_finish(treq, in_stat, n, ONLINE ? nullptr : in_thr, cur_max_out, blockIdx.x == 0);
-    q = make_qparams_rt(max_, levels, lo_neg_max, eps, in_thr);
-  }
+  QParams q = {};
+  if (QUANT)                                              // while the first block is on its way
+    q = dw_qparams_finish<ONLINE>(treq, in_stat, n, in_thr, levels, lo_neg_max, eps, cur_max_out);
   PW_STAMP(1);
   __syncthreads();                                        // statistic table zeroed
   for (unsigned blk = blk_begin; blk < blk_end; ++blk) {
@@ -834,46 +826,27 @@ __global__ __launch_bounds__(kBlock) void dwconv3x3_flat_kernel(
     float m = 0.0f;
     const bool is_out = b_lane && j < left;
     if (b_lane) {
-      auto left_of = [&](float v) -> float {              // (every lane takes the shift; the edge lanes drop it afterwards)
-        const float t = lane_prev(v);
-        return first ? 0.0f : t;
-      };
-      auto right_of = [&](float v) -> float {
-        const float t = lane_next(v);
-        return last ? 0.0f : t;
-      };
+      const f4 w03 = cur.w03, w47 = cur.w47;
       if (PAIR) {
         float* lp = my_tile + j * IN + pos * 2;
-        const f2 w0 = splat2(cur.w03.x), w1 = splat2(cur.w03.y), w2 = splat2(cur.w03.z), w3 = splat2(cur.w03.w),
-                 w4 = splat2(cur.w47.x), w5 = splat2(cur.w47.y), w6 = splat2(cur.w47.z), w7 = splat2(cur.w47.w),
-                 w8 = splat2(cur.w8);
         f2 aL = {0.f, 0.f}, aC = {0.f, 0.f}, aR = {0.f, 0.f};     // row r-1: (L, q0), (q0, q1), (q1, R)
         f2 bL, bC, bR;
         {
           const f2 v = *reinterpret_cast<const f2*>(lp);
-          bL = (f2){left_of(v.y), v.x};
+          bL = (f2){left_of(v.y, first), v.x};
           bC = v;
-          bR = (f2){v.y, right_of(v.x)};
+          bR = (f2){v.y, right_of(v.x, last)};
         }
 #pragma unroll
         for (int r = 0; r < H; ++r) {
           f2 cL = {0.f, 0.f}, cC = {0.f, 0.f}, cR = {0.f, 0.f};
           if (r + 1 < H) {
             const f2 v = *reinterpret_cast<const f2*>(lp + (r + 1) * W);
-            cL = (f2){left_of(v.y), v.x};
+            cL = (f2){left_of(v.y, first), v.x};
             cC = v;
-            cR = (f2){v.y, right_of(v.x)};
+            cR = (f2){v.y, right_of(v.x, last)};
           }
-          f2 acc = {0.f, 0.f};
-          acc = __builtin_elementwise_fma(w0, aL, acc);
-          acc = __builtin_elementwise_fma(w1, aC, acc);
-          acc = __builtin_elementwise_fma(w2, aR, acc);
-          acc = __builtin_elementwise_fma(w3, bL, acc);
-          acc = __builtin_elementwise_fma(w4, bC, acc);
-          acc = __builtin_elementwise_fma(w5, bR, acc);
-          acc = __builtin_elementwise_fma(w6, cL, acc);
-          acc = __builtin_elementwise_fma(w7, cC, acc);
-          acc = __builtin_elementwise_fma(w8, cR, acc);
+          f2 acc = dw_taps2(w03.x, w03.y, w03.z, w03.w, w47.x, w47.y, w47.z, w47.w, cur.w8, aL, aC, aR, bL, bC, bR, cL, cC, cR);
           acc = dw_finish2<EPI>(acc, has_bias, cur.bch, has_bn, cur.bsc, cur.bsh, act);
           m = fmaxf(m, fmaxf(fabsf(acc.x), fabsf(acc.y)));
           *reinterpret_cast<f2*>(lp + r * W) = acc;          // row r of the tile was read in the previous step
@@ -882,16 +855,7 @@ __global__ __launch_bounds__(kBlock) void dwconv3x3_flat_kernel(
         }
       } else {
         auto window = [&](float a0, float a1, float a2, float b0, float b1, float b2, float c0, float c1, float c2) -> float {
-          float acc = 0.0f;
-          acc = fmaf(cur.w03.x, a0, acc);
-          acc = fmaf(cur.w03.y, a1, acc);
-          acc = fmaf(cur.w03.z, a2, acc);
-          acc = fmaf(cur.w03.w, b0, acc);
-          acc = fmaf(cur.w47.x, b1, acc);
-          acc = fmaf(cur.w47.y, b2, acc);
-          acc = fmaf(cur.w47.z, c0, acc);
-          acc = fmaf(cur.w47.w, c1, acc);
-          acc = fmaf(cur.w8, c2, acc);
+          float acc = dw_taps(w03.x, w03.y, w03.z, w03.w, w47.x, w47.y, w47.z, w47.w, cur.w8, a0, a1, a2, b0, b1, b2, c0, c1, c2);
           acc = dw_finish<EPI>(acc, has_bias, cur.bch, has_bn, cur.bsc, cur.bsh, act);
           m = fmaxf(m, fabsf(acc));
           return acc;
@@ -900,14 +864,14 @@ __global__ __launch_bounds__(kBlock) void dwconv3x3_flat_kernel(
           float* lp = my_tile + j * IN + pos;
           float a0 = 0.f, a1 = 0.f, a2 = 0.f;
           float b1 = lp[0];
-          float b0 = left_of(b1), b2 = right_of(b1);
+          float b0 = left_of(b1, first), b2 = right_of(b1, last);
 #pragma unroll
           for (int r = 0; r < H; ++r) {
             float c0 = 0.f, c1 = 0.f, c2 = 0.f;
             if (r + 1 < H) {
               c1 = lp[(r + 1) * W];
-              c0 = left_of(c1);
-              c2 = right_of(c1);
+              c0 = left_of(c1, first);
+              c2 = right_of(c1, last);
             }
             lp[r * W] = window(a0, a1, a2, b0, b1, b2, c0, c1, c2);
             a0 = b0; a1 = b1; a2 = b2;
@@ -921,13 +885,13 @@ __global__ __launch_bounds__(kBlock) void dwconv3x3_flat_kernel(
 #pragma unroll
           for (int r = 0; r < HO; ++r) {
             const f2 vb = *reinterpret_cast<const f2*>(lp + (2 * r) * W);
-            const float b0 = left_of(vb.y);
+            const float b0 = left_of(vb.y, first);
             float c0 = 0.f, c1 = 0.f, c2 = 0.f;
             if (2 * r + 1 < H) {
               const f2 vc = *reinterpret_cast<const f2*>(lp + (2 * r + 1) * W);
               c1 = vc.x;
               c2 = vc.y;
-              c0 = left_of(vc.y);
+              c0 = left_of(vc.y, first);
             }
             op[r * WO] = window(a0, a1, a2, b0, vb.x, vb.y, c0, c1, c2);
             a0 = c0; a1 = c1; a2 = c2;
@@ -947,31 +911,13 @@ __global__ __launch_bounds__(kBlock) void dwconv3x3_flat_kernel(
       hold_store_data(ov);              // fq_common.h: nothing may write a store's data registers right behind it
     }
     if (has_stat) {
-      m = is_out ? m : 0.0f;
       const unsigned sample = fast_div(base + (is_out ? j : 0u), g.by_c);
-      const unsigned s0 = (unsigned)__builtin_amdgcn_readfirstlane((int)sample);
-      const bool wave_uniform = __all(!is_out || sample == s0);
-      if (wave_uniform) {
-        const float wm = wave_max_nonneg(m);
-        if (lane == 0 && __float_as_uint(wm) != 0u) {
-          const unsigned slot = s0 - s_base;
-          if (slot < (unsigned)kStatSlots) atomicMax(&k_stat[slot], __float_as_uint(wm));
-          else atomic_max_f32(stat_out + s0, wm);
-        }
-      } else if (is_out) {
-        const unsigned slot = sample - s_base;
-        if (slot < (unsigned)kStatSlots) atomicMax(&k_stat[slot], __float_as_uint(m));
-        else atomic_max_f32(stat_out + sample, m);
-      }
+      dw_stat_update(k_stat, s_base, sample, is_out, m, (int)lane, stat_out);
     }
     __builtin_amdgcn_wave_barrier();                      // (the next block's phase A overwrites the tile)
   }
   PW_STAMP(3);
-  if (has_stat) {
-    __syncthreads();
-    if (threadIdx.x < kStatSlots && k_stat[threadIdx.x] != 0u && s_base + threadIdx.x < n_samples)
-      FQ_STAT_FLUSH_MAX(reinterpret_cast<unsigned*>(stat_out) + s_base + threadIdx.x, k_stat[threadIdx.x]);
-  }
+  if (has_stat) dw_stat_flush(k_stat, s_base, n_samples, stat_out);
   PW_STAMP(5);
 }
 
@@ -995,18 +941,12 @@ __global__ __launch_bounds__(kBlock) void dwconv3x3_cols4_kernel(
   // and hit the same DRAM pages; one load per step (a ring) spreads them ~700 cycles apart, and with thousands of
   // waves each streaming its own plane every access then opens a new page.
   constexpr int D = (S == 1) ? 4 : 2;
-  constexpr int kStatSlots = 16;
   __shared__ unsigned k_stat[kStatSlots];
   if (threadIdx.x < kStatSlots) k_stat[threadIdx.x] = 0u;
   // (deriving q after the first block's loads, as K2d does, was measured 3-5 % SLOWER here: the row bursts of these large
   // planes already hide the prologue, and the extra live state costs registers)
-  QParams q;
-  q.lo = q.hi = q.denom = q.scale = 0.0f;
-  q.rden = 0.0;
-  if (QUANT) {
-    const float max_ = input_threshold(in_stat, n, ONLINE ? nullptr : in_thr, cur_max_out, blockIdx.x == 0);
-    q = make_qparams_rt(max_, levels, lo_neg_max, eps, in_thr);
-  }
+  QParams q = {};
+  if (QUANT) q = dw_qparams<ONLINE>(in_stat, n, in_thr, levels, lo_neg_max, eps, cur_max_out);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int seg_in_wave = lane / g.SEG;
   const int pos = lane - seg_in_wave * g.SEG;
@@ -1016,31 +956,10 @@ __global__ __launch_bounds__(kBlock) void dwconv3x3_cols4_kernel(
   const bool has_bn = bn_scale != nullptr, has_stat = stat_out != nullptr;
   const int plane_in = g.H * g.W, plane_out = g.Ho * g.Wo;
   const int last_row = g.H - 1;
-  auto keep4 = [](f4 v, bool ok) -> f4 {
-    const unsigned mk = ok ? 0xFFFFFFFFu : 0u;
-    f4 r;
-    r.x = __uint_as_float(__float_as_uint(v.x) & mk);
-    r.y = __uint_as_float(__float_as_uint(v.y) & mk);
-    r.z = __uint_as_float(__float_as_uint(v.z) & mk);
-    r.w = __uint_as_float(__float_as_uint(v.w) & mk);
-    return r;
-  };
-  auto keep = [](float v, bool ok) -> float { return __uint_as_float(__float_as_uint(v) & (ok ? 0xFFFFFFFFu : 0u)); };
-
-  // A workgroup takes a CONTIGUOUS range of blocks (few samples -> a small LDS statistic table, one flush) and its
-  // wavefronts run through them without barriers.  Index arithmetic is unsigned 32-bit (host: total_segs < 2^31): the
-  // 64-bit divisions it replaces cost each block 2.3 us (tools/dw_trace.py).
-  const unsigned nblk_u = (unsigned)nblk, tsegs = (unsigned)total_segs, nsegx = (unsigned)g.nsegx, C_u = (unsigned)g.C;
-  const unsigned blk_begin = (unsigned)((uint64_t)nblk_u * blockIdx.x / gridDim.x);
-  const unsigned blk_end = (unsigned)((uint64_t)nblk_u * (blockIdx.x + 1) / gridDim.x);
-  const unsigned n_samples = tsegs / nsegx / C_u;
-  unsigned s_base;
-  {
-    const unsigned seg0 = blk_begin * (unsigned)segs_per_block;
-    s_base = (seg0 < tsegs ? seg0 : tsegs - 1) / nsegx / C_u;
-  }
+  const unsigned tsegs = (unsigned)total_segs, nsegx = (unsigned)g.nsegx, C_u = (unsigned)g.C;
+  const DwBlkRange rg = dw_block_range((unsigned)nblk, tsegs, (unsigned)segs_per_block, nsegx, C_u);
   __syncthreads();                                       // statistic table zeroed
-  for (unsigned blk = blk_begin; blk < blk_end; ++blk) {
+  for (unsigned blk = rg.begin; blk < rg.end; ++blk) {
     const unsigned seg = blk * (unsigned)segs_per_block + (unsigned)wave * (unsigned)g.segs + (unsigned)seg_in_wave;
     const bool seg_ok = lane_used && seg < tsegs;
     const unsigned plane = seg_ok ? seg / nsegx : 0u;
@@ -1089,17 +1008,8 @@ __global__ __launch_bounds__(kBlock) void dwconv3x3_cols4_kernel(
         float o[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-          float acc = 0.0f;
-          acc = fmaf(w00, a[k], acc);
-          acc = fmaf(w01, a[k + 1], acc);
-          acc = fmaf(w02, a[k + 2], acc);
-          acc = fmaf(w10, b[k], acc);
-          acc = fmaf(w11, b[k + 1], acc);
-          acc = fmaf(w12, b[k + 2], acc);
-          acc = fmaf(w20, c[k], acc);
-          acc = fmaf(w21, c[k + 1], acc);
-          acc = fmaf(w22, c[k + 2], acc);
-          o[k] = finish(acc);
+          o[k] = finish(dw_taps(w00, w01, w02, w10, w11, w12, w20, w21, w22, a[k], a[k + 1], a[k + 2], b[k], b[k + 1],
+                                b[k + 2], c[k], c[k + 1], c[k + 2]));
         }
         const float mm = fmaxf(fmaxf(fabsf(o[0]), fabsf(o[1])), fmaxf(fabsf(o[2]), fabsf(o[3])));
         m = fmaxf(m, keep(mm, is_out));
@@ -1142,17 +1052,8 @@ __global__ __launch_bounds__(kBlock) void dwconv3x3_cols4_kernel(
         float o[2];
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
-          float acc = 0.0f;
-          acc = fmaf(w00, a[2 * k], acc);
-          acc = fmaf(w01, a[2 * k + 1], acc);
-          acc = fmaf(w02, a[2 * k + 2], acc);
-          acc = fmaf(w10, b[2 * k], acc);
-          acc = fmaf(w11, b[2 * k + 1], acc);
-          acc = fmaf(w12, b[2 * k + 2], acc);
-          acc = fmaf(w20, c[2 * k], acc);
-          acc = fmaf(w21, c[2 * k + 1], acc);
-          acc = fmaf(w22, c[2 * k + 2], acc);
-          o[k] = finish(acc);
+          o[k] = finish(dw_taps(w00, w01, w02, w10, w11, w12, w20, w21, w22, a[2 * k], a[2 * k + 1], a[2 * k + 2], b[2 * k],
+                                b[2 * k + 1], b[2 * k + 2], c[2 * k], c[2 * k + 1], c[2 * k + 2]));
         }
         m = fmaxf(m, keep(fmaxf(fabsf(o[0]), fabsf(o[1])), is_out));
         if (is_out) {
@@ -1183,31 +1084,10 @@ __global__ __launch_bounds__(kBlock) void dwconv3x3_cols4_kernel(
       for (int k = 0; k < D; ++k)
         if (r0 + k < g.Ho) emit2(r0 + k, rb[k], rc[k]);
     }
-    if (has_stat) {
-      // per-wave update of the workgroup's LDS table (no barrier inside the block loop); flushed once at the end
-      const unsigned s0 = (unsigned)__builtin_amdgcn_readfirstlane(sample);
-      const bool wave_uniform = __all(!is_out || (unsigned)sample == s0);
-      if (wave_uniform) {
-        const float wm = wave_max_nonneg(is_out ? m : 0.0f);
-        if (lane == 0 && __float_as_uint(wm) != 0u) {
-          const unsigned slot = s0 - s_base;
-          if (slot < (unsigned)kStatSlots) atomicMax(&k_stat[slot], __float_as_uint(wm));
-          else atomic_max_f32(stat_out + s0, wm);
-        }
-      } else if (is_out) {
-        const unsigned slot = (unsigned)sample - s_base;
-        if (slot < (unsigned)kStatSlots) atomicMax(&k_stat[slot], __float_as_uint(m));
-        else atomic_max_f32(stat_out + sample, m);
-      }
-    }
+    if (has_stat) dw_stat_update(k_stat, rg.s_base, sample, is_out, m, lane, stat_out);
   }
-  if (has_stat) {
-    __syncthreads();
-    if (threadIdx.x < kStatSlots && k_stat[threadIdx.x] != 0u && s_base + threadIdx.x < (unsigned)n_samples)
-      FQ_STAT_FLUSH_MAX(reinterpret_cast<unsigned*>(stat_out) + s_base + threadIdx.x, k_stat[threadIdx.x]);
-  }
+  if (has_stat) dw_stat_flush(k_stat, rg.s_base, rg.n_samples, stat_out);
 }
-
 
 }  // namespace
 
@@ -1216,276 +1096,214 @@ __global__ __launch_bounds__(kBlock) void dwconv3x3_cols4_kernel(
 constexpr unsigned kFlagRangeRecord = 0x100u;
 constexpr unsigned kFlagBiasMultiplies = 0x200u;      // `bias` is the per-channel dequantisation factor (kActBiasMul)
 
-static int dwconv3x3_impl(const float* x, const float* w, const float* bias, float* y, int64_t n, int64_t c, int64_t h,
-                          int64_t wdt, int stride, const float* in_stat, const float* in_thr, int in_width, unsigned in_flags,
-                          float* out_current_max, const float* bn_scale, const float* bn_shift, int act, float* stat_out,
-                          fqStream_t stream) {
-  FQ_REQUIRE(x && w && y, "fq_dwconv3x3: null pointer");
-  FQ_REQUIRE(n > 0 && c > 0 && h > 0 && wdt > 0 && n * c < (1ll << 31) && h * wdt < (1ll << 28),
-             "fq_dwconv3x3: bad shape (n=%lld c=%lld h=%lld w=%lld)", (long long)n, (long long)c, (long long)h,
-             (long long)wdt);
-  FQ_REQUIRE(stride == 1 || stride == 2, "fq_dwconv3x3: stride must be 1 or 2, got %d", stride);
-  // in_stat alone: online; in_thr alone: offline; both: offline, the statistic only feeds out_current_max
-  FQ_REQUIRE((bn_scale == nullptr) == (bn_shift == nullptr), "fq_dwconv3x3: bn_scale and bn_shift go together");
-  const bool prezeroed = (act & FQ_STAT_PREZEROED) != 0;
-  act &= ~FQ_STAT_PREZEROED;
-  FQ_REQUIRE(act >= FQ_ACT_NONE && act <= FQ_ACT_RELU6, "fq_dwconv3x3: unknown activation %d", act);
-  const bool quant = in_stat != nullptr || in_thr != nullptr;
-  if (quant) FQ_REQUIRE(in_width >= 2 && in_width <= 16, "fq_dwconv3x3: width %d out of range", in_width);
-  if (in_flags & kFlagBiasMultiplies) act |= kActBiasMul;   // (after the range check; bias != NULL: run-time epilogue)
-  static const int epi_on = env_int("FQ_DW_EPI", 1);    // 0: always the run-time epilogue (A/B)
-  const int epi = (epi_on && bn_scale != nullptr && bias == nullptr)
-                      ? (act == FQ_ACT_RELU ? kEpiBnRelu : act == FQ_ACT_RELU6 ? kEpiBnRelu6 : kEpiRuntime)
-                      : kEpiRuntime;
-  hipStream_t st = (hipStream_t)stream;
-  static const int form = env_int("FQ_DW_FORM", 0);     // 0 auto, 1 LDS tiles, 2 sliding window 1 col/lane, 3: 4 cols/lane
-  const bool can4 = (wdt % 4 == 0) && aligned16(x) && aligned16(y) && ((h * wdt) % 4 == 0) &&
-                    (stride == 1 || ((wdt / 2) % 2 == 0));
-  // 14x14 (stride 1 and 2), 7x7 and 28x28 (stride 1 and 2) planes: flat 16-byte accesses through an LDS transpose (K2p)
-  // tuning: bit 0 14x14 s1, bit 1 14x14 s2, bit 2 7x7, bit 3 28x28 s1, bit 4 28x28 s2
-  // (28x28: 40.1 -> 34.6 us stride 1.  Stride 2 on 28x28 was dropped in round 2 because 0.05 % of its outputs changed from run
-  // to run at full size; round 3 found the cause - NOT a data race: a VALU write of a 16-byte buffer store's data register
-  // right behind the store, a hazard hipcc does not guard when soffset is a register (fq_common.h at buf_st_v4f,
-  // profiles/r3_dw_flat_race.txt, tools/isa_lint.py) - every instantiation of this kernel had the
-  // pattern one instruction further away.  With the stores guarded the form is exact at every occupancy.  Through round 4 it
-  // was built and tested but not chosen by shape - one batch at a time it was no faster than the four-columns-per-lane form
-  // (28.3 us against ~25; whole step 1.1967 against 1.1919 ms, profiles/r3_dw_flat_race.txt); with three batches in flight and
-  // its nontemporal loads it is: default workload +1.77 % images/s (sd 0.03, profiles/r5_heuristics_ab.txt).)
+namespace {
+
+// One call of the unit: the arguments and what every form derives from them.
+struct DwCall {
+  const float *x, *w, *bias;
+  float* y;
+  int64_t n, c, h, wdt;
+  int stride;
+  const float *in_stat, *in_thr;
+  float* out_current_max;
+  const float *bn_scale, *bn_shift;
+  int act;
+  float* stat_out;
+  hipStream_t st;
+  bool quant, online, prezeroed;
+  int epi;                  // kEpi*: the epilogue fixed at compile time, or the run-time one
+  float levels, eps;
+  int lo_neg;
+  int64_t ho, wo;
+};
+
+// The launch of every form: zeroes the statistic, opens the profile scope, turns (quant, online) and epi into template
+// arguments and launches kernel_for(quant_c, online_c, epi_c) with `geom...` between y and in_stat.
+template <class KernelFor, class... Geom>
+int dw_launch(const DwCall& d, int grid, size_t lds, KernelFor kernel_for, Geom... geom) {
+  using std::integral_constant;
+  if (d.stat_out && !d.prezeroed) FQ_HIP(hipMemsetAsync(d.stat_out, 0, d.n * sizeof(float), d.st));
+  ProfScope prof(FQ_KERNEL_DWCONV, 4.0 * ((double)d.n * d.c * d.h * d.wdt + (double)d.n * d.c * d.ho * d.wo), d.st);
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, d.st, d.x, d.w, d.bias, d.y, geom..., d.in_stat, (int)d.n,
+                       d.in_thr, d.levels, d.lo_neg, d.eps, d.out_current_max, d.bn_scale, d.bn_shift, d.act, d.stat_out);
+  };
+  auto with_epi = [&](auto quant_c, auto online_c) {
+    if (d.epi == kEpiBnRelu) launch(kernel_for(quant_c, online_c, integral_constant<int, kEpiBnRelu>{}));
+    else if (d.epi == kEpiBnRelu6) launch(kernel_for(quant_c, online_c, integral_constant<int, kEpiBnRelu6>{}));
+    else launch(kernel_for(quant_c, online_c, integral_constant<int, kEpiRuntime>{}));
+  };
+  if (!d.quant) with_epi(std::false_type{}, std::false_type{});
+  else if (d.online) with_epi(std::true_type{}, std::true_type{});
+  else with_epi(std::true_type{}, std::false_type{});
+  FQ_LAUNCH_CHECK();
+  return FQ_OK;
+}
+template <int V>
+using dw_int = std::integral_constant<int, V>;
+
+// Persistent grids: a block is what the four wavefronts of a workgroup do in one step (`segs` segments or planes each);
+// every workgroup is resident at once and walks a contiguous range of blocks.
+int64_t dw_blocks(int64_t total_segs, int segs) {
+  const int64_t per_block = (int64_t)segs * (kBlock / 64);
+  return (total_segs + per_block - 1) / per_block;
+}
+int dw_grid(int64_t nblk, int wg_per_cu) {
+  const int64_t cap = (int64_t)num_cu() * wg_per_cu;
+  return (int)(nblk < cap ? nblk : cap);
+}
+
+// Lanes of the register forms: a plane row of `units` compute lanes is cut into nsegx segments of sw lanes, each with `halo`
+// lanes beside them, and a wavefront holds as many segments as fit.
+DwColGeom dw_col_geom(const DwCall& d, int units, int halo) {
+  DwColGeom cg = {};
+  cg.C = (int)d.c;
+  cg.H = (int)d.h;
+  cg.W = (int)d.wdt;
+  cg.Ho = (int)d.ho;
+  cg.Wo = (int)d.wo;
+  const int max_sw = 64 - halo;
+  cg.nsegx = (units + max_sw - 1) / max_sw;
+  cg.sw = (units + cg.nsegx - 1) / cg.nsegx;
+  cg.SEG = cg.sw + halo;
+  cg.segs = 64 / cg.SEG;
+  return cg;
+}
+
+// ---- K2p, flat: 14x14 (stride 1 and 2), 7x7 and 28x28 (stride 1 and 2) planes ------------------------------------------------
+// tuning: bit 0 14x14 s1, bit 1 14x14 s2, bit 2 7x7, bit 3 28x28 s1, bit 4 28x28 s2
+// (28x28: 40.1 -> 34.6 us stride 1.  Stride 2 on 28x28 was dropped in round 2 because 0.05 % of its outputs changed from run
+// to run at full size; round 3 found the cause - NOT a data race: a VALU write of a 16-byte buffer store's data register
+// right behind the store, a hazard hipcc does not guard when soffset is a register (fq_common.h at buf_st_v4f,
+// profiles/r3_dw_flat_race.txt, tools/isa_lint.py) - every instantiation of this kernel had the
+// pattern one instruction further away.  With the stores guarded the form is exact at every occupancy.  Through round 4 it
+// was built and tested but not chosen by shape - one batch at a time it was no faster than the four-columns-per-lane form
+// (28.3 us against ~25; whole step 1.1967 against 1.1919 ms, profiles/r3_dw_flat_race.txt); with three batches in flight and
+// its nontemporal loads it is: default workload +1.77 % images/s (sd 0.03, profiles/r5_heuristics_ab.txt).)
+int dw_flat_kind(const DwCall& d) {           // the bit of FQ_DW_FLAT, -1: not a plane size of this form
+  return (d.h == 14 && d.wdt == 14) ? (d.stride == 1 ? 0 : 1)
+         : (d.h == 7 && d.wdt == 7 && d.stride == 1) ? 2
+         : (d.h == 28 && d.wdt == 28) ? (d.stride == 1 ? 3 : 4) : -1;
+}
+int dw_flat_planes(int kind) { return kind == 0 ? 9 : kind >= 3 ? 4 : 8; }      // per wavefront and block (dwconv3x3_flat_kernel: P)
+bool dw_flat_applies(const DwCall& d, int form) {
   static const int flat_on = env_int("FQ_DW_FLAT", 31) & 31;
-  {
-    const int kind = (h == 14 && wdt == 14) ? (stride == 1 ? 0 : 1)
-                     : (h == 7 && wdt == 7 && stride == 1) ? 2
-                     : (h == 28 && wdt == 28) ? (stride == 1 ? 3 : 4) : -1;
-    const int kP = kind == 0 ? 9 : kind >= 3 ? 4 : 8;      // planes per wavefront and block (dwconv3x3_flat_kernel: P)
-    const bool whole = kind == 0 || kind >= 3 || (n * c) % kP == 0;     // planes of 49 floats: no 16-byte tail
-    if (kind >= 0 && (form == 5 || (form == 0 && ((flat_on >> kind) & 1))) && whole && aligned16(x) && aligned16(y) &&
-        n * c * h * wdt * 4 < (1ll << 31)) {
-      DwFlatGeom fg;
-      fg.C = (int)c;
-      fg.planes = (unsigned)(n * c);
-      fg.by_c = fast_div_for((unsigned)c);
-      const int64_t nblk = (n * c + kP * (kBlock / 64) - 1) / (kP * (kBlock / 64));
-      static const int fl_tune = env_int("FQ_DW_FLAT_WG_PER_CU", 0);
-      // three workgroups per CU, each with one block in work and one requested: measured best for all three shapes
-      // (512 x 14x14: 2 / 3 / 4 / 6 per CU = 22.2 / 19.6 / 20.7 / 21.9 us; 1024 x 7x7: 16.1 / 14.6 / 17.3 (8) / 16.4 us)
-      const int fl_wg_per_cu = fl_tune > 0 ? fl_tune : 3;
-      const int grid = (int)(nblk < (int64_t)num_cu() * fl_wg_per_cu ? nblk : (int64_t)num_cu() * fl_wg_per_cu);
-      fg.per = (unsigned)(nblk / grid);
-      fg.rem = (unsigned)(nblk % grid);
-      const float levels = act_levels(in_width, in_flags);
-      const int lo_neg = (in_flags & kFlagRangeRecord) ? kRangeMode : ((in_flags & FQ_ACT_LO_NEG_MAX) ? 1 : 0);
-      const float eps = (in_flags & FQ_ACT_NO_EPS) ? 0.0f : kEps;
-      const int64_t ho = (h - 1) / stride + 1, wo = (wdt - 1) / stride + 1;
-      if (stat_out && !prezeroed) FQ_HIP(hipMemsetAsync(stat_out, 0, n * sizeof(float), st));
-      ProfScope prof(FQ_KERNEL_DWCONV, 4.0 * ((double)n * c * h * wdt + (double)n * c * ho * wo), st);
-#define FQ_DWF_E(SS, HH, Q, O, E)                                                                                 \
-  hipLaunchKernelGGL((dwconv3x3_flat_kernel<SS, Q, O, HH, HH, E>), dim3(grid), dim3(kBlock), 0, st, x, w, bias, y, \
-                     fg, in_stat, (int)n, in_thr, levels, lo_neg, eps, out_current_max, bn_scale, bn_shift, act,  \
-                     stat_out)
-#define FQ_DWF(SS, HH, Q, O)                                                                                      \
-  do {                                                                                                            \
-    if (epi == kEpiBnRelu) FQ_DWF_E(SS, HH, Q, O, kEpiBnRelu);                                                    \
-    else if (epi == kEpiBnRelu6) FQ_DWF_E(SS, HH, Q, O, kEpiBnRelu6);                                             \
-    else FQ_DWF_E(SS, HH, Q, O, kEpiRuntime);                                                                     \
-  } while (0)
-#define FQ_DWF_Q(SS, HH)                                                                                          \
-  do {                                                                                                            \
-    if (!quant) FQ_DWF(SS, HH, false, false);                                                                     \
-    else if (!in_thr) FQ_DWF(SS, HH, true, true);                                                                 \
-    else FQ_DWF(SS, HH, true, false);                                                                             \
-  } while (0)
-      if (kind == 0) FQ_DWF_Q(1, 14);
-      else if (kind == 1) FQ_DWF_Q(2, 14);
-      else if (kind == 2) FQ_DWF_Q(1, 7);
-      else if (kind == 4) FQ_DWF_Q(2, 28);
-      else FQ_DWF_Q(1, 28);
-#undef FQ_DWF_Q
-#undef FQ_DWF
-#undef FQ_DWF_E
-      FQ_LAUNCH_CHECK();
-      return FQ_OK;
-    }
-  }
-  // small planes: whole planes in registers, pipelined across blocks (K2o)
-  static const int planes_on = env_int("FQ_DW_PLANES", 1);
+  const int kind = dw_flat_kind(d);
+  const bool whole = kind == 0 || kind >= 3 || (d.n * d.c) % dw_flat_planes(kind) == 0;     // planes of 49 floats: no 16-byte tail
+  return kind >= 0 && (form == 5 || (form == 0 && ((flat_on >> kind) & 1))) && whole && aligned16(d.x) && aligned16(d.y) &&
+         d.n * d.c * d.h * d.wdt * 4 < (1ll << 31);
+}
+int dw_run_flat(const DwCall& d) {
+  const int kind = dw_flat_kind(d);
+  DwFlatGeom fg;
+  fg.C = (int)d.c;
+  fg.planes = (unsigned)(d.n * d.c);
+  fg.by_c = fast_div_for((unsigned)d.c);
+  const int64_t nblk = dw_blocks(d.n * d.c, dw_flat_planes(kind));
+  static const int fl_tune = env_int("FQ_DW_FLAT_WG_PER_CU", 0);
+  // three workgroups per CU, each with one block in work and one requested: measured best for all three shapes
+  // (512 x 14x14: 2 / 3 / 4 / 6 per CU = 22.2 / 19.6 / 20.7 / 21.9 us; 1024 x 7x7: 16.1 / 14.6 / 17.3 (8) / 16.4 us)
+  const int grid = dw_grid(nblk, fl_tune > 0 ? fl_tune : 3);
+  fg.per = (unsigned)(nblk / grid);
+  fg.rem = (unsigned)(nblk % grid);
+  auto go = [&](auto s, auto hw) {
+    return dw_launch(d, grid, 0, [](auto q, auto o, auto e) {
+      return dwconv3x3_flat_kernel<decltype(s)::value, q(), o(), decltype(hw)::value, decltype(hw)::value, e()>;
+    }, fg);
+  };
+  return kind == 0 ? go(dw_int<1>{}, dw_int<14>{}) : kind == 1 ? go(dw_int<2>{}, dw_int<14>{})
+         : kind == 2 ? go(dw_int<1>{}, dw_int<7>{}) : kind == 4 ? go(dw_int<2>{}, dw_int<28>{})
+                     : go(dw_int<1>{}, dw_int<28>{});
+}
+
+// ---- K2o, planes: small planes whole in registers, pipelined across blocks ------------------------------------------------
+bool dw_planes_two_cols(const DwCall& d) {
   static const int planes_cpl = env_int("FQ_DW_PLANES_CPL", 2);          // 1: one column per lane even where W is even (A/B)
-  const int64_t ho_ = (h - 1) / stride + 1, wo_ = (wdt - 1) / stride + 1;
-  const bool al8 = ((((uintptr_t)x) | ((uintptr_t)y)) & 7) == 0;
-  const bool two_cols = wdt % 2 == 0 && al8 && (stride == 2 || planes_cpl == 2);
-  const bool can_planes = (h == 14 || h == 7) && wdt <= 64 && (stride == 1 || (two_cols && h == 14)) &&
-                          n * c * h * wdt * 4 < (1ll << 31);
-  if ((form == 4 || (form == 0 && planes_on)) && can_planes) {
-    DwColGeom cg = {};
-    cg.C = (int)c;
-    cg.H = (int)h;
-    cg.W = (int)wdt;
-    cg.Ho = (int)ho_;
-    cg.Wo = (int)wo_;
-    cg.nsegx = 1;
-    cg.sw = cg.Wo;
-    cg.SEG = stride == 2 ? cg.Wo : (two_cols ? cg.W / 2 : cg.W);       // lanes per plane (no halo lanes)
-    cg.segs = 64 / cg.SEG;
-    const int64_t total_segs = n * c;
-    const int64_t segs_per_block = (int64_t)cg.segs * (kBlock / 64);
-    const int64_t nblk = (total_segs + segs_per_block - 1) / segs_per_block;
-    static const int pl_wg_per_cu = env_int("FQ_DW_PLANES_WG_PER_CU", 5);
-    const int grid = (int)(nblk < (int64_t)num_cu() * pl_wg_per_cu ? nblk : (int64_t)num_cu() * pl_wg_per_cu);
-    const float levels = act_levels(in_width, in_flags);
-    const int lo_neg = (in_flags & kFlagRangeRecord) ? kRangeMode : ((in_flags & FQ_ACT_LO_NEG_MAX) ? 1 : 0);
-    const float eps = (in_flags & FQ_ACT_NO_EPS) ? 0.0f : kEps;
-    if (stat_out && !prezeroed) FQ_HIP(hipMemsetAsync(stat_out, 0, n * sizeof(float), st));
-    ProfScope prof(FQ_KERNEL_DWCONV, 4.0 * ((double)n * c * h * wdt + (double)n * c * cg.Ho * cg.Wo), st);
-#define FQ_DWP_E(SS, Q, O, HH, CP, E)                                                                             \
-  hipLaunchKernelGGL((dwconv3x3_planes_kernel<SS, Q, O, HH, CP, E>), dim3(grid), dim3(kBlock), 0, st, x, w, bias,  \
-                     y, cg, total_segs, in_stat, (int)n, in_thr, levels, lo_neg, eps, out_current_max, bn_scale,  \
-                     bn_shift, act, stat_out)
-#define FQ_DWP(SS, Q, O, HH, CP)                                                                                  \
-  do {                                                                                                            \
-    if (epi == kEpiBnRelu) FQ_DWP_E(SS, Q, O, HH, CP, kEpiBnRelu);                                                \
-    else if (epi == kEpiBnRelu6) FQ_DWP_E(SS, Q, O, HH, CP, kEpiBnRelu6);                                         \
-    else FQ_DWP_E(SS, Q, O, HH, CP, kEpiRuntime);                                                                 \
-  } while (0)
-#define FQ_DWP_Q(SS, HH, CP)                                                                                      \
-  do {                                                                                                            \
-    if (!quant) FQ_DWP(SS, false, false, HH, CP);                                                                 \
-    else if (!in_thr) FQ_DWP(SS, true, true, HH, CP);                                                             \
-    else FQ_DWP(SS, true, false, HH, CP);                                                                         \
-  } while (0)
-    if (stride == 2) FQ_DWP_Q(2, 14, 2);
-    else if (h == 14 && two_cols) FQ_DWP_Q(1, 14, 2);
-    else if (h == 14) FQ_DWP_Q(1, 14, 1);
-    else if (two_cols) FQ_DWP_Q(1, 7, 2);
-    else FQ_DWP_Q(1, 7, 1);
-#undef FQ_DWP_Q
-#undef FQ_DWP
-#undef FQ_DWP_E
-    FQ_LAUNCH_CHECK();
-    return FQ_OK;
-  }
-  if ((form == 3 || form == 0) && can4) {
-    DwColGeom cg = {};
-    cg.C = (int)c;
-    cg.H = (int)h;
-    cg.W = (int)wdt;
-    cg.Ho = (int)((h - 1) / stride + 1);
-    cg.Wo = (int)((wdt - 1) / stride + 1);
-    const int halo = stride == 1 ? 2 : 1;
-    const int quads = (int)(wdt / 4);                    // compute lanes per full row
-    const int max_sw = 64 - halo;
-    cg.nsegx = (quads + max_sw - 1) / max_sw;
-    cg.sw = (quads + cg.nsegx - 1) / cg.nsegx;           // compute lanes per segment
-    cg.SEG = cg.sw + halo;
-    cg.segs = 64 / cg.SEG;
-    const int64_t total_segs = n * c * cg.nsegx;
-    const int64_t segs_per_block = (int64_t)cg.segs * (kBlock / 64);
-    const int64_t nblk = (total_segs + segs_per_block - 1) / segs_per_block;
-    FQ_REQUIRE(total_segs < (1ll << 31) - 1024, "fq_dwconv3x3: tensor too large for 32-bit segment indices");
-    // every workgroup resident at once, each walking a contiguous range of blocks.  6 per CU: the kernels use ~100 scalar
-    // registers, and a CU admits 256-thread workgroups 8 at a time only up to 80 (MI355X_MICROARCH.md, residency) - with
-    // 8 per CU asked for, a quarter of the grid ran as a second, thin round (14x14 layers: 31.7 -> 28.0 us; capping the
-    // scalar registers at 80 instead makes all 8 resident and is no faster)
-    static const int dw_wg_per_cu = env_int("FQ_DW_WG_PER_CU", 6);
-    const int grid = (int)(nblk < (int64_t)num_cu() * dw_wg_per_cu ? nblk : (int64_t)num_cu() * dw_wg_per_cu);
-    const float levels = act_levels(in_width, in_flags);
-    const int lo_neg = (in_flags & kFlagRangeRecord) ? kRangeMode : ((in_flags & FQ_ACT_LO_NEG_MAX) ? 1 : 0);
-    const float eps = (in_flags & FQ_ACT_NO_EPS) ? 0.0f : kEps;
-    if (stat_out && !prezeroed) FQ_HIP(hipMemsetAsync(stat_out, 0, n * sizeof(float), st));
-    ProfScope prof(FQ_KERNEL_DWCONV, 4.0 * ((double)n * c * h * wdt + (double)n * c * cg.Ho * cg.Wo), st);
-    // nontemporal loads above this many MB of input (300 through round 4 = the 411 MB tensor only; 200 takes in the three
-    // 205 MB ones: +0.4 ... +0.7 % images/s in two alternating A/Bs, 100 +0.3 %, 500 -0.5 %: profiles/r5_heuristics_ab.txt)
-    static const int dw_nt_mb = env_int("FQ_DW_NT_MB", 200);
-    const bool nt = 4.0 * (double)n * c * h * wdt > 1e6 * dw_nt_mb;
-    static const int dw_nts_mb = env_int("FQ_DW_NTS_MB", 1 << 30);        // nontemporal stores from this many MB of output on
-    cg.nts = 4.0 * (double)n * c * cg.Ho * cg.Wo >= 1e6 * dw_nts_mb ? 1 : 0;
-#define FQ_DWC4_E(SS, Q, O, NT_, E)                                                                               \
-  hipLaunchKernelGGL((dwconv3x3_cols4_kernel<SS, Q, O, NT_, E>), dim3(grid), dim3(kBlock), 0, st, x, w, bias, y,  \
-                     cg, total_segs, in_stat, (int)n, in_thr, levels, lo_neg, eps, out_current_max, bn_scale,     \
-                     bn_shift, act, stat_out)
-#define FQ_DWC4_N(SS, Q, O, NT_)                                                                                  \
-  do {                                                                                                            \
-    if (epi == kEpiBnRelu) FQ_DWC4_E(SS, Q, O, NT_, kEpiBnRelu);                                                  \
-    else if (epi == kEpiBnRelu6) FQ_DWC4_E(SS, Q, O, NT_, kEpiBnRelu6);                                           \
-    else FQ_DWC4_E(SS, Q, O, NT_, kEpiRuntime);                                                                   \
-  } while (0)
-#define FQ_DWC4(SS, Q, O)                                                                                         \
-  do {                                                                                                            \
-    if (nt) FQ_DWC4_N(SS, Q, O, true);                                                                            \
-    else FQ_DWC4_N(SS, Q, O, false);                                                                              \
-  } while (0)
-    if (stride == 1) {
-      if (!quant) FQ_DWC4(1, false, false);
-      else if (!in_thr) FQ_DWC4(1, true, true);
-      else FQ_DWC4(1, true, false);
-    } else {
-      if (!quant) FQ_DWC4(2, false, false);
-      else if (!in_thr) FQ_DWC4(2, true, true);
-      else FQ_DWC4(2, true, false);
-    }
-#undef FQ_DWC4
-#undef FQ_DWC4_N
-#undef FQ_DWC4_E
-    FQ_LAUNCH_CHECK();
-    return FQ_OK;
-  }
-  if (form == 2 || ((form == 0 || form == 3) && wdt >= 14)) {   // narrow planes (7x7): LDS staging coalesces better
-    DwColGeom cg = {};
-    cg.C = (int)c;
-    cg.H = (int)h;
-    cg.W = (int)wdt;
-    cg.Ho = (int)((h - 1) / stride + 1);
-    cg.Wo = (int)((wdt - 1) / stride + 1);
-    const int halo = stride == 1 ? 2 : 1;
-    const int max_sw = 64 - halo;
-    cg.nts = 0;
-    cg.nsegx = (cg.Wo + max_sw - 1) / max_sw;
-    cg.sw = (cg.Wo + cg.nsegx - 1) / cg.nsegx;
-    cg.SEG = cg.sw + halo;
-    cg.segs = 64 / cg.SEG;
-    const int64_t total_segs = n * c * cg.nsegx;
-    const int64_t segs_per_block = (int64_t)cg.segs * (kBlock / 64);
-    const int64_t nblk = (total_segs + segs_per_block - 1) / segs_per_block;
-    FQ_REQUIRE(total_segs < (1ll << 31) - 1024, "fq_dwconv3x3: tensor too large for 32-bit segment indices");
-    // every workgroup resident at once, each walking a contiguous range of blocks.  6 per CU: the kernels use ~100 scalar
-    // registers, and a CU admits 256-thread workgroups 8 at a time only up to 80 (MI355X_MICROARCH.md, residency) - with
-    // 8 per CU asked for, a quarter of the grid ran as a second, thin round (14x14 layers: 31.7 -> 28.0 us; capping the
-    // scalar registers at 80 instead makes all 8 resident and is no faster)
-    static const int dw_wg_per_cu = env_int("FQ_DW_WG_PER_CU", 6);
-    const int grid = (int)(nblk < (int64_t)num_cu() * dw_wg_per_cu ? nblk : (int64_t)num_cu() * dw_wg_per_cu);
-    const float levels = act_levels(in_width, in_flags);
-    const int lo_neg = (in_flags & kFlagRangeRecord) ? kRangeMode : ((in_flags & FQ_ACT_LO_NEG_MAX) ? 1 : 0);
-    const float eps = (in_flags & FQ_ACT_NO_EPS) ? 0.0f : kEps;
-    if (stat_out && !prezeroed) FQ_HIP(hipMemsetAsync(stat_out, 0, n * sizeof(float), st));
-    ProfScope prof(FQ_KERNEL_DWCONV, 4.0 * ((double)n * c * h * wdt + (double)n * c * cg.Ho * cg.Wo), st);
-#define FQ_DWC_E(SS, Q, O, E)                                                                                     \
-  hipLaunchKernelGGL((dwconv3x3_cols_kernel<SS, Q, O, E>), dim3(grid), dim3(kBlock), 0, st, x, w, bias, y, cg,     \
-                     total_segs, in_stat, (int)n, in_thr, levels, lo_neg, eps, out_current_max, bn_scale,         \
-                     bn_shift, act, stat_out)
-#define FQ_DWC(SS, Q, O)                                                                                          \
-  do {                                                                                                            \
-    if (epi == kEpiBnRelu) FQ_DWC_E(SS, Q, O, kEpiBnRelu);                                                        \
-    else if (epi == kEpiBnRelu6) FQ_DWC_E(SS, Q, O, kEpiBnRelu6);                                                 \
-    else FQ_DWC_E(SS, Q, O, kEpiRuntime);                                                                         \
-  } while (0)
-    if (stride == 1) {
-      if (!quant) FQ_DWC(1, false, false);
-      else if (!in_thr) FQ_DWC(1, true, true);
-      else FQ_DWC(1, true, false);
-    } else {
-      if (!quant) FQ_DWC(2, false, false);
-      else if (!in_thr) FQ_DWC(2, true, true);
-      else FQ_DWC(2, true, false);
-    }
-#undef FQ_DWC
-#undef FQ_DWC_E
-    FQ_LAUNCH_CHECK();
-    return FQ_OK;
-  }
+  const bool al8 = ((((uintptr_t)d.x) | ((uintptr_t)d.y)) & 7) == 0;
+  return d.wdt % 2 == 0 && al8 && (d.stride == 2 || planes_cpl == 2);
+}
+bool dw_planes_applies(const DwCall& d, int form) {
+  static const int planes_on = env_int("FQ_DW_PLANES", 1);
+  const bool can_planes = (d.h == 14 || d.h == 7) && d.wdt <= 64 && (d.stride == 1 || (dw_planes_two_cols(d) && d.h == 14)) &&
+                          d.n * d.c * d.h * d.wdt * 4 < (1ll << 31);
+  return (form == 4 || (form == 0 && planes_on)) && can_planes;
+}
+int dw_run_planes(const DwCall& d) {
+  const bool two_cols = dw_planes_two_cols(d);
+  // lanes per plane (no halo lanes): one segment per plane
+  DwColGeom cg = dw_col_geom(d, (int)(d.stride == 2 ? d.wo : (two_cols ? d.wdt / 2 : d.wdt)), 0);
+  cg.sw = cg.Wo;                                          // (output columns, as the other forms have it: two per lane with two_cols)
+  const int64_t total_segs = d.n * d.c;
+  static const int pl_wg_per_cu = env_int("FQ_DW_PLANES_WG_PER_CU", 5);
+  const int grid = dw_grid(dw_blocks(total_segs, cg.segs), pl_wg_per_cu);
+  auto go = [&](auto s, auto h, auto cpl) {
+    return dw_launch(d, grid, 0, [](auto q, auto o, auto e) {
+      return dwconv3x3_planes_kernel<decltype(s)::value, q(), o(), decltype(h)::value, decltype(cpl)::value, e()>;
+    }, cg, total_segs);
+  };
+  if (d.stride == 2) return go(dw_int<2>{}, dw_int<14>{}, dw_int<2>{});
+  if (d.h == 14) return two_cols ? go(dw_int<1>{}, dw_int<14>{}, dw_int<2>{}) : go(dw_int<1>{}, dw_int<14>{}, dw_int<1>{});
+  return two_cols ? go(dw_int<1>{}, dw_int<7>{}, dw_int<2>{}) : go(dw_int<1>{}, dw_int<7>{}, dw_int<1>{});
+}
+
+// ---- K2e / K2d, cols4 and cols: the sliding window with four columns / one column per lane ------------------------------------
+// Both: every workgroup resident at once, each walking a contiguous range of blocks.  6 per CU: the kernels use ~100 scalar
+// registers, and a CU admits 256-thread workgroups 8 at a time only up to 80 (MI355X_MICROARCH.md, residency) - with
+// 8 per CU asked for, a quarter of the grid ran as a second, thin round (14x14 layers: 31.7 -> 28.0 us; capping the
+// scalar registers at 80 instead makes all 8 resident and is no faster)
+int dw_cols_grid(int64_t total_segs, const DwColGeom& cg) {
+  static const int dw_wg_per_cu = env_int("FQ_DW_WG_PER_CU", 6);
+  return dw_grid(dw_blocks(total_segs, cg.segs), dw_wg_per_cu);
+}
+bool dw_cols4_applies(const DwCall& d, int form) {
+  const bool can4 = (d.wdt % 4 == 0) && aligned16(d.x) && aligned16(d.y) && ((d.h * d.wdt) % 4 == 0) &&
+                    (d.stride == 1 || ((d.wdt / 2) % 2 == 0));
+  return (form == 3 || form == 0) && can4;
+}
+int dw_run_cols4(const DwCall& d) {
+  DwColGeom cg = dw_col_geom(d, (int)(d.wdt / 4), d.stride == 1 ? 2 : 1);      // compute lanes per full row: quads
+  const int64_t total_segs = d.n * d.c * cg.nsegx;
+  FQ_REQUIRE(total_segs < (1ll << 31) - 1024, "fq_dwconv3x3: tensor too large for 32-bit segment indices");
+  const int grid = dw_cols_grid(total_segs, cg);
+  // nontemporal loads above this many MB of input (300 through round 4 = the 411 MB tensor only; 200 takes in the three
+  // 205 MB ones: +0.4 ... +0.7 % images/s in two alternating A/Bs, 100 +0.3 %, 500 -0.5 %: profiles/r5_heuristics_ab.txt)
+  static const int dw_nt_mb = env_int("FQ_DW_NT_MB", 200);
+  const bool nt = 4.0 * (double)d.n * d.c * d.h * d.wdt > 1e6 * dw_nt_mb;
+  static const int dw_nts_mb = env_int("FQ_DW_NTS_MB", 1 << 30);        // nontemporal stores from this many MB of output on
+  cg.nts = 4.0 * (double)d.n * d.c * cg.Ho * cg.Wo >= 1e6 * dw_nts_mb ? 1 : 0;
+  auto go = [&](auto s, auto nt_c) {
+    return dw_launch(d, grid, 0, [](auto q, auto o, auto e) {
+      return dwconv3x3_cols4_kernel<decltype(s)::value, q(), o(), decltype(nt_c)::value, e()>;
+    }, cg, total_segs);
+  };
+  if (d.stride == 1) return nt ? go(dw_int<1>{}, std::true_type{}) : go(dw_int<1>{}, std::false_type{});
+  return nt ? go(dw_int<2>{}, std::true_type{}) : go(dw_int<2>{}, std::false_type{});
+}
+bool dw_cols_applies(const DwCall& d, int form) {      // narrow planes (7x7): LDS staging coalesces better
+  return form == 2 || ((form == 0 || form == 3) && d.wdt >= 14);
+}
+int dw_run_cols(const DwCall& d) {
+  const DwColGeom cg = dw_col_geom(d, (int)d.wo, d.stride == 1 ? 2 : 1);
+  const int64_t total_segs = d.n * d.c * cg.nsegx;
+  FQ_REQUIRE(total_segs < (1ll << 31) - 1024, "fq_dwconv3x3: tensor too large for 32-bit segment indices");
+  const int grid = dw_cols_grid(total_segs, cg);
+  auto go = [&](auto s) {
+    return dw_launch(d, grid, 0, [](auto q, auto o, auto e) {
+      return dwconv3x3_cols_kernel<decltype(s)::value, q(), o(), e()>;
+    }, cg, total_segs);
+  };
+  return d.stride == 1 ? go(dw_int<1>{}) : go(dw_int<2>{});
+}
+
+// ---- K2c, tiles: every shape ---------------------------------------------------------------------------------------------------
+int dw_run_tiles(const DwCall& d) {
+  const int stride = d.stride;
   DwGeom g;
-  g.C = (int)c;
-  g.H = (int)h;
-  g.W = (int)wdt;
-  g.Ho = (int)((h - 1) / stride + 1);
-  g.Wo = (int)((wdt - 1) / stride + 1);
+  g.C = (int)d.c;
+  g.H = (int)d.h;
+  g.W = (int)d.wdt;
+  g.Ho = (int)d.ho;
+  g.Wo = (int)d.wo;
   g.WS = g.W + 2;
   if ((g.WS & 1) == 0) g.WS += 1;                       // odd dword stride
   const int lds_budget = 8192;                          // floats (32 KiB) -> up to 5 workgroups per CU
@@ -1495,8 +1313,8 @@ static int dwconv3x3_impl(const float* x, const float* w, const float* bias, flo
     g.strips = 1;
     g.IR = g.H + 2;
     g.P = 1;
-    for (int p = (int)(c < 64 ? c : 64); p >= 1; --p)
-      if (c % p == 0 && p * g.IR * g.WS <= lds_budget) {
+    for (int p = (int)(d.c < 64 ? d.c : 64); p >= 1; --p)
+      if (d.c % p == 0 && p * g.IR * g.WS <= lds_budget) {
         g.P = p;
         break;
       }
@@ -1516,35 +1334,65 @@ static int dwconv3x3_impl(const float* x, const float* w, const float* bias, flo
     g.RS = (g.TR + nseg - 1) / nseg;
     g.nseg = (g.TR + g.RS - 1) / g.RS;
   }
-  const bool base_ok = aligned16(x);
+  const bool base_ok = aligned16(d.x);
   if (g.P > 1 || g.strips == 1)
     g.vec_in = base_ok && (((int64_t)g.P * plane_in) % 4 == 0) && (plane_in % 4 == 0 || g.P % 4 == 0);
   else
     g.vec_in = base_ok && (g.W % 4 == 0) && (plane_in % 4 == 0);
-  const int64_t tiles = (n * c / g.P) * g.strips;
-  size_t lds = (size_t)((g.P * g.IR * g.WS + 3) / 4 * 4 + 16) * sizeof(float);
-  const int grid = grid_for(tiles);
-  const float levels = act_levels(in_width, in_flags);
-  const int lo_neg = (in_flags & kFlagRangeRecord) ? kRangeMode : ((in_flags & FQ_ACT_LO_NEG_MAX) ? 1 : 0);
-  const float eps = (in_flags & FQ_ACT_NO_EPS) ? 0.0f : kEps;
-  if (stat_out && !prezeroed) FQ_HIP(hipMemsetAsync(stat_out, 0, n * sizeof(float), st));
-  ProfScope prof(FQ_KERNEL_DWCONV, 4.0 * ((double)n * c * h * wdt + (double)n * c * g.Ho * g.Wo), st);
-#define FQ_DW(SS, Q, O)                                                                                           \
-  hipLaunchKernelGGL((dwconv3x3_kernel<SS, Q, O>), dim3(grid), dim3(kBlock), lds, st, x, w, bias, y, g, tiles,    \
-                     in_stat, (int)n, in_thr, levels, lo_neg, eps, out_current_max, bn_scale, bn_shift, act,      \
-                     stat_out)
-  if (stride == 1) {
-    if (!quant) FQ_DW(1, false, false);
-    else if (!in_thr) FQ_DW(1, true, true);
-    else FQ_DW(1, true, false);
-  } else {
-    if (!quant) FQ_DW(2, false, false);
-    else if (!in_thr) FQ_DW(2, true, true);
-    else FQ_DW(2, true, false);
-  }
-#undef FQ_DW
-  FQ_LAUNCH_CHECK();
-  return FQ_OK;
+  const int64_t tiles = (d.n * d.c / g.P) * g.strips;
+  const size_t lds = (size_t)((g.P * g.IR * g.WS + 3) / 4 * 4 + 16) * sizeof(float);
+  auto go = [&](auto s) {       // (this form has the run-time epilogue only)
+    return dw_launch(d, grid_for(tiles), lds, [](auto q, auto o, auto) {
+      return dwconv3x3_kernel<decltype(s)::value, q(), o()>;
+    }, g, tiles);
+  };
+  return stride == 1 ? go(dw_int<1>{}) : go(dw_int<2>{});
+}
+
+}  // namespace
+
+static int dwconv3x3_impl(const float* x, const float* w, const float* bias, float* y, int64_t n, int64_t c, int64_t h,
+                          int64_t wdt, int stride, const float* in_stat, const float* in_thr, int in_width, unsigned in_flags,
+                          float* out_current_max, const float* bn_scale, const float* bn_shift, int act, float* stat_out,
+                          fqStream_t stream) {
+  FQ_REQUIRE(x && w && y, "fq_dwconv3x3: null pointer");
+  FQ_REQUIRE(n > 0 && c > 0 && h > 0 && wdt > 0 && n * c < (1ll << 31) && h * wdt < (1ll << 28),
+             "fq_dwconv3x3: bad shape (n=%lld c=%lld h=%lld w=%lld)", (long long)n, (long long)c, (long long)h,
+             (long long)wdt);
+  FQ_REQUIRE(stride == 1 || stride == 2, "fq_dwconv3x3: stride must be 1 or 2, got %d", stride);
+  // in_stat alone: online; in_thr alone: offline; both: offline, the statistic only feeds out_current_max
+  FQ_REQUIRE((bn_scale == nullptr) == (bn_shift == nullptr), "fq_dwconv3x3: bn_scale and bn_shift go together");
+  const bool prezeroed = (act & FQ_STAT_PREZEROED) != 0;
+  act &= ~FQ_STAT_PREZEROED;
+  FQ_REQUIRE(act >= FQ_ACT_NONE && act <= FQ_ACT_RELU6, "fq_dwconv3x3: unknown activation %d", act);
+  const bool quant = in_stat != nullptr || in_thr != nullptr;
+  if (quant) FQ_REQUIRE(in_width >= 2 && in_width <= 16, "fq_dwconv3x3: width %d out of range", in_width);
+  if (in_flags & kFlagBiasMultiplies) act |= kActBiasMul;   // (after the range check; bias != NULL: run-time epilogue)
+  static const int epi_on = env_int("FQ_DW_EPI", 1);    // 0: always the run-time epilogue (A/B)
+
+  DwCall d = {};
+  d.x = x; d.w = w; d.bias = bias; d.y = y;
+  d.n = n, d.c = c, d.h = h, d.wdt = wdt, d.stride = stride;
+  d.in_stat = in_stat, d.in_thr = in_thr, d.out_current_max = out_current_max;
+  d.bn_scale = bn_scale, d.bn_shift = bn_shift, d.act = act, d.stat_out = stat_out;
+  d.st = (hipStream_t)stream;
+  d.quant = quant, d.online = quant && in_thr == nullptr, d.prezeroed = prezeroed;
+  d.epi = (epi_on && bn_scale != nullptr && bias == nullptr)
+              ? (act == FQ_ACT_RELU ? kEpiBnRelu : act == FQ_ACT_RELU6 ? kEpiBnRelu6 : kEpiRuntime)
+              : kEpiRuntime;
+  d.levels = act_levels(in_width, in_flags);
+  d.lo_neg = (in_flags & kFlagRangeRecord) ? kRangeMode : ((in_flags & FQ_ACT_LO_NEG_MAX) ? 1 : 0);
+  d.eps = (in_flags & FQ_ACT_NO_EPS) ? 0.0f : kEps;
+  d.ho = (h - 1) / stride + 1, d.wo = (wdt - 1) / stride + 1;
+
+  // 0 auto, 1 LDS tiles, 2 one column per lane, 3 four columns per lane, 4 whole planes, 5 flat.  A forced form that does
+  // not take the shape falls through to the next one that does.
+  static const int form = env_int("FQ_DW_FORM", 0);
+  if (dw_flat_applies(d, form)) return dw_run_flat(d);
+  if (dw_planes_applies(d, form)) return dw_run_planes(d);
+  if (dw_cols4_applies(d, form)) return dw_run_cols4(d);
+  if (dw_cols_applies(d, form)) return dw_run_cols(d);
+  return dw_run_tiles(d);
 }
 
 namespace fqi {
