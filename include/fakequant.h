@@ -407,12 +407,20 @@ int fq_pwconv_i8_gap(const float* x, const int8_t* wcodes, const float* wscale, 
  * Shapes: fq_pwdw_fused_supported - cin in (0, 256] with ceil(cin / 32) in {1, 2, 4, 8}, cout % 32 == 0 (at most 8 wavefronts:
  * ceil(w / 30) * cout / 64 <= 8), w % 4 == 0, w >= 30 or w == 28; stride 2 needs even h and w % 8 == 0.  x: (n, cin, h, w);
  * z: (n, cout, ho, wo).  wcodes: fq_weight_codes' buffer (both copies), cout_pad its rows_pad.  dw_act may carry
- * FQ_STAT_PREZEROED.                                                                                                      */
+ * FQ_STAT_PREZEROED.
+ * Handing the codes of x from (A) to (B).  Both launches quantise the same x with the same threshold, and (B) needs one byte
+ * per element where it reads four.  fq_pwconv_i8_stat(x_codes_out != NULL) also stores the codes it multiplies with, as a C16
+ * code tensor (below: byte = (code + 128 - zoff) ^ 0x80) of WHOLE 32-channel slabs: int8 [n][2 * ceil(cin / 32)][h * w][16],
+ * channels past cin hold the code of 0; n * 2 * ceil(cin / 32) * h * w * 16 bytes, 16-byte aligned.  fq_pwdw_fused(x_codes !=
+ * NULL) reads that buffer INSTEAD of x (x may then be NULL and is never dereferenced) and quantises nothing on its input side;
+ * every value it produces is the one it produces from x.  Contract: x_codes is what fq_pwconv_i8_stat wrote for the same x,
+ * in_stat / in_thr, in_width and in_flags - the launch cannot check it.  NULL on either side: behave as without it.         */
 int fq_pwconv_i8_stat_supported(int64_t n, int64_t cin, int64_t cout, int64_t hw);
 int fq_pwconv_i8_stat(const float* x, const int8_t* wcodes, const float* wscale, const int32_t* wsum, const float* bias,
                       int64_t n, int64_t cin, int64_t cin_pad, int64_t cout_pad, int64_t cout, int64_t hw,
                       const float* in_stat, const float* in_thr, int in_width, unsigned in_flags, float* out_current_max,
-                      const float* bn_scale, const float* bn_shift, int act, float* stat_out, fqStream_t stream);
+                      const float* bn_scale, const float* bn_shift, int act, float* stat_out, void* x_codes_out,
+                      fqStream_t stream);
 int fq_pwdw_fused_supported(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w, int stride);
 /* Test hook: out[i] <- the fp32 quotient c[i] / d[0] as the two kernels above compute it (the fp32 correction step of
  * csrc/fq_common.h: fast_quot, or the fp64-reciprocal form when d[0] does not qualify; took_fast_path[0] says which) - must
@@ -424,7 +432,7 @@ int fq_pwdw_fused(const float* x, const int8_t* wcodes, const float* wscale, con
                   const float* pw_bn_shift, int pw_act, const float* mid_stat, const float* mid_thr, int mid_width,
                   unsigned mid_flags, float* mid_current_max, const float* dw_w, const float* dw_bias, int dw_stride,
                   const float* dw_bn_scale, const float* dw_bn_shift, int dw_act, float* y, float* stat_out,
-                  fqStream_t stream);
+                  const void* x_codes, fqStream_t stream);
 
 /* ---- int8 hand-over between fused convolutions under OFFLINE input quantisation (round 3) ------------------------------
  * When the consumer quantises its input with a STORED threshold (`--quantize-input-offline`: convert_conv2d.py:58 takes

@@ -50,6 +50,8 @@ struct PwCall {
   const long long* eval_labels = nullptr;
   float* eval_counters = nullptr;
   void* eval_ws = nullptr;
+  // fq_pwconv_i8_stat: where the statistic pass leaves the codes of x for fq_pwdw_fused ([n][2 ceil(cin / 32)][hw][16] bytes)
+  void* x_codes_out = nullptr;
 };
 
 // K2z  fq_pwdw.hip: the statistic-only pass (fq_pwconv_i8_stat): stat_out and out_current_max only, c.y is not touched

@@ -245,7 +245,8 @@ int fq_pwconv_i8_stat_supported(int64_t n, int64_t cin, int64_t cout, int64_t hw
 int fq_pwconv_i8_stat(const float* x, const int8_t* wcodes, const float* wscale, const int32_t* wsum, const float* bias,
                       int64_t n, int64_t cin, int64_t cin_pad, int64_t cout_pad, int64_t cout, int64_t hw,
                       const float* in_stat, const float* in_thr, int in_width, unsigned in_flags, float* out_current_max,
-                      const float* bn_scale, const float* bn_shift, int act, float* stat_out, fqStream_t stream) {
+                      const float* bn_scale, const float* bn_shift, int act, float* stat_out, void* x_codes_out,
+                      fqStream_t stream) {
   FQ_REQUIRE(x && wcodes && wscale && wsum && stat_out, "fq_pwconv_i8_stat: null pointer");
   FQ_REQUIRE(pw_stat_shape_ok(n, cin, cout, hw), "fq_pwconv_i8_stat: shape not taken (n=%lld cin=%lld cout=%lld hw=%lld): see "
              "fq_pwconv_i8_stat_supported", (long long)n, (long long)cin, (long long)cout, (long long)hw);
@@ -259,7 +260,8 @@ int fq_pwconv_i8_stat(const float* x, const int8_t* wcodes, const float* wscale,
   c.prezeroed = (act & FQ_STAT_PREZEROED) != 0;
   act &= ~FQ_STAT_PREZEROED;
   FQ_REQUIRE(act >= FQ_ACT_NONE && act <= FQ_ACT_RELU6, "fq_pwconv_i8_stat: unknown activation %d", act);
-  FQ_REQUIRE(aligned16(wcodes) && aligned16(x), "fq_pwconv_i8_stat: x and wcodes must be 16-byte aligned");
+  FQ_REQUIRE(aligned16(wcodes) && aligned16(x) && aligned16(x_codes_out),
+             "fq_pwconv_i8_stat: x, wcodes and x_codes_out must be 16-byte aligned");
   c.x = x; c.wcodes = wcodes + cout_pad * cin_pad; c.wscale = wscale; c.wsum = wsum; c.bias = bias; c.y = nullptr;
   c.n = n; c.cin = cin; c.cin_pad = cin_pad; c.cout = cout; c.hw = hw; c.stride = 1; c.h_in = c.w_in = c.w_out = 0;
   c.in_stat = in_stat; c.in_thr = in_thr;
@@ -268,9 +270,12 @@ int fq_pwconv_i8_stat(const float* x, const int8_t* wcodes, const float* wscale,
   c.zoff = (in_flags & FQ_ACT_SIGNED) ? 0 : 128;
   c.out_current_max = out_current_max; c.bn_scale = bn_scale; c.bn_shift = bn_shift; c.act = act;
   c.stat_out = stat_out; c.residual = nullptr; c.ws = nullptr; c.st = (hipStream_t)stream; c.form = 0;
-  // algorithmic bytes: the pointwise layer's (this launch stands for it); moved: its input only
+  c.x_codes_out = x_codes_out;
+  // algorithmic bytes: the pointwise layer's (this launch stands for it); moved: its input, and the codes of it when they are
+  // kept (whole 32-channel slabs, one byte per element)
   const double in_elems = (double)n * cin * hw, out_elems = (double)n * cout * hw;
-  ProfScope prof(FQ_KERNEL_PWCONV, 4.0 * (in_elems + out_elems), c.st, 4.0 * in_elems);
+  const double code_bytes = x_codes_out ? 32.0 * (double)((cin + 31) / 32) * n * hw : 0.0;
+  ProfScope prof(FQ_KERNEL_PWCONV, 4.0 * (in_elems + out_elems), c.st, 4.0 * in_elems + code_bytes);
   return pw_stat_launch(c);
 }
 

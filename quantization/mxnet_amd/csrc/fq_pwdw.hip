@@ -41,20 +41,27 @@ constexpr int kRowSlack = 8;          // floats in front of each row buffer (a s
 
 // slabs in flight per lane: a ring of NB buffers of 16 values, the loads of slab q + NB - 1 issued before slab q is quantised
 // (stride 1 keeps 32 more partial sums per channel tile: two buffers there)
-template <int KT, int S> struct PwDwRing { static constexpr int NB = S == 1 ? 2 : (KT <= 2 ? 3 : 4); };
+template <int KT, int S> struct PwDwRing {
+  static constexpr int NB = S == 1 ? 2 : (KT <= 2 ? 3 : 4);
+  // code input (CODES below): a slab is ONE 16-byte load per lane, so the ring holds whole rows - KT fragments each, 4 KT
+  // registers - and the loads of row t + NR - 1 leave before row t is multiplied: a row's arithmetic covers their latency
+  static constexpr int NR = 2;
+};
 
 // FAST 0: every epilogue decided at run time, general quantisers; 1: the fused-inference case - no bias, BatchNorm and ReLU
 // (ReLU6 when `relu6`) behind both convolutions, unsigned activations (both clip ranges start at 0)
-template <int KT, int CW, int S, int LZ, int FAST>
+// CODES 1: the input arrives as the codes the statistic pass left behind (`xc`: [n][2 KT][H * W][16] bytes, a lane's A fragment
+// of a pixel and a slab is one 16-byte vector of it) - x is not read, nothing is quantised on the input side
+template <int KT, int CW, int S, int LZ, int FAST, int CODES>
 __global__ __launch_bounds__(512) void pwdw_kernel(
-    const float* __restrict__ x, const int8_t* __restrict__ wfrag, const float* __restrict__ wscale,
+    const float* __restrict__ x, const int8_t* __restrict__ xc, const int8_t* __restrict__ wfrag, const float* __restrict__ wscale,
     const int* __restrict__ wsum, const float* __restrict__ bias1, PwDwGeom g, const float* __restrict__ in_stat, int n,
     const float* __restrict__ in_thr, float levels1, int lo_neg1, float eps, const float* __restrict__ bn1_scale,
     const float* __restrict__ bn1_shift, int act1, const float* __restrict__ mid_stat, const float* __restrict__ mid_thr,
     float levels2, int lo_neg2, float* __restrict__ mid_cur_out, const float* __restrict__ dww,
     const float* __restrict__ bias2, const float* __restrict__ bn2_scale, const float* __restrict__ bn2_shift, int act2,
     float* __restrict__ y, float* __restrict__ stat_out) {
-  constexpr int NB = PwDwRing<KT, S>::NB;
+  constexpr int NB = CODES ? 1 : PwDwRing<KT, S>::NB, NR = CODES ? PwDwRing<KT, S>::NR : 1;
   extern __shared__ __attribute__((aligned(16))) unsigned char pwdw_smem[];
   __shared__ float red[8];
   const int CT = g.ctg * CW;
@@ -86,8 +93,9 @@ __global__ __launch_bounds__(512) void pwdw_kernel(
   const int pl = 16 * ((i32 >> 2) & 1) + 4 * (i32 >> 3) + (i32 & 3);
   int col_ld = c0 + pl - 1;
   col_ld = col_ld < 0 ? 0 : (col_ld >= g.W ? g.W - 1 : col_ld);
-  const fq_rsrc rs = make_rsrc(x + (int64_t)smp * g.Cin * HW, (int64_t)g.Cin * HW * 4);
-  const unsigned voff = (unsigned)((16 * h * HW + col_ld) * 4);
+  const fq_rsrc rs = CODES ? make_rsrc(xc + (int64_t)smp * 2 * KT * HW * 16, (int64_t)2 * KT * HW * 16)
+                           : make_rsrc(x + (int64_t)smp * g.Cin * HW, (int64_t)g.Cin * HW * 4);
+  const unsigned voff = CODES ? (unsigned)((h * HW + col_ld) * 16) : (unsigned)((16 * h * HW + col_ld) * 4);
   // LDS float offset of this lane's output 0 inside a channel row: stride 1 - own pixel k is output column c0 + 16 h + k - 1
   // (k = 0 of the lower half and k = 15 of the upper half are no outputs); stride 2 - output oc = 8 h + c is column 15 s + oc
   // (c = 7 of the upper half is no output).  Columns past the plane fall into the row's padding.
@@ -111,8 +119,25 @@ __global__ __launch_bounds__(512) void pwdw_kernel(
 #pragma unroll
     for (int i = 0; i < 16; ++i) v[i] = buf_ld_f32(rs, voff, so + (unsigned)(i * HW * 4));
   };
+  // code input: row t's fragments, channel block 2 kt + h of this lane's pixel (rows outside the image or past the band are
+  // neither requested nor used, as above)
+  v4i crow[NR][KT];
 #pragma unroll
-  for (int q = 0; q < NB - 1; ++q) issue(t_first + q / KT, q % KT, raw[q]);
+  for (int b = 0; b < NR; ++b)
+#pragma unroll
+    for (int kt = 0; kt < KT; ++kt) crow[b][kt] = (v4i){0, 0, 0, 0};
+  auto issue_row = [&](int t, v4i (&v)[KT]) __attribute__((always_inline)) {
+    if (t < 0 || t >= g.H || t > t_last) return;
+#pragma unroll
+    for (int kt = 0; kt < KT; ++kt) v[kt] = buf_ld_v4i(rs, voff, (unsigned)((2 * kt * HW + t * g.W) * 16));
+  };
+  if constexpr (CODES) {
+#pragma unroll
+    for (int r = 0; r < NR - 1; ++r) issue_row(t_first + r, crow[r]);
+  } else {
+#pragma unroll
+    for (int q = 0; q < NB - 1; ++q) issue(t_first + q / KT, q % KT, raw[q]);
+  }
   FQ_PIN();
 
   // ---- thresholds: the pointwise input's (statistic of x) and the depthwise input's (statistic of the pointwise output) ----
@@ -198,26 +223,31 @@ __global__ __launch_bounds__(512) void pwdw_kernel(
     QParams qc = q2;                               // FAST: ReLU / ReLU6 and the clip as one median (clip range starts at 0)
     if (FAST) qc.hi = fminf(q2.hi, top);
 
-    // one input row; PH: its first slab is slab (PH * KT) mod NB of the ring
+    // one input row; PH: its first slab is slab (PH * KT) mod NB of the ring (code input: the row is row PH mod NR of its ring)
     auto row = [&](int t, auto ph_c) __attribute__((always_inline)) {
       constexpr int PH = decltype(ph_c)::value;
       const bool row_ok = t >= 0 && t < g.H;
       v4i afrag[KT];
-#pragma unroll
-      for (int kt = 0; kt < KT; ++kt) {
-        constexpr int dummy = 0;
-        (void)dummy;
-        const int qn = kt + NB - 1;                                  // the slab NB - 1 ahead goes into the buffer freed last
-        issue(t + qn / KT, qn % KT, raw[(PH * KT + kt + NB - 1) % NB]);
+      if constexpr (CODES) {
+        issue_row(t + NR - 1, crow[(PH + NR - 1) % NR]);             // into the row freed last
         FQ_PIN();
-        float (&mine)[16] = raw[(PH * KT + kt) % NB];
-        v4i f;
 #pragma unroll
-        for (int d = 0; d < 4; ++d)
-          f[d] = pack_x(mine[4 * d + 0], mine[4 * d + 1], mine[4 * d + 2], mine[4 * d + 3]);
-        asm volatile("" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]));
-        afrag[kt] = f;
-        FQ_PIN();
+        for (int kt = 0; kt < KT; ++kt) afrag[kt] = crow[PH % NR][kt];
+      } else {
+#pragma unroll
+        for (int kt = 0; kt < KT; ++kt) {
+          const int qn = kt + NB - 1;                                  // the slab NB - 1 ahead goes into the buffer freed last
+          issue(t + qn / KT, qn % KT, raw[(PH * KT + kt + NB - 1) % NB]);
+          FQ_PIN();
+          float (&mine)[16] = raw[(PH * KT + kt) % NB];
+          v4i f;
+#pragma unroll
+          for (int d = 0; d < 4; ++d)
+            f[d] = pack_x(mine[4 * d + 0], mine[4 * d + 1], mine[4 * d + 2], mine[4 * d + 3]);
+          asm volatile("" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]));
+          afrag[kt] = f;
+          FQ_PIN();
+        }
       }
       const int r_emit = S == 1 ? t - 1 : (t - 1) >> 1;          // output row an odd (S = 2) / any (S = 1) input row closes
       const bool emits = (S == 1 || (t & 1)) && r_emit >= ro0 && r_emit < ro1;
@@ -398,7 +428,8 @@ __global__ __launch_bounds__(512) void pwdw_kernel(
       }
     };
     // rows in groups whose ring phases are static: U rows per turn, U * KT a multiple of NB
-    constexpr int U = (KT % NB == 0) ? 1 : ((2 * KT) % NB == 0 ? 2 : NB);
+    constexpr int U = CODES ? NR : ((KT % NB == 0) ? 1 : ((2 * KT) % NB == 0 ? 2 : NB));
+    static_assert(U <= 3, "the row loop below unrolls at most three phases");
     using std::integral_constant;
     for (int t = t_first; t <= t_last; t += U) {
       row(t, integral_constant<int, 0>{});
@@ -433,6 +464,17 @@ __global__ __launch_bounds__(512) void pwdw_kernel(
 // instruction per output value instead of the storing kernel's six) and runs the fp32 epilogue on those two only, once per
 // sample: bit for bit the statistic of fq_pwconv_i8.  That turns the pass from instruction-bound (3.5 TB/s as the storing
 // kernel without its stores) into a read of x.
+// x_codes_out (optional): the codes of x do exist once this pass has quantised them - lane (i32, h) holds, per slab kt, the 16
+// codes of ITS pixel's channels 32 kt + 16 h .. + 15 as the bytes of an MFMA A fragment, which is a C16 vector (fakequant.h).  The
+// lane stores it at [smp][2 kt + h][p][16]: fq_pwdw_fused's lane of the same pixel and slab loads it back with one instruction
+// instead of sixteen loads and sixteen quantisations.  The 32 lanes of a half write 512 contiguous bytes per instruction; the
+// lanes of a partial last tile, clamped to the last pixel, rewrite that pixel's own bytes.
+__device__ __forceinline__ void buf_st_v4i(fq_rsrc r, unsigned voff, v4i v) {
+  typedef unsigned v4u __attribute__((ext_vector_type(4)));
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, v), r, (int)voff, 0, 0);
+  asm volatile("s_nop 1" : : "v"(v));
+}
+
 struct PwStatGeom {
   int Cin, KTS, Cout, CT, HW;
   int64_t cols, tiles;
@@ -446,7 +488,8 @@ __global__ __launch_bounds__(kBlock, 3) void pw_stat_kernel(
     const float* __restrict__ x, const int8_t* __restrict__ wfrag, const float* __restrict__ wscale,
     const int* __restrict__ wsum, const float* __restrict__ bias, PwStatGeom g, const float* __restrict__ in_stat, int n,
     const float* __restrict__ in_thr, float levels, int lo_neg, float eps, float* __restrict__ cur_max_out,
-    const float* __restrict__ bn_scale, const float* __restrict__ bn_shift, int act, float* __restrict__ stat_out) {
+    const float* __restrict__ bn_scale, const float* __restrict__ bn_shift, int act, float* __restrict__ stat_out,
+    int8_t* __restrict__ x_codes_out) {
   extern __shared__ __attribute__((aligned(16))) unsigned char pst_smem[];
   v4i* ldsW = reinterpret_cast<v4i*>(pst_smem);                                           // [CT][KT][64]
   int* c_zs = reinterpret_cast<int*>(pst_smem + (size_t)g.CT * KT * 1024);                 // [CT * 32]
@@ -506,6 +549,8 @@ __global__ __launch_bounds__(kBlock, 3) void pw_stat_kernel(
   const QParams q = make_qparams(max_, levels, lo_neg != 0, eps);
   const int ubias = 128 - g.zoff;
   const unsigned nn_xor = fq_nonneg_xor(ubias);
+  const bool wr_codes = x_codes_out != nullptr;
+  const fq_rsrc rcodes = make_rsrc(x_codes_out, wr_codes ? (int64_t)(cols / HW) * 2 * KT * HW * 16 : 0);
   for (int idx = threadIdx.x; idx < g.CT * KT * 64; idx += kBlock) {
     const int f = idx >> 6, ct = f / KT, kt = f - ct * KT;
     ldsW[idx] = *reinterpret_cast<const v4i*>(wfrag + (((int64_t)ct * g.KTS + kt) << 10) + ((idx & 63) << 4));
@@ -630,12 +675,17 @@ __global__ __launch_bounds__(kBlock, 3) void pw_stat_kernel(
   unsigned cur = fast_div((unsigned)((t_begin < g.tiles ? t_begin : g.tiles - 1) * 32), g.hw);
   auto run_tile = [&](int64_t t, auto ph_c, auto nn_c) __attribute__((always_inline)) {
     constexpr int PH = decltype(ph_c)::value;                 // the tile's first slab sits in buffer (PH * KT) % NB
+    const Pix px = pix_of(t);
+    const unsigned cvo = ((px.smp * (unsigned)(2 * KT) + (unsigned)h) * HW + px.p) * 16u;
 #pragma unroll
     for (int kt = 0; kt < KT; ++kt) {
       const int qn = kt + NB - 1;
       issue(t + qn / KT, qn % KT, raw[(PH * KT + kt + NB - 1) % NB]);
       FQ_PIN();
       quant(kt, raw[(PH * KT + kt) % NB], nn_c);
+      // (the whole offset in the lane register: with a constant scalar offset the compiler itself keeps the data registers of a
+      // 16-byte store untouched for as long as the store reads them - fq_common.h at buf_st_v4f)
+      if (wr_codes) buf_st_v4i(rcodes, cvo + (unsigned)(2 * kt) * HW * 16u, afrag[kt]);
       FQ_PIN();
     }
     const unsigned j0 = (unsigned)t * 32u, j1 = j0 + 31u < cols ? j0 + 31u : cols - 1;
@@ -778,7 +828,7 @@ int pw_stat_launch(const PwCall& c) {
     FQ_REQUIRE(attr_ok, "fq_pwconv_i8_stat: cannot raise the dynamic LDS limit");                                          \
     hipLaunchKernelGGL((pw_stat_kernel<KT_>), dim3((unsigned)grid), dim3(kBlock), lds, c.st, c.x, c.wcodes, c.wscale,       \
                        (const int*)c.wsum, c.bias, g, c.in_stat, (int)c.n, c.in_thr, c.levels, c.lo_neg, kEps,              \
-                       c.out_current_max, c.bn_scale, c.bn_shift, c.act, c.stat_out);                                      \
+                       c.out_current_max, c.bn_scale, c.bn_shift, c.act, c.stat_out, (int8_t*)c.x_codes_out);              \
   } break;
   switch (kt) {
     FQ_PST_GO(1) FQ_PST_GO(2) FQ_PST_GO(4) FQ_PST_GO(8)
@@ -813,8 +863,8 @@ int fq_pwdw_fused(const float* x, const int8_t* wcodes, const float* wscale, con
                   const float* pw_bn_shift, int pw_act, const float* mid_stat, const float* mid_thr, int mid_width,
                   unsigned mid_flags, float* mid_current_max, const float* dw_w, const float* dw_bias, int dw_stride,
                   const float* dw_bn_scale, const float* dw_bn_shift, int dw_act, float* y, float* stat_out,
-                  fqStream_t stream) {
-  FQ_REQUIRE(x && wcodes && wscale && wsum && dw_w && y, "fq_pwdw_fused: null pointer");
+                  const void* x_codes, fqStream_t stream) {
+  FQ_REQUIRE((x || x_codes) && wcodes && wscale && wsum && dw_w && y, "fq_pwdw_fused: null pointer");
   FQ_REQUIRE(in_stat != nullptr || in_thr != nullptr, "fq_pwdw_fused: give in_stat (online) or in_thr (offline)");
   FQ_REQUIRE(mid_stat != nullptr || mid_thr != nullptr, "fq_pwdw_fused: give mid_stat (the per-sample maxima of the pointwise "
              "output, from fq_pwconv_i8_stat) or mid_thr (a stored threshold)");
@@ -829,7 +879,8 @@ int fq_pwdw_fused(const float* x, const int8_t* wcodes, const float* wscale, con
   dw_act &= ~FQ_STAT_PREZEROED;
   FQ_REQUIRE(pw_act >= FQ_ACT_NONE && pw_act <= FQ_ACT_RELU6 && dw_act >= FQ_ACT_NONE && dw_act <= FQ_ACT_RELU6,
              "fq_pwdw_fused: unknown activation");
-  FQ_REQUIRE(aligned16(wcodes) && aligned16(x) && aligned16(y), "fq_pwdw_fused: x, wcodes and y must be 16-byte aligned");
+  FQ_REQUIRE(aligned16(wcodes) && (x_codes ? aligned16(x_codes) : aligned16(x)) && aligned16(y),
+             "fq_pwdw_fused: x (x_codes when given), wcodes and y must be 16-byte aligned");
   const PwDwPlan p = pwdw_plan(n, cin, cout, h, w, dw_stride);
   FQ_REQUIRE(p.ok, "fq_pwdw_fused: shape not taken (n=%lld cin=%lld cout=%lld %lldx%lld stride %d): see fq_pwdw_fused_supported",
              (long long)n, (long long)cin, (long long)cout, (long long)h, (long long)w, dw_stride);
@@ -856,21 +907,28 @@ int fq_pwdw_fused(const float* x, const int8_t* wcodes, const float* wscale, con
   // algorithmic bytes: those of the depthwise layer this launch stands for (its input is never written: SURVEY.md 8d counts
   // what the layer's arithmetic needs); moved: what the launch really reads and writes
   const double in_elems = (double)n * cin * h * w, mid_elems = (double)n * cout * h * w, out_elems = (double)n * cout * ho * wo;
-  ProfScope prof(FQ_KERNEL_DWCONV, 4.0 * (mid_elems + out_elems), st, 4.0 * (in_elems + out_elems));
+  // (code input: 16 bytes per pixel and 16-channel block of whole 32-channel slabs instead of 4 per element)
+  const double in_moved = x_codes ? 32.0 * p.kt * (double)n * h * w : 4.0 * in_elems;
+  ProfScope prof(FQ_KERNEL_DWCONV, 4.0 * (mid_elems + out_elems), st, in_moved + 4.0 * out_elems);
+  const int8_t* xc = static_cast<const int8_t*>(x_codes);
   const unsigned grid = (unsigned)(n * p.bands);
-#define FQ_PWDW_GO(KT_, CW_, S_, LZ_, F_)                                                                                   \
+#define FQ_PWDW_GO(KT_, CW_, S_, LZ_, F_, C_)                                                                               \
   {                                                                                                                        \
-    static const bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&pwdw_kernel<KT_, CW_, S_, LZ_, F_>),    \
+    static const bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&pwdw_kernel<KT_, CW_, S_, LZ_, F_, C_>), \
                                                     hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) == hipSuccess; \
     FQ_REQUIRE(attr_ok, "fq_pwdw_fused: cannot raise the dynamic LDS limit");                                              \
-    hipLaunchKernelGGL((pwdw_kernel<KT_, CW_, S_, LZ_, F_>), dim3(grid), dim3((unsigned)p.threads), p.lds, st, x, wfrag,    \
-                       wscale, (const int*)wsum, pw_bias, g, in_stat, (int)n, in_thr, levels1, lo1, kEps, pw_bn_scale,      \
-                       pw_bn_shift, pw_act, mid_stat, mid_thr, levels2, lo2, mid_current_max, dw_w, dw_bias, dw_bn_scale,   \
-                       dw_bn_shift, dw_act, y, stat_out);                                                                  \
+    hipLaunchKernelGGL((pwdw_kernel<KT_, CW_, S_, LZ_, F_, C_>), dim3(grid), dim3((unsigned)p.threads), p.lds, st, x, xc,   \
+                       wfrag, wscale, (const int*)wsum, pw_bias, g, in_stat, (int)n, in_thr, levels1, lo1, kEps,            \
+                       pw_bn_scale, pw_bn_shift, pw_act, mid_stat, mid_thr, levels2, lo2, mid_current_max, dw_w, dw_bias,   \
+                       dw_bn_scale, dw_bn_shift, dw_act, y, stat_out);                                                     \
+  }
+#define FQ_PWDW_C(KT_, CW_, S_, LZ_, F_)                                                                                    \
+  {                                                                                                                        \
+    if (xc != nullptr) FQ_PWDW_GO(KT_, CW_, S_, LZ_, F_, 1) else FQ_PWDW_GO(KT_, CW_, S_, LZ_, F_, 0)                       \
   }
 #define FQ_PWDW_F(KT_, CW_, S_, LZ_)                                                                                        \
   {                                                                                                                        \
-    if (fast == 1) FQ_PWDW_GO(KT_, CW_, S_, LZ_, 1) else FQ_PWDW_GO(KT_, CW_, S_, LZ_, 0)                                   \
+    if (fast == 1) FQ_PWDW_C(KT_, CW_, S_, LZ_, 1) else FQ_PWDW_C(KT_, CW_, S_, LZ_, 0)                                     \
   }
 #define FQ_PWDW_S(KT_, CW_)                                                                                                 \
   {                                                                                                                        \
@@ -888,6 +946,7 @@ int fq_pwdw_fused(const float* x, const int8_t* wcodes, const float* wscale, con
 #undef FQ_PWDW_K
 #undef FQ_PWDW_S
 #undef FQ_PWDW_F
+#undef FQ_PWDW_C
 #undef FQ_PWDW_GO
   FQ_LAUNCH_CHECK();
   return FQ_OK;

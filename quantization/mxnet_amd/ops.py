@@ -653,9 +653,27 @@ def pwdw_supported(xshape, cout, stride):
         bool(lib.fq_pwdw_fused_supported(n, cin, int(cout), h, w, int(stride)))
 
 
+def pair_codes_shape(xshape):
+    """Shape of the int8 buffer in which `pwconv_i8_stat` hands the codes of an (N, Cin, H, W) input to `pwdw_fused`: the C16
+    layout of include/fakequant.h over whole 32-channel slabs."""
+    n, cin, h, w = (int(v) for v in xshape)
+    return (n, 2 * ((cin + 31) // 32), h * w, 16)
+
+
+def _check_pair_codes(t, name, x):
+    _check(t, name, torch.int8)
+    if x.dim() != 4 or tuple(t.shape) != pair_codes_shape(x.shape):
+        raise ValueError("%s must be int8 %s for x %s; got %s" % (name, pair_codes_shape(x.shape) if x.dim() == 4 else "(4-d x)",
+                                                                  tuple(x.shape), tuple(t.shape)))
+    if t.device != x.device:
+        raise ValueError("%s lives on %s, x on %s" % (name, t.device, x.device))
+    return t
+
+
 def pwconv_i8_stat(x, wcodes, wscale, wsum, bias=None, in_stat=None, in_thr=None, width=8, flags=0, cur_out=None,
-                   bn_scale=None, bn_shift=None, act=None):
+                   bn_scale=None, bn_shift=None, act=None, x_codes_out=None):
     """The statistic-only pass of a fused 1x1 convolution (fq_pwconv_i8_stat): what `pwconv_i8` computes without storing it.
+    `x_codes_out` (int8, `pair_codes_shape(x.shape)`): also keep the codes of x it multiplies with, for `pwdw_fused(x_codes=)`.
     Returns the per-sample maxima max|y[n]| (N,)."""
     _check(x, "x")
     _check(wcodes, "wcodes", torch.int8)
@@ -672,20 +690,24 @@ def pwconv_i8_stat(x, wcodes, wscale, wsum, bias=None, in_stat=None, in_thr=None
         raise ValueError("x has %d channels but the weight codes were made for a row length that pads to %d" % (cin, cin_pad))
     if in_stat is not None and cur_out is None:
         cur_out = torch.empty(1, dtype=torch.float32, device=x.device)
+    if x_codes_out is not None:
+        _check_pair_codes(x_codes_out, "x_codes_out", x)
     stat, zflag = _stat_target(n, x.device, True)
     hw = x.numel() // (n * cin)
     check_call(_lib_().fq_pwconv_i8_stat(_ptr(x), _ptr(wcodes), _ptr(wscale), _ptr(wsum), _ptr(bias), n, cin, cin_pad,
                                          wcodes.shape[0], cout, hw, _ptr(in_stat), _ptr(in_thr), int(width), int(flags), _ptr(cur_out),
-                                         _ptr(bn_scale), _ptr(bn_shift), _ACTS[act] | zflag, _ptr(stat), _stream(x)))
+                                         _ptr(bn_scale), _ptr(bn_shift), _ACTS[act] | zflag, _ptr(stat), _ptr(x_codes_out),
+                                         _stream(x)))
     return stat
 
 
 def pwdw_fused(x, wcodes, wscale, wsum, dw_w, pw_bias=None, in_stat=None, in_thr=None, width=8, flags=0, pw_bn_scale=None,
                pw_bn_shift=None, pw_act=None, mid_stat=None, mid_thr=None, mid_width=8, mid_flags=0, mid_cur_out=None,
-               dw_bias=None, stride=1, dw_bn_scale=None, dw_bn_shift=None, dw_act=None, want_stat=True):
+               dw_bias=None, stride=1, dw_bn_scale=None, dw_bn_shift=None, dw_act=None, want_stat=True, x_codes=None):
     """A fused 1x1 convolution and the depthwise 3x3 behind it in one launch (fq_pwdw_fused): the values of `pwconv_i8`
     followed by `dwconv3x3` with quantise-on-load, without the tensor between them.  `mid_stat`: the per-sample maxima of the
-    1x1 output (`pwconv_i8_stat`), or `mid_thr`: a stored threshold.  Returns (z, stat or None)."""
+    1x1 output (`pwconv_i8_stat`), or `mid_thr`: a stored threshold.  `x_codes`: what `pwconv_i8_stat(x_codes_out=)` wrote for
+    this x and this in_stat / in_thr / width / flags - the launch reads it instead of x.  Returns (z, stat or None)."""
     _check(x, "x")
     _check(wcodes, "wcodes", torch.int8)
     _check(wscale, "wscale")
@@ -705,6 +727,8 @@ def pwdw_fused(x, wcodes, wscale, wsum, dw_w, pw_bias=None, in_stat=None, in_thr
     cout_pad, cin_pad = wcodes.shape
     if (cin + 63) // 64 * 64 != cin_pad:
         raise ValueError("x has %d channels but the weight codes were made for a row length that pads to %d" % (cin, cin_pad))
+    if x_codes is not None:
+        _check_pair_codes(x_codes, "x_codes", x)
     ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
     y = torch.empty((n, cout, ho, wo), dtype=torch.float32, device=x.device)
     stat, zflag = _stat_target(n, x.device, want_stat)
@@ -713,7 +737,7 @@ def pwdw_fused(x, wcodes, wscale, wsum, dw_w, pw_bias=None, in_stat=None, in_thr
                                      _ptr(pw_bn_shift), _ACTS[pw_act], _ptr(mid_stat), _ptr(mid_thr), int(mid_width),
                                      int(mid_flags), _ptr(mid_cur_out), _ptr(dw_w), _ptr(dw_bias), int(stride),
                                      _ptr(dw_bn_scale), _ptr(dw_bn_shift), _ACTS[dw_act] | zflag, _ptr(y), _ptr(stat),
-                                     _stream(x)))
+                                     _ptr(x_codes), _stream(x)))
     return y, stat
 
 

@@ -469,7 +469,7 @@ def depthwise_recompute(block, x, weight_q, bias, flags, width):
                               width=p["width"], flags=p["flags"], pw_bn_scale=d["bn"][0], pw_bn_shift=d["bn"][1],
                               pw_act=d["act"], mid_stat=stat, mid_width=width, mid_flags=flags, mid_cur_out=cur,
                               dw_bias=None if bias is None else bias._t, stride=block._kwargs["stride"][0],
-                              dw_bn_scale=scale, dw_bn_shift=shift, dw_act=fz["act"])
+                              dw_bn_scale=scale, dw_bn_shift=shift, dw_act=fz["act"], x_codes=d.get("x_codes"))
     if not side:
         block._fq_last_n = n
         block.current_input_max = DeviceScalar(cur)
@@ -625,13 +625,19 @@ def pointwise_fused(block, F, x, weight_raw, weight_q, bias, plan, weights_quant
             if pair is not None:
                 # statistic only; the depthwise block behind recomputes the values inside its own launch
                 b_ = None if bias is None else bias._t
-                stat = ops.pwconv_i8_stat(x_arg, codes, scales, rowsum, b_, bn_scale=scale, bn_shift=shift, act=fz["act"], **plan)
+                from .. import fuse as _fuse
+                # the codes of x the pass quantises anyway, kept for the launch behind: a fresh buffer of the current stream per
+                # pair and forward (as the fused launch's output: safe with batches in flight and under graph capture)
+                xcodes = torch.empty(ops.pair_codes_shape(x_arg.shape), dtype=torch.int8, device=x_arg.device) \
+                    if _fuse.PAIR_CODES else None
+                stat = ops.pwconv_i8_stat(x_arg, codes, scales, rowsum, b_, bn_scale=scale, bn_shift=shift, act=fz["act"],
+                                          x_codes_out=xcodes, **plan)
                 xs = tuple(x_arg.shape)
                 res_ = NDArray(_placeholder((xs[0], block._kwargs["num_filter"], xs[2], xs[3]), x_arg.device))
                 res_._fq_stat = stat
                 res_._fq_deferred = dict(x=x_arg, codes=(codes, scales, rowsum), bias=b_, bn=(scale, shift), act=fz["act"],
                                          plan=dict(in_stat=plan["in_stat"], width=plan["width"], flags=plan["flags"],
-                                                   cur_out=plan.get("cur_out")), consumer=pair)
+                                                   cur_out=plan.get("cur_out")), consumer=pair, x_codes=xcodes)
                 return res_
             out = ops.pwconv_i8(x_arg, codes, scales, rowsum, None if bias is None else bias._t,
                                 bn_scale=scale, bn_shift=shift,

@@ -166,6 +166,9 @@ BN_ADD = _os.environ.get("FQ_BN_ADD", "1") != "0"
 RECOMPUTE = _os.environ.get("FQ_RECOMPUTE", "1") != "0"
 RECOMPUTE_MIN_PIXELS = int(_os.environ.get("FQ_RECOMPUTE_MIN_PIXELS", "3136"))
 RECOMPUTE_MAX_CIN = int(_os.environ.get("FQ_RECOMPUTE_MAX_CIN", "128"))      # (input channels of the 1x1: see DESIGN.md for the pairs that pay)
+# FQ_PWDW_CODES=0: the recomputing launch reads the fp32 input again and quantises it again instead of loading the codes the
+# statistic pass kept for it (A/B; results identical either way)
+PAIR_CODES = _os.environ.get("FQ_PWDW_CODES", "1") != "0"
 # Subsampled trunk (round 6, fq_pwconv_i8_sub2): the closing 1x1 of a ResNet-v1 stage stores only the pixels its two readers -
 # the next stage's first 1x1 and shortcut 1x1, both stride 2 without padding - look at (FQ_SUBSAMPLE=0: the whole tensor; A/B)
 SUBSAMPLE = _os.environ.get("FQ_SUBSAMPLE", "1") != "0"

@@ -1,7 +1,9 @@
 """The recompute pair alone on the GPU (round 6): fq_pwconv_i8 + fq_dwconv3x3 (two launches, the tensor between them written and
 read) against fq_pwconv_i8_stat + fq_pwdw_fused, on MobileNet1.0's pointwise -> depthwise pairs at batch 128.
 
-    python tools/pwdwbench.py [--batch 128] [--reps 30] [--pairs 1,2,3,4,5]
+    python tools/pwdwbench.py [--batch 128] [--reps 30] [--pairs 1,2,3,4,5] [--codes 0]
+
+--codes 1 (default): the statistic pass keeps the int8 codes of x and the fused launch loads them; 0: both read the fp32 x.
 
 Per pair: time of each launch (HIP events on the launch stream, median over reps, all launches back to back), bytes each form
 moves, and the resulting TB/s.  Values are checked bit-equal before timing."""
@@ -38,6 +40,7 @@ def main():
     ap.add_argument("--batch", type=int, default=128)
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--pairs", default="1,2,3,4,5")
+    ap.add_argument("--codes", type=int, default=1)
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
@@ -59,6 +62,7 @@ def main():
             print("%4d  %s: shape not taken" % (p, (n, cin, cout, hw, stride)))
             continue
         st = {}
+        xc = torch.empty(ops.pair_codes_shape(x.shape), dtype=torch.int8, device=dev) if a.codes else None
 
         def pw():
             st["y"], st["ys"] = ops.pwconv_i8(x, codes, scales, rowsum, None, in_stat=xstat, cur_out=cur1, bn_scale=sc1,
@@ -70,19 +74,20 @@ def main():
 
         def sa():
             st["ys1"] = ops.pwconv_i8_stat(x, codes, scales, rowsum, None, in_stat=xstat, cur_out=cur1, bn_scale=sc1,
-                                           bn_shift=sh1, act="relu")
+                                           bn_shift=sh1, act="relu", x_codes_out=xc)
 
         def fb():
             st["z1"], st["zs1"] = ops.pwdw_fused(x, codes, scales, rowsum, w2, in_stat=xstat, pw_bn_scale=sc1, pw_bn_shift=sh1,
                                                  pw_act="relu", mid_stat=st["ys1"], mid_cur_out=cur2, stride=stride,
-                                                 dw_bn_scale=sc2, dw_bn_shift=sh2, dw_act="relu")
+                                                 dw_bn_scale=sc2, dw_bn_shift=sh2, dw_act="relu", x_codes=xc)
         pw(); dw(); sa(); fb()
         torch.cuda.synchronize()
         ok = torch.equal(st["z"], st["z1"]) and torch.equal(st["zs"], st["zs1"]) and torch.equal(st["ys"], st["ys1"])
         t_pw, t_dw, t_sa, t_fb = timed(pw, a.reps), timed(dw, a.reps), timed(sa, a.reps), timed(fb, a.reps)
         ho = (hw - 1) // stride + 1
         xb, yb, zb = 4e-6 * n * cin * hw * hw, 4e-6 * n * cout * hw * hw, 4e-6 * n * cout * ho * ho
-        mb2, mb1 = xb + 2 * yb + zb, 2 * xb + zb
+        cb = 32e-6 * n * ((cin + 31) // 32) * hw * hw if a.codes else 0.0      # the code buffer: written once, read once
+        mb2, mb1 = xb + 2 * yb + zb, (xb + 2 * cb + zb if a.codes else 2 * xb + zb)
         tot2 += t_pw + t_dw
         tot1 += t_sa + t_fb
         print("%4d  %3d->%3d @%3dx%-3d dw stride %d   %7.1f + %6.1f = %7.1f (%4.2f TB/s)   %6.1f + %6.1f = %7.1f (%4.2f TB/s)   "
