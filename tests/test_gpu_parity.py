@@ -377,6 +377,11 @@ DW_SHAPES = [(2, 8, 7, 7), (3, 16, 14, 14), (2, 32, 28, 28), (2, 8, 56, 56), (2,
 @pytest.mark.parametrize("stride", [1, 2])
 @pytest.mark.parametrize("mode", ["plain", "online", "offline_signed", "bn_relu_online", "bias_relu6"])
 def test_dwconv3x3_vs_oracle(dev, ops, shape, stride, mode):
+    _dwconv_case(dev, ops, shape, stride, mode)
+
+
+def _dwconv_case(dev, ops, shape, stride, mode, twin=False):
+    """`twin`: also bit for bit against the host twin's true fmaf chain (the poisoned runs of tests/test_gpu_poison.py)."""
     rng = np.random.default_rng(sum(shape) * 7 + stride)
     n, c, h, w = shape
     x = (rng.standard_normal(shape) * 2).astype(np.float32)
@@ -411,6 +416,14 @@ def test_dwconv3x3_vs_oracle(dev, ops, shape, stride, mode):
     _eq(N(stat_out), O.absmax_per_sample(got), "statistic of the produced output")
     if "online" in mode:
         assert N(cur)[0] == okw["in_max"]
+    if twin:
+        from oracle import host as H
+        hkw = dict(okw)
+        if "online" in mode:
+            hkw.update(in_max=None, in_stat=stat)
+        hy, hstat = H.dwconv3x3(x, wt, stride=stride, want_stat=True, **hkw)
+        _eq(got, hy, "host twin")
+        _eq(N(stat_out), hstat, "host twin's statistic")
     # against an independent implementation (torch conv on the quantised input), loose
     import torch.nn.functional as TF
     xq = x if "in_max" not in okw else O.conv_input_fake_quant(x, okw["signed"], okw["width"],

@@ -86,7 +86,9 @@ def _t(a, dev):
     return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
 
 
-def _run_pair(k, dev, ops, fused):
+def _run_pair(k, dev, ops, fused, codes_buf=None):
+    """`codes_buf` (int8, `ops.pair_codes_shape`; fused only): the statistic pass writes the codes of x into it and the fused
+    launch reads them instead of x."""
     n, cin, cout, h, w, stride = k["case"]
     x = _t(k["x"], dev)
     flags = ops.act_flags(signed=k["signed"])
@@ -113,12 +115,12 @@ def _run_pair(k, dev, ops, fused):
                                  bn_shift=bn2[1], act=k["act2"], **in2)
         return dict(z=N(z), zstat=N(zstat), ystat=N(ystat), cur1=N(cur1), cur2=N(cur2))
     ystat = ops.pwconv_i8_stat(x, codes, scales, rowsum, b1, width=8, flags=flags, cur_out=cur1, bn_scale=bn1[0],
-                               bn_shift=bn1[1], act=k["act1"], **in1)
+                               bn_shift=bn1[1], act=k["act1"], x_codes_out=codes_buf, **in1)
     z, zstat = ops.pwdw_fused(x, codes, scales, rowsum, w2, pw_bias=b1, width=8, flags=flags, pw_bn_scale=bn1[0],
                               pw_bn_shift=bn1[1], pw_act=k["act1"], mid_stat=ystat, mid_thr=thr2, mid_width=8,
                               mid_flags=flags, mid_cur_out=cur2, dw_bias=b2, stride=stride, dw_bn_scale=bn2[0],
                               dw_bn_shift=bn2[1], dw_act=k["act2"], in_stat=None if k["offline"] else xstat,
-                              in_thr=in1.get("in_thr"))
+                              in_thr=in1.get("in_thr"), x_codes=codes_buf)
     return dict(z=N(z), zstat=N(zstat), ystat=N(ystat), cur1=N(cur1), cur2=N(cur2))
 
 
