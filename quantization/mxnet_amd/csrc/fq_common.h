@@ -15,6 +15,8 @@
 //   fq_pw_sample.hip   K2r pointwise, one block of 96..128 pixels x 256 / 512 channels per workgroup, output-stationary
 //   fq_pw_split.hip    K2m pointwise, one (pixel tile, channel group) per workgroup: every other layer from 28x28 planes down
 //   fq_pw_generic.hip  K2f pointwise for every other shape (quantise + transpose, then an integer GEMM)
+//   fq_mma.h           (header) what the kernels on v_mfma_i32_32x32x32_i8 share: statistic table, output quantiser
+//                      of a code output, epilogue choice, XCD work order, output windows (split, stream, 3x3, shortcut, generic)
 //   fq_pwconv.hip      fq_pwconv_i8: shape-based choice between the pointwise forms; the weight-code kernel (fq_weight_codes)
 //   fq_weights.hip     K3 weight fake-quant (layer / group / channel), generic STE, K4 Winograd-domain weights
 //   fq_calib.hip       K5 EMA, K6 global max, K7 histogram, K8 KL threshold search

@@ -3,6 +3,7 @@
 #ifndef FQ_CONV3X3_KERNEL_H_
 #define FQ_CONV3X3_KERNEL_H_
 
+#include "fq_mma.h"
 #include "fq_common.h"
 
 namespace {
@@ -60,14 +61,13 @@ __global__ __launch_bounds__(NW * 64, LB) void conv3x3_i8_kernel(
     const float* __restrict__ in_stat, int n, const float* __restrict__ in_thr, float levels, int lo_neg_max, float eps,
     float* __restrict__ cur_max_out, const float* __restrict__ bn_scale, const float* __restrict__ bn_shift, int act,
     float* __restrict__ stat_out, const float* __restrict__ out_thr) {
-  constexpr int kSlots = 8;
   constexpr int WP = NW / WC;                                           // wavefronts along the pixel direction
   constexpr int PT = PTW * WP;                                          // pixel tiles of a workgroup
   constexpr int NCH = WC * 32;                                          // output channels of a workgroup
   constexpr int RS = D + 1;
   constexpr int NS = 9 * KT;                                            // K-steps
   extern __shared__ __attribute__((aligned(16))) unsigned char c3_smem[];
-  __shared__ unsigned k_stat[kSlots];
+  __shared__ unsigned k_stat[kStatSlots];
   unsigned char* panel = c3_smem;                                       // [RT * 32][ROW] codes of the region
   float* c_sxw = reinterpret_cast<float*>(c3_smem + (size_t)g.RT * 32 * g.ROW);
   float* c_bsc = c_sxw + NCH;
@@ -76,17 +76,13 @@ __global__ __launch_bounds__(NW * 64, LB) void conv3x3_i8_kernel(
   int* c_zs = reinterpret_cast<int*>(c_bias + NCH);                     // [NSL][NCH]
 
   const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // scalar (see K2m)
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // scalar: what derives from it lives in SGPRs
   const int h = lane >> 5, pl = lane & 31;
   const unsigned HW = (unsigned)g.HW, W = (unsigned)g.W, cols = (unsigned)g.cols;
   const unsigned plane4 = HW * 4u;
   const bool has_bn = bn_scale != nullptr, has_stat = stat_out != nullptr;
-  unsigned item;                                                        // XCD-contiguous work order (K2m)
-  {
-    const unsigned per = ((unsigned)g.items + 7u) >> 3;
-    item = (blockIdx.x & 7u) * per + (blockIdx.x >> 3);
-    if ((blockIdx.x >> 3) >= per || item >= (unsigned)g.items) return;
-  }
+  unsigned item;                                                        // a (pixel block, group) pair, in mma_xcd_item's order
+  if (!mma_xcd_item(g.items, item)) return;
   const unsigned pb = item / (unsigned)g.CS, cg = item - pb * (unsigned)g.CS;
   const int ch0 = (int)cg * NCH;
   const unsigned j0 = pb * (32u * PT);                                  // first pixel of the block
@@ -133,7 +129,7 @@ __global__ __launch_bounds__(NW * 64, LB) void conv3x3_i8_kernel(
   // range mode (nn.Conv2D(quantized=True)): `bias` holds int32 codes that join the integer sum (one slice only)
   const int* ibias = lo_neg_max == kRangeMode ? reinterpret_cast<const int*>(bias) : nullptr;
   const float* fbias = lo_neg_max == kRangeMode ? nullptr : bias;
-  if (threadIdx.x < kSlots) k_stat[threadIdx.x] = 0u;
+  mma_stat_init(k_stat);
   for (int i = threadIdx.x; i < NCH; i += NW * 64) {
     const bool ok = ch0 + i < g.Cout;
     const int ic = ok ? ch0 + i : 0;
@@ -223,18 +219,12 @@ __global__ __launch_bounds__(NW * 64, LB) void conv3x3_i8_kernel(
   const int cvalid = g.Cout - (ch0 + wc * 32);                          // valid channels of this wavefront's tile
   const int zb = stored_zero4(ubias);                                   // four codes "0" in the stored representation
   // the consumer's quantiser of a C16 output (nn2_c: its clip range starts at 0 - the five-instruction form of fq_common.h)
-  QParams q2;
-  q2.lo = q2.hi = q2.denom = q2.scale = 0.0f;
-  q2.rden = 0.0;
-  if (OUT16) q2 = make_qparams(out_thr[0], g.out_levels, g.out_lo_neg != 0, eps);
+  const QParams q2 = mma_out_qparams<OUT16, false>(out_thr, nullptr, g.out_levels, g.out_lo_neg, eps);
   auto run = [&](auto bias_c, auto bn_c, auto act_c, auto nn2_c) __attribute__((always_inline)) {
     constexpr int BIAS_M = decltype(bias_c)::value, BN_M = decltype(bn_c)::value, ACT_M = decltype(act_c)::value;
     constexpr bool NN2 = decltype(nn2_c)::value;
-    // (a code output behind the compile-time ReLU: activation and the consumer's clip as ONE median, the statistic from the raw
-    // values - fq_pw_split_kernel.h)
-    constexpr bool FOLD = OUT16 && ACT_M == FQ_ACT_RELU;
-    QParams qc = q2;
-    if (FOLD) qc.lo = 0.0f;
+    constexpr bool FOLD = OUT16 && ACT_M == FQ_ACT_RELU;                 // (mma_fold; the ReLU is this form's only compile-time cell)
+    const QParams qc = mma_fold<ACT_M, FOLD>(q2);
     v16i acc[NSL][PTW];
 #pragma unroll
     for (int sl = 0; sl < NSL; ++sl)
@@ -254,8 +244,6 @@ __global__ __launch_bounds__(NW * 64, LB) void conv3x3_i8_kernel(
       }
 #pragma unroll
       for (int kt = 0; kt < KT; ++kt) {
-        constexpr int dummy = 0;
-        (void)dummy;
         const int s = tap * KT + kt;
         if (s + D < NS) {
 #pragma unroll
@@ -279,15 +267,14 @@ __global__ __launch_bounds__(NW * 64, LB) void conv3x3_i8_kernel(
       }
     }
     PW_STAMP(3);
-    // ---- 3. epilogue (K2m): lane = pixel, channels past Cout masked through out-of-range offsets ----------------------
-    int64_t y_bytes = (n_samp - s_base) * y_samp - (int64_t)(ch0 + wc * 32) * plane4;
-    y_bytes = y_bytes < 0x7FFFFFFFll ? y_bytes : 0x7FFFFFFFll;
+    // ---- 3. epilogue: lane = pixel; a window (mma_out_rsrc) from this wavefront's channel tile on - OUT16: from its first
+    // 16-channel block on; channels past Cout: kOobOffset
+    const int64_t skip = (int64_t)(ch0 + wc * 32) * plane4;
+    const int64_t y_bytes = mma_out_bytes(s_base, n_samp, y_samp, skip);
     const int64_t y_samp16 = (int64_t)g.CBo * HW * 16;
-    const int cb0 = (ch0 + wc * 32) >> 4;                                 // first output block of this wavefront (OUT16)
-    int64_t y16_bytes = (n_samp - s_base) * y_samp16 - (int64_t)cb0 * HW * 16;
-    y16_bytes = y16_bytes < 0x7FFFFFFFll ? y16_bytes : 0x7FFFFFFFll;
-    const fq_rsrc yr = OUT16 ? make_rsrc(reinterpret_cast<char*>(y) + s_base * y_samp16 + (int64_t)cb0 * HW * 16, y16_bytes)
-                             : make_rsrc(reinterpret_cast<char*>(y) + s_base * y_samp + (int64_t)(ch0 + wc * 32) * plane4, y_bytes);
+    const int64_t skip16 = (int64_t)((ch0 + wc * 32) >> 4) * HW * 16;
+    const int64_t y16_bytes = mma_out_bytes(s_base, n_samp, y_samp16, skip16);
+    const fq_rsrc yr = OUT16 ? mma_out_rsrc(y, s_base, y_samp16, skip16, y16_bytes) : mma_out_rsrc(y, s_base, y_samp, skip, y_bytes);
     const int ubias2 = 128 - g.out_zoff;
     const int cb = wc * 32 + 4 * h;
     const bool partial = cvalid < 32;
@@ -327,16 +314,16 @@ __global__ __launch_bounds__(NW * 64, LB) void conv3x3_i8_kernel(
           if (!FOLD) v = ACT_M < 0 ? act_rt(v, act) : act_rt(v, ACT_M);
           vq[r] = v;
           if (!OUT16) {
-            const unsigned off = partial ? (8 * gq + 4 * h + r < cvalid ? yo : 0x80000000u) : yo;
+            const unsigned off = partial ? (8 * gq + 4 * h + r < cvalid ? yo : kOobOffset) : yo;
             buf_st_f32(yr, off, (unsigned)(8 * gq + r) * plane4, v);
           }
           m = FOLD ? fmaxf(m, v) : fmaxf(m, fabsf(v));
         }
-        if (OUT16) {                               // (fq_pw_split_kernel.h: the consumer's codes of the four values, 4 bytes)
+        if (OUT16) {                               // the consumer's codes of the four values, 4 bytes
           const int packed = fq_pack4<NN2>(vq[0], vq[1], vq[2], vq[3], qc, ubias2, fq_nonneg_xor(ubias2));
           const bool blk_ok = !partial || 16 * (gq >> 1) < cvalid;
           const unsigned yo16 = (smp[t] - s_base) * (unsigned)g.CBo * HW * 16u + pp[t] * 16u + 4u * h;
-          buf_st_f32(yr, blk_ok ? yo16 : 0x80000000u, (unsigned)((gq >> 1) * (int)HW * 16 + 8 * (gq & 1)), __int_as_float(packed));
+          buf_st_f32(yr, blk_ok ? yo16 : kOobOffset, (unsigned)((gq >> 1) * (int)HW * 16 + 8 * (gq & 1)), __int_as_float(packed));
         }
       }
       if (has_stat) {
@@ -345,12 +332,12 @@ __global__ __launch_bounds__(NW * 64, LB) void conv3x3_i8_kernel(
           const float wm = wave_max_nonneg(m);
           if (lane == 0) {
             const unsigned slot = s0 - s_base;
-            if (slot < (unsigned)kSlots) atomicMax(&k_stat[slot], __float_as_uint(wm));
+            if (slot < (unsigned)kStatSlots) atomicMax(&k_stat[slot], __float_as_uint(wm));
             else atomic_max_f32(stat_out + s0, wm);
           }
         } else {
           const unsigned slot = smp[t] - s_base;
-          if (slot < (unsigned)kSlots) atomicMax(&k_stat[slot], __float_as_uint(m));
+          if (slot < (unsigned)kStatSlots) atomicMax(&k_stat[slot], __float_as_uint(m));
           else atomic_max_f32(stat_out + smp[t], m);
         }
       }
@@ -377,8 +364,7 @@ __global__ __launch_bounds__(NW * 64, LB) void conv3x3_i8_kernel(
   PW_STAMP(4);
   if (has_stat) {
     __syncthreads();
-    if (threadIdx.x < kSlots && k_stat[threadIdx.x] != 0u && s_base + threadIdx.x < cols / HW)
-      FQ_STAT_FLUSH_MAX(reinterpret_cast<unsigned*>(stat_out) + s_base + threadIdx.x, k_stat[threadIdx.x]);
+    mma_stat_flush(k_stat, stat_out, s_base, cols, HW);
   }
   PW_STAMP(5);
 }

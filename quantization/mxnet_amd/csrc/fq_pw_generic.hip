@@ -1,5 +1,6 @@
 // libfakequant — K2f pointwise (1x1) convolution on int8 codes for shapes the specialised forms do not take
 // (see fq_common.h for the list of translation units and the design rules)
+#include "fq_mma.h"
 #include "fq_pw.h"
 
 namespace {
@@ -100,10 +101,10 @@ __global__ __launch_bounds__(kBlock) void pwconv_i8_kernel(
     const float* __restrict__ bn_shift, int act, float* __restrict__ stat_out) {
   // per-output-channel constants of this workgroup's channel block, staged in LDS once: loading them from global in
   // the epilogue (16 dependent round trips per tile) was 90 % of this kernel's time
-  constexpr int kStatSlots = 16;
   __shared__ float k_sxw[256], k_bias[256], k_bsc[256], k_bsh[256];
   __shared__ int k_zs[256];
-  __shared__ unsigned k_stat[kStatSlots];
+  constexpr int kTileStatSlots = 16;     // a tile of up to 256 columns spans <= 16 samples from 16-pixel planes up (more: to memory)
+  __shared__ unsigned k_stat[kTileStatSlots];
   const float sx = sx_src[0] / levels;                                  // scale = max_/levels, as make_qparams
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wmi = wave % g.wm, wni = wave / g.wm;
@@ -168,13 +169,13 @@ __global__ __launch_bounds__(kBlock) void pwconv_i8_kernel(
     // holds, per (uu, tt), the 4 consecutive PIXELS j0 + uu*16 + 4*(lane>>4) + r of channel co0 + tt*16 + (lane&15)
     // -> one 16-byte store per (uu, tt) when the four pixels sit in one sample, and the per-channel constants are
     // per LANE (read once per tt).
-    // per-sample maxima of this tile go through an LDS table (a tile spans <= kStatSlots samples), then ONE global
+    // per-sample maxima of this tile go through an LDS table (mma_stat_init / _flush; a tile spans <= kTileStatSlots samples, else straight to memory), then ONE global
     // atomic per touched sample: per-wave global atomics on the 128 hot addresses serialised in L2 and cost 80 % of the
     // kernel (100 k same-address atomics per launch)
     const unsigned s_base = (unsigned)(ctile * g.PT_B) / HW;
     if (has_stat) {
       __syncthreads();
-      if (threadIdx.x < kStatSlots) k_stat[threadIdx.x] = 0u;
+      mma_stat_init(k_stat);
       __syncthreads();
     }
     int64_t ybase[4];
@@ -228,7 +229,7 @@ __global__ __launch_bounds__(kBlock) void pwconv_i8_kernel(
               if (smp == smps[uu]) m[uu] = fmaxf(m[uu], fabsf(o[r]));
               else if (has_stat) {
                 const unsigned slot = smp - s_base;
-                if (slot < kStatSlots) atomicMax(&k_stat[slot], __float_as_uint(fabsf(o[r])));
+                if (slot < kTileStatSlots) atomicMax(&k_stat[slot], __float_as_uint(fabsf(o[r])));
                 else atomic_max_f32(stat_out + smp, fabsf(o[r]));
               }
             }
@@ -241,13 +242,12 @@ __global__ __launch_bounds__(kBlock) void pwconv_i8_kernel(
       for (int uu = 0; uu < 4; ++uu) {
         if (cok[uu]) {
           const unsigned slot = smps[uu] - s_base;
-          if (slot < kStatSlots) atomicMax(&k_stat[slot], __float_as_uint(m[uu]));
+          if (slot < kTileStatSlots) atomicMax(&k_stat[slot], __float_as_uint(m[uu]));
           else atomic_max_f32(stat_out + smps[uu], m[uu]);
         }
       }
       __syncthreads();
-      if (threadIdx.x < kStatSlots && k_stat[threadIdx.x] != 0u && s_base + threadIdx.x < (unsigned)(g.cols / HW))
-        FQ_STAT_FLUSH_MAX(reinterpret_cast<unsigned*>(stat_out) + s_base + threadIdx.x, k_stat[threadIdx.x]);
+      mma_stat_flush(k_stat, stat_out, s_base, g.cols, HW);
     }
   }
 }

@@ -1,5 +1,6 @@
 // libfakequant — K2s: the closing 1x1 convolution of a residual unit WITH the unit's shortcut convolution in the same launch
 // (fq_pwconv_i8_shortcut; see fq_common.h for the list of translation units and the design rules)
+#include "fq_mma.h"
 #include "fq_pw.h"
 
 namespace {
@@ -57,14 +58,13 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 3) void pwconv_short_kernel(
     const float* __restrict__ in_stat, int n, const float* __restrict__ in_thr, float levels, int lo_neg_max, float eps,
     float* __restrict__ cur_max_out, const float* __restrict__ bn_scale, const float* __restrict__ bn_shift, int act,
     float* __restrict__ stat_out, PwShortIn2 s2) {
-  constexpr int kSlots = 8;
   constexpr int kShNW = NW;
   constexpr int NCH = NW * kShCW * 32;
   constexpr int NS = KT + KT2;                                          // slabs of the two inputs together
   constexpr int SLABS = (NS + kShNW - 1) / kShNW;                       // ... a wavefront quantises (s = wave + 4 j < NS)
   constexpr int RB = SLABS < 4 ? SLABS : 4;                             // slabs (16 loads each) in flight per lane
   extern __shared__ __attribute__((aligned(16))) unsigned char pwsh_smem[];
-  __shared__ unsigned k_stat[kSlots];
+  __shared__ unsigned k_stat[kStatSlots];
   v4i* panel = reinterpret_cast<v4i*>(pwsh_smem);                       // [KT][64] B fragments of y2's tile
   v4i* panel2 = panel + KT * 64;                                        // [KT2][64] ... of x's tile
   float* c_sxw = reinterpret_cast<float*>(pwsh_smem + (size_t)NS * 1024);
@@ -83,12 +83,8 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 3) void pwconv_short_kernel(
   const unsigned HW = (unsigned)g.HW, cols = (unsigned)g.cols;
   const unsigned plane4 = HW * 4u;
   const bool has_bn = bn_scale != nullptr, has_stat = stat_out != nullptr;
-  unsigned item;
-  {
-    const unsigned per = ((unsigned)g.items + 7u) >> 3;
-    item = (blockIdx.x & 7u) * per + (blockIdx.x >> 3);
-    if ((blockIdx.x >> 3) >= per || item >= (unsigned)g.items) return;
-  }
+  unsigned item;                                                        // a (tile, group) pair, in mma_xcd_item's order
+  if (!mma_xcd_item(g.items, item)) return;
   const unsigned tile = item / (unsigned)g.CS, cg = item - tile * (unsigned)g.CS;
   const int ch0 = (int)cg * NCH;
   const unsigned s_base = (tile * 32u) / HW;                            // first sample the tile touches
@@ -144,7 +140,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 3) void pwconv_short_kernel(
   const QParams q = make_qparams_rt(max_, levels, lo_neg_max, eps, in_thr);
   const QParams q2 = make_qparams_rt(max2_, s2.levels, s2.lo_neg, eps, s2.in_thr);
   const float sx = q.scale, sx2 = q2.scale;
-  if (threadIdx.x < kSlots) k_stat[threadIdx.x] = 0u;
+  mma_stat_init(k_stat);
   for (int i = threadIdx.x; i < NCH; i += kShNW * 64) {
     const int ic = ch0 + i;                                             // (host: Cout is a multiple of 256)
     c_sxw[i] = sx * wscale[ic];
@@ -212,22 +208,17 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 3) void pwconv_short_kernel(
   for (int d = 0; d < DD; ++d) ring[d] = frag(0, d);
   FQ_PIN();
   __syncthreads();                                                      // panels, constants and the statistic table
-  int64_t y_bytes = (n_samp - s_base) * y_samp - (int64_t)(ch0 + ctl0 * 32) * plane4;
-  y_bytes = y_bytes < 0x7FFFFFFFll ? y_bytes : 0x7FFFFFFFll;
-  const fq_rsrc yr = make_rsrc(reinterpret_cast<char*>(y) + s_base * y_samp + (int64_t)(ch0 + ctl0 * 32) * plane4, y_bytes);
+  // windows (mma_out_rsrc) from this wavefront's first channel tile on
+  const int64_t skip = (int64_t)(ch0 + ctl0 * 32) * plane4;
+  const fq_rsrc yr = mma_out_rsrc(y, s_base, y_samp, skip, mma_out_bytes(s_base, n_samp, y_samp, skip));
   const unsigned yo = ((smp - s_base) * (unsigned)g.Cout + 4u * h) * plane4 + p * 4u;
   // DUAL: the codes of y under the next unit's first convolution's threshold, beside y (unsigned codes of a [0, thr] range)
-  QParams q3;
-  q3.lo = q3.hi = q3.denom = q3.scale = 0.0f;
-  q3.rden = 0.0;
-  if (DUAL) q3 = make_qparams(g.dual_thr[0], g.out_levels, g.out_lo_neg != 0, eps);
+  const QParams q3 = mma_out_qparams<false, DUAL>(nullptr, g.dual_thr, g.out_levels, g.out_lo_neg, eps);
   const int ubias3 = 128 - g.out_zoff;
   const int64_t y_samp16 = (int64_t)g.CBo * HW * 16;
-  const int cb0 = (ch0 + ctl0 * 32) >> 4;                               // first output block of this wavefront
-  int64_t y16_bytes = (n_samp - s_base) * y_samp16 - (int64_t)cb0 * HW * 16;
-  y16_bytes = y16_bytes < 0x7FFFFFFFll ? y16_bytes : 0x7FFFFFFFll;
-  const fq_rsrc yr16 = make_rsrc(DUAL ? g.y16 + s_base * y_samp16 + (int64_t)cb0 * HW * 16 : reinterpret_cast<char*>(y),
-                                 DUAL ? y16_bytes : 0);
+  const int64_t skip16 = (int64_t)((ch0 + ctl0 * 32) >> 4) * HW * 16;   // ... first output block on
+  const fq_rsrc yr16 = DUAL ? mma_out_rsrc(g.y16, s_base, y_samp16, skip16, mma_out_bytes(s_base, n_samp, y_samp16, skip16))
+                            : make_rsrc(y, 0);
   const unsigned yo16 = (smp - s_base) * (unsigned)g.CBo * HW * 16u + p * 16u + 4u * h;
   float m = 0.0f;
 #pragma unroll
@@ -287,22 +278,9 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 3) void pwconv_short_kernel(
     }
   }
   if (has_stat) {
-    const unsigned s0 = (unsigned)__builtin_amdgcn_readfirstlane((int)smp);
-    if (__all(smp == s0)) {
-      const float wm = wave_max_nonneg(m);
-      if (lane == 0) {
-        const unsigned slot = s0 - s_base;
-        if (slot < (unsigned)kSlots) atomicMax(&k_stat[slot], __float_as_uint(wm));
-        else atomic_max_f32(stat_out + s0, wm);
-      }
-    } else {
-      const unsigned slot = smp - s_base;
-      if (slot < (unsigned)kSlots) atomicMax(&k_stat[slot], __float_as_uint(m));
-      else atomic_max_f32(stat_out + smp, m);
-    }
+    mma_stat_update(k_stat, stat_out, smp, s_base, m);
     __syncthreads();
-    if (threadIdx.x < kSlots && k_stat[threadIdx.x] != 0u && s_base + threadIdx.x < cols / HW)
-      FQ_STAT_FLUSH_MAX(reinterpret_cast<unsigned*>(stat_out) + s_base + threadIdx.x, k_stat[threadIdx.x]);
+    mma_stat_flush(k_stat, stat_out, s_base, cols, HW);
   }
 }
 

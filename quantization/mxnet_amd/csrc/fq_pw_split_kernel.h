@@ -3,6 +3,7 @@
 #ifndef FQ_PW_SPLIT_KERNEL_H_
 #define FQ_PW_SPLIT_KERNEL_H_
 
+#include "fq_mma.h"
 #include "fq_pw.h"
 
 namespace {
@@ -55,13 +56,12 @@ __global__ __launch_bounds__(NW * 64, LB) void pwconv_split_kernel(
     float* __restrict__ cur_max_out, const float* __restrict__ bn_scale, const float* __restrict__ bn_shift, int act,
     float* __restrict__ stat_out, const float* __restrict__ residual, const float* __restrict__ out_thr) {
   static_assert(!SUB || !OUT16, "the subsampled output is built for fp32 output (DUAL: and its code copy)");
-  constexpr int kSlots = 8;
   constexpr int SLABS = (KT + NW - 1) / NW;                             // slabs a wavefront quantises (kt = wave + NW j < KT)
   constexpr int RB = SLABS < 4 ? SLABS : 4;                             // slabs (16 loads each) in flight per lane
   constexpr int NCH = NW * CW * 32;                                     // output channels of one workgroup
   constexpr int RS = D + 1;                                             // ring slots
   extern __shared__ __attribute__((aligned(16))) unsigned char pwsp_smem[];
-  __shared__ unsigned k_stat[kSlots];
+  __shared__ unsigned k_stat[kStatSlots];
   v4i* panel = reinterpret_cast<v4i*>(pwsp_smem);                       // [KT][64] B fragments of the tile
   float* c_sxw = reinterpret_cast<float*>(pwsp_smem + (size_t)KT * 1024);
   float* c_bsc = c_sxw + NCH;
@@ -76,15 +76,8 @@ __global__ __launch_bounds__(NW * 64, LB) void pwconv_split_kernel(
   const unsigned HW = (unsigned)g.HW, cols = (unsigned)g.cols;
   const unsigned plane4 = HW * 4u;                                      // bytes between two channels of one sample
   const bool has_bn = bn_scale != nullptr, has_stat = stat_out != nullptr;
-  // XCD-aware order: workgroup b runs on XCD b % 8 (each XCD has its own L2), and a 32-pixel tile of a 14x14 / 7x7 plane
-  // is 128 bytes that are NOT line-aligned, so neighbouring tiles share their first / last cache line of every channel:
-  // give every XCD a CONTIGUOUS range of (tile, group) items so that both halves of such a line meet in one L2
-  unsigned item;
-  {
-    const unsigned per = ((unsigned)g.items + 7u) >> 3;
-    item = (blockIdx.x & 7u) * per + (blockIdx.x >> 3);
-    if ((blockIdx.x >> 3) >= per || item >= (unsigned)g.items) return;
-  }
+  unsigned item;                                                        // a (tile, group) pair, in mma_xcd_item's order
+  if (!mma_xcd_item(g.items, item)) return;
   const unsigned tile = item / (unsigned)g.CS, cg = item - tile * (unsigned)g.CS;
   const int ch0 = (int)cg * NCH;                                        // first output channel of this workgroup
   const unsigned s_base = (tile * 32u) / HW;                            // first sample the tile touches
@@ -118,7 +111,7 @@ __global__ __launch_bounds__(NW * 64, LB) void pwconv_split_kernel(
                            : ((smp - s_base) * (unsigned)g.Cin + 16u * h) * plane4_in + p_in * 4u;
   auto issue = [&](int kt, float (&v)[16]) __attribute__((always_inline)) {
     if (IN16) {
-      const unsigned off = (2 * kt + h) < g.CBi ? xo : 0x80000000u;      // a block past the tensor's channels: zeros
+      const unsigned off = (2 * kt + h) < g.CBi ? xo : kOobOffset; // a block past the tensor's channels: zeros
       const v4i c = buf_ld_v4i(xr, off, (unsigned)(2 * kt) * (unsigned)g.HWin * 16u);
       v[0] = __int_as_float(c[0]); v[1] = __int_as_float(c[1]); v[2] = __int_as_float(c[2]); v[3] = __int_as_float(c[3]);
       return;
@@ -149,7 +142,7 @@ __global__ __launch_bounds__(NW * 64, LB) void pwconv_split_kernel(
   // range mode (nn.Conv2D(quantized=True)): `bias` holds int32 codes that join the integer sum
   const int* ibias = lo_neg_max == kRangeMode ? reinterpret_cast<const int*>(bias) : nullptr;
   const float* fbias = lo_neg_max == kRangeMode ? nullptr : bias;
-  if (threadIdx.x < kSlots) k_stat[threadIdx.x] = 0u;
+  mma_stat_init(k_stat);
   for (int i = threadIdx.x; i < NCH; i += NW * 64) {
     const bool ok = ch0 + i < g.Cout;                                   // channels past Cout: all-zero constants
     const int ic = ok ? ch0 + i : 0;
@@ -212,27 +205,14 @@ __global__ __launch_bounds__(NW * 64, LB) void pwconv_split_kernel(
   __syncthreads();                                                      // panel, constants and the statistic table
   PW_STAMP(3);
   const int cvalid = g.Cout - (ch0 + ctl0 * 32);                       // valid output channels from this wavefront's first tile on
-  QParams q2;
-  q2.lo = q2.hi = q2.denom = q2.scale = 0.0f;
-  q2.rden = 0.0;
-  if (OUT16) q2 = make_qparams(out_thr[0], g.out_levels, g.out_lo_neg != 0, eps);
   // DUAL (fq_pwconv_i8_c16_dual): y is fp32 AND g.y16 receives the codes of the same values under g.dual_thr - the trunk of a
   // ResNet stored a second time, 1 B per element, for the next unit's first 1x1 (the shortcut keeps reading the fp32 tensor)
-  if (DUAL) q2 = make_qparams(g.dual_thr[0], g.out_levels, g.out_lo_neg != 0, eps);
-  // (nn2_c: the CONSUMER's clip range of a C16 output starts at 0 - the five-instruction quantiser of fq_common.h writes its
-  // codes; round 5: until then only the second output's)
+  const QParams q2 = mma_out_qparams<OUT16, DUAL>(out_thr, g.dual_thr, g.out_levels, g.out_lo_neg, eps);
   auto run = [&](auto bias_c, auto bn_c, auto act_c, auto nn2_c) __attribute__((always_inline)) {
     constexpr int BIAS_M = decltype(bias_c)::value, BN_M = decltype(bn_c)::value, ACT_M = decltype(act_c)::value;
     constexpr bool NN2 = decltype(nn2_c)::value;
-    // A code output behind a compile-time ReLU / ReLU6: activation and the consumer's clip are ONE median - clip(relu6(v), lo
-    // <= 0, hi) == med3(v, 0, min(6, hi)) for every v, NaN -> 0 on both sides - and the statistic max_i relu6(v_i) ==
-    // min(max(0, max_i v_i), 6) is taken from the raw values and clamped once per wavefront (a v_med3 less per output)
-    constexpr bool FOLD = OUT16 && !DUAL && (ACT_M == FQ_ACT_RELU || ACT_M == FQ_ACT_RELU6);
-    QParams qc = q2;
-    if (FOLD) {
-      qc.lo = 0.0f;
-      if (ACT_M == FQ_ACT_RELU6) qc.hi = fminf(q2.hi, 6.0f);
-    }
+    constexpr bool FOLD = OUT16 && !DUAL && (ACT_M == FQ_ACT_RELU || ACT_M == FQ_ACT_RELU6);   // (mma_fold)
+    const QParams qc = mma_fold<ACT_M, FOLD>(q2);
     // accumulators start at zero (the first MFMA takes the constant): initialising them with the +128 re-centring terms
     // keeps a second set of 16 * CW registers alive next to the destination of the first MFMAs; the terms are added as
     // integers in the epilogue instead (one VALU per output)
@@ -260,40 +240,35 @@ __global__ __launch_bounds__(NW * 64, LB) void pwconv_split_kernel(
     }
     PW_STAMP(4);
     // ---- 3. epilogue: lane = pixel, two full lines per store instruction -------------------------------------------------
-    // The resource is bounded below 2 GiB, so a lane offset of 0x80000000 is out of range for it: that is how the channels
-    // past Cout of a PARTIAL channel tile are masked (the hardware drops the store; no branch, no exec juggling).
-    int64_t y_bytes = (n_samp - s_base) * y_samp - (int64_t)(ch0 + ctl0 * 32) * plane4;
-    y_bytes = y_bytes < 0x7FFFFFFFll ? y_bytes : 0x7FFFFFFFll;
+    // Windows (mma_out_rsrc) from this wavefront's first channel tile on; channels past Cout of a PARTIAL tile: kOobOffset.
     // SUB: stores go to the dense tensor of the even pixels of the even rows (plane4s bytes per channel); the residual
     // operand keeps the full planes
+    const int64_t skip = (int64_t)(ch0 + ctl0 * 32) * plane4;
+    const int64_t y_bytes = mma_out_bytes(s_base, n_samp, y_samp, skip);
     const unsigned plane4s = SUB ? (unsigned)g.SHWs * 4u : plane4;
     const int64_t y_samp_s = SUB ? (int64_t)g.Cout * g.SHWs * 4 : y_samp;
-    int64_t ys_bytes = (n_samp - s_base) * y_samp_s - (int64_t)(ch0 + ctl0 * 32) * plane4s;
-    ys_bytes = ys_bytes < 0x7FFFFFFFll ? ys_bytes : 0x7FFFFFFFll;
-    // OUT16: y is a C16 code tensor; the resource starts at (first sample, this wavefront's first 16-channel block)
+    const int64_t skip_s = (int64_t)(ch0 + ctl0 * 32) * plane4s;
+    const int64_t ys_bytes = mma_out_bytes(s_base, n_samp, y_samp_s, skip_s);
+    // OUT16: y is a C16 code tensor; the window starts at (first sample, this wavefront's first 16-channel block)
     // (SUB + DUAL: the code copy holds the stored pixels only, as y does)
     const unsigned HWo = SUB ? (unsigned)g.SHWs : HW;                      // pixels of a stored plane
     const int64_t y_samp16 = (int64_t)g.CBo * HWo * 16;
-    const int cb0 = (ch0 + ctl0 * 32) >> 4;                               // first output block of this wavefront
-    int64_t y16_bytes = (n_samp - s_base) * y_samp16 - (int64_t)cb0 * HWo * 16;
-    y16_bytes = y16_bytes < 0x7FFFFFFFll ? y16_bytes : 0x7FFFFFFFll;
-    const fq_rsrc yr = OUT16 ? make_rsrc(reinterpret_cast<char*>(y) + s_base * y_samp16 + (int64_t)cb0 * HWo * 16, y16_bytes)
-                             : make_rsrc(reinterpret_cast<char*>(y) + s_base * y_samp_s + (int64_t)(ch0 + ctl0 * 32) * plane4s, ys_bytes);
+    const int64_t skip16 = (int64_t)((ch0 + ctl0 * 32) >> 4) * HWo * 16;  // ... to the first output block of this wavefront
+    const int64_t y16_bytes = mma_out_bytes(s_base, n_samp, y_samp16, skip16);
+    const fq_rsrc yr = OUT16 ? mma_out_rsrc(y, s_base, y_samp16, skip16, y16_bytes) : mma_out_rsrc(y, s_base, y_samp_s, skip_s, ys_bytes);
     unsigned yo16 = (smp - s_base) * (unsigned)g.CBo * HWo * 16u + p * 16u + 4u * h;
-    const fq_rsrc yr16 = make_rsrc(DUAL ? g.y16 + s_base * y_samp16 + (int64_t)cb0 * HWo * 16 : reinterpret_cast<char*>(y),
-                                   DUAL ? y16_bytes : 0);
+    const fq_rsrc yr16 = DUAL ? mma_out_rsrc(g.y16, s_base, y_samp16, skip16, y16_bytes) : make_rsrc(y, 0);
     const int ubias2 = 128 - g.out_zoff;
     // the residual operand (the shortcut of a ResNet / MobileNetV2 unit) has y's shape: same offsets, added after BatchNorm
     const bool has_res = residual != nullptr;
-    const fq_rsrc rr = make_rsrc(reinterpret_cast<const char*>(has_res ? residual : y) + s_base * y_samp +
-                                 (int64_t)(ch0 + ctl0 * 32) * plane4, has_res ? y_bytes : 0);
+    const fq_rsrc rr = mma_out_rsrc(has_res ? residual : y, s_base, y_samp, skip, has_res ? y_bytes : 0);
     const unsigned yo = ((smp - s_base) * (unsigned)g.Cout + 4u * h) * plane4 + p * 4u;
     unsigned yos = yo;                           // the lane's store offset (SUB: out of range for a pixel that is not stored)
     if (SUB) {
       const unsigned ho = p / (unsigned)g.SW, wo = p - ho * (unsigned)g.SW;
-      yos = ((ho | wo) & 1u) ? 0x80000000u
+      yos = ((ho | wo) & 1u) ? kOobOffset
                              : ((smp - s_base) * (unsigned)g.Cout + 4u * h) * plane4s + ((ho >> 1) * (unsigned)g.SWs + (wo >> 1)) * 4u;
-      yo16 = ((ho | wo) & 1u) ? 0x80000000u
+      yo16 = ((ho | wo) & 1u) ? kOobOffset
                               : (smp - s_base) * (unsigned)g.CBo * HWo * 16u + ((ho >> 1) * (unsigned)g.SWs + (wo >> 1)) * 16u + 4u * h;
     }
     float m = 0.0f;
@@ -302,12 +277,10 @@ __global__ __launch_bounds__(NW * 64, LB) void pwconv_split_kernel(
       const int cb = (ctl0 + c) * 32 + 4 * h;                           // channel inside the workgroup's group
       float res[16];
       if (has_res) {                             // all 16 in flight before the first use
-        // channels past Cout of a PARTIAL tile get the same out-of-range offset as their stores and so read 0: the
-        // resource runs to the end of the tensor, an unmasked load would fetch the NEXT sample's channels 0.. and, with
-        // all-zero constants, carry that foreign value into the statistic `m` below
+        // (channels past Cout of a PARTIAL tile: masked like their stores, see kOobOffset)
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-          const unsigned off = MASKED ? (8 * (i >> 2) + 4 * h + (i & 3) < cv ? yo : 0x80000000u) : yo;
+          const unsigned off = MASKED ? (8 * (i >> 2) + 4 * h + (i & 3) < cv ? yo : kOobOffset) : yo;
           res[i] = buf_ld_f32(rr, off, (unsigned)(c * 32 + 8 * (i >> 2) + (i & 3)) * plane4);
         }
       }
@@ -333,7 +306,7 @@ __global__ __launch_bounds__(NW * 64, LB) void pwconv_split_kernel(
           if (!FOLD) v = ACT_M < 0 ? act_rt(v, act) : act_rt(v, ACT_M);
           vq[r] = v;
           if (!OUT16) {
-            const unsigned off = MASKED ? (8 * gq + 4 * h + r < cv ? yos : 0x80000000u) : yos;
+            const unsigned off = MASKED ? (8 * gq + 4 * h + r < cv ? yos : kOobOffset) : yos;
             buf_st_f32(yr, off, (unsigned)(c * 32 + 8 * gq + r) * plane4s, v);
           }
           m = FOLD ? fmaxf(m, v) : fmaxf(m, fabsf(v));   // channels past Cout have all-zero constants: v == 0
@@ -347,7 +320,7 @@ __global__ __launch_bounds__(NW * 64, LB) void pwconv_split_kernel(
           const int packed = DUAL ? fq_pack4<true>(vq[0], vq[1], vq[2], vq[3], q2, ubias2, 0x80808080u)
                                   : fq_pack4<NN2>(vq[0], vq[1], vq[2], vq[3], qc, ubias2, fq_nonneg_xor(ubias2));
           const bool blk_ok = !MASKED || 16 * (gq >> 1) < cv;             // a whole block past Cout does not exist
-          buf_st_f32(OUT16 ? yr : yr16, blk_ok ? yo16 : 0x80000000u,
+          buf_st_f32(OUT16 ? yr : yr16, blk_ok ? yo16 : kOobOffset,
                      (unsigned)((c * 2 + (gq >> 1)) * (int)HWo * 16 + 8 * (gq & 1)), __int_as_float(packed));
         }
       }
@@ -360,48 +333,13 @@ __global__ __launch_bounds__(NW * 64, LB) void pwconv_split_kernel(
       else if (cv > 0) store_tile(c, cv, std::true_type{});
     }
     if (FOLD && ACT_M == FQ_ACT_RELU6) m = fminf(m, 6.0f);
-    if (has_stat) {
-      const unsigned s0 = (unsigned)__builtin_amdgcn_readfirstlane((int)smp);
-      if (__all(smp == s0)) {
-        const float wm = wave_max_nonneg(m);
-        if (lane == 0) {
-          const unsigned slot = s0 - s_base;
-          if (slot < (unsigned)kSlots) atomicMax(&k_stat[slot], __float_as_uint(wm));
-          else atomic_max_f32(stat_out + s0, wm);
-        }
-      } else {
-        const unsigned slot = smp - s_base;
-        if (slot < (unsigned)kSlots) atomicMax(&k_stat[slot], __float_as_uint(m));
-        else atomic_max_f32(stat_out + smp, m);
-      }
-    }
+    if (has_stat) mma_stat_update(k_stat, stat_out, smp, s_base, m);
   };
-  using std::integral_constant;
-  // (only a kernel that writes codes is instantiated twice: with the five-instruction quantiser of fq_common.h where the values it
-  // clips cannot be negative - the consumer's range starts at 0, or a ReLU stands in front of it - and with the general one)
-  auto go = [&](auto bias_c, auto bn_c, auto act_c, bool nn2) __attribute__((always_inline)) {
-    if constexpr (OUT16 && !DUAL) {
-      if (nn2) run(bias_c, bn_c, act_c, std::true_type{});
-      else run(bias_c, bn_c, act_c, std::false_type{});
-    } else {
-      run(bias_c, bn_c, act_c, std::false_type{});
-    }
-  };
-  const bool nn2_relu = q2.denom > 0.0f, nn2_any = fq_nonneg(q2);
-  if (cvalid <= 0) {
-    // nothing to multiply (a channel group wider than the layer): this wavefront only helped to quantise the tile
-  } else if (fbias == nullptr && has_bn && act == FQ_ACT_RELU)
-    go(integral_constant<int, 0>{}, integral_constant<int, 1>{}, integral_constant<int, FQ_ACT_RELU>{}, nn2_relu);
-  else if (fbias == nullptr && has_bn && act == FQ_ACT_RELU6)
-    go(integral_constant<int, 0>{}, integral_constant<int, 1>{}, integral_constant<int, FQ_ACT_RELU6>{}, nn2_relu);
-  else if (fbias == nullptr && has_bn && act == FQ_ACT_NONE)
-    go(integral_constant<int, 0>{}, integral_constant<int, 1>{}, integral_constant<int, FQ_ACT_NONE>{}, nn2_any);
-  else
-    go(integral_constant<int, -1>{}, integral_constant<int, -1>{}, integral_constant<int, -1>{}, nn2_any);
+  // (cvalid <= 0 - a channel group wider than the layer: nothing to multiply, this wavefront only helped to quantise the tile)
+  if (cvalid > 0) mma_epilogue_dispatch(fbias, has_bn, act, q2, std::integral_constant<bool, OUT16 && !DUAL>{}, run);
   if (has_stat) {
     __syncthreads();
-    if (threadIdx.x < kSlots && k_stat[threadIdx.x] != 0u && s_base + threadIdx.x < cols / HW)
-      FQ_STAT_FLUSH_MAX(reinterpret_cast<unsigned*>(stat_out) + s_base + threadIdx.x, k_stat[threadIdx.x]);
+    mma_stat_flush(k_stat, stat_out, s_base, cols, HW);
   }
   PW_STAMP(5);
 }

@@ -1,5 +1,6 @@
 // libfakequant — K2h pointwise (1x1) convolution on int8 codes, whole weight matrix resident in LDS
 // (see fq_common.h for the list of translation units and the design rules)
+#include "fq_mma.h"
 #include "fq_pw.h"
 
 namespace {
@@ -50,9 +51,8 @@ __global__ __launch_bounds__(kBlock, 2) void pwconv_stream_kernel(
     const float* __restrict__ in_stat, int n, const float* __restrict__ in_thr, float levels, int lo_neg_max, float eps,
     float* __restrict__ cur_max_out, const float* __restrict__ bn_scale, const float* __restrict__ bn_shift, int act,
     float* __restrict__ stat_out, const float* __restrict__ residual, const float* __restrict__ out_thr) {
-  constexpr int kSlots = 8;
   extern __shared__ __attribute__((aligned(16))) unsigned char pws_smem[];
-  __shared__ unsigned k_stat[kSlots];
+  __shared__ unsigned k_stat[kStatSlots];
   v4i* ldsA = reinterpret_cast<v4i*>(pws_smem);                        // [CT][KT][64] fragments
   const int nch = g.CT * 32;
   float* c_sxw = reinterpret_cast<float*>(pws_smem + (size_t)g.CT * KT * 1024);
@@ -137,7 +137,7 @@ __global__ __launch_bounds__(kBlock, 2) void pwconv_stream_kernel(
   if (OUT16) q2 = make_qparams(out_thr[0], g.out_levels, g.out_lo_neg != 0, eps);
   if (DUAL) q2 = make_qparams(g.dual_thr[0], g.out_levels, g.out_lo_neg != 0, eps);
   const int ubias2 = 128 - g.out_zoff;
-  if (threadIdx.x < kSlots) k_stat[threadIdx.x] = 0u;
+  mma_stat_init(k_stat);
   // weights -> fragment order: fragment (ct, kt), lane (row % 32) + 32 * (16-byte chunk % 2)
   for (int idx = threadIdx.x; idx < nch * KT * 2; idx += kBlock) {
     const int row = idx / (KT * 2), kc = idx - row * (KT * 2);
@@ -182,7 +182,7 @@ __global__ __launch_bounds__(kBlock, 2) void pwconv_stream_kernel(
     constexpr bool NN2 = decltype(nn2_c)::value;
     constexpr int BIAS_M = decltype(bias_c)::value, BN_M = decltype(bn_c)::value, ACT_M = decltype(act_c)::value;
     // (a code output behind a compile-time ReLU / ReLU6: activation and the consumer's clip as ONE median, the statistic from
-    // the raw values - fq_pw_split_kernel.h)
+    // the raw values - mma_fold in fq_mma.h)
     constexpr bool FOLD = OUT16 && !DUAL && (ACT_M == FQ_ACT_RELU || ACT_M == FQ_ACT_RELU6);
     QParams qc = q2;
     if (FOLD) {
@@ -211,8 +211,8 @@ __global__ __launch_bounds__(kBlock, 2) void pwconv_stream_kernel(
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
           const bool okc = !PART || ct * 32 + 8 * (i >> 2) + 4 * h + (i & 3) < g.Cout;
-          res[i] = (NT & 1) ? buf_ld_f32_nt(rr, okc ? yoff : 0x80000000u, (unsigned)((ct * 32 + 8 * (i >> 2) + (i & 3)) * plane * 4))
-                            : buf_ld_f32(rr, okc ? yoff : 0x80000000u, (unsigned)((ct * 32 + 8 * (i >> 2) + (i & 3)) * plane * 4));
+          res[i] = (NT & 1) ? buf_ld_f32_nt(rr, okc ? yoff : kOobOffset, (unsigned)((ct * 32 + 8 * (i >> 2) + (i & 3)) * plane * 4))
+                            : buf_ld_f32(rr, okc ? yoff : kOobOffset, (unsigned)((ct * 32 + 8 * (i >> 2) + (i & 3)) * plane * 4));
         }
       }
 #pragma unroll
@@ -254,8 +254,8 @@ __global__ __launch_bounds__(kBlock, 2) void pwconv_stream_kernel(
           } else if (PART) {
             const int chn = ct * 32 + 8 * gq + 4 * h + r;
             const unsigned so = (unsigned)((ct * 32 + 8 * gq + r) * plane * 4);
-            buf_st_f32(yrp, chn < g.Cout ? yoff : 0x80000000u, so, v.x);
-            buf_st_f32(yrp, chn + 1 < g.Cout ? yoff : 0x80000000u, so + (unsigned)(plane * 4), v.y);
+            buf_st_f32(yrp, chn < g.Cout ? yoff : kOobOffset, so, v.x);
+            buf_st_f32(yrp, chn + 1 < g.Cout ? yoff : kOobOffset, so + (unsigned)(plane * 4), v.y);
           } else {
             char* yb = reinterpret_cast<char*>(y) + (int64_t)(ct * 32 + 8 * gq + r) * plane * 4 + yoff;
             if (NT & 2) {
@@ -277,7 +277,7 @@ __global__ __launch_bounds__(kBlock, 2) void pwconv_stream_kernel(
             const int blk = 2 * ct + (gq >> 1);
             const unsigned o16 = (unsigned)((((int64_t)px.smp * g.CBo + (blk < g.CBo ? blk : 0)) * plane + px.p) * 16 +
                                             8 * (gq & 1) + 4 * h);
-            buf_st_f32(yrp, blk < g.CBo ? o16 : 0x80000000u, 0, __int_as_float(packed));
+            buf_st_f32(yrp, blk < g.CBo ? o16 : kOobOffset, 0, __int_as_float(packed));
           } else {                                     // (DUAL: the host asks for Cout % 32 == 0)
             char* yb = (DUAL ? g.y16 : reinterpret_cast<char*>(y)) +
                        (((int64_t)px.smp * g.CBo + 2 * ct + (gq >> 1)) * plane + px.p) * 16 + 8 * (gq & 1) + 4 * h;
@@ -294,12 +294,12 @@ __global__ __launch_bounds__(kBlock, 2) void pwconv_stream_kernel(
         const float wm = wave_max_nonneg(px.valid ? m : 0.0f);
         if (lane == 0) {
           const unsigned slot = s0 - s_base;
-          if (slot < (unsigned)kSlots) atomicMax(&k_stat[slot], __float_as_uint(wm));
+          if (slot < (unsigned)kStatSlots) atomicMax(&k_stat[slot], __float_as_uint(wm));
           else atomic_max_f32(stat_out + s0, wm);
         }
       } else if (px.valid) {
         const unsigned slot = px.smp - s_base;
-        if (slot < (unsigned)kSlots) atomicMax(&k_stat[slot], __float_as_uint(m));
+        if (slot < (unsigned)kStatSlots) atomicMax(&k_stat[slot], __float_as_uint(m));
         else atomic_max_f32(stat_out + px.smp, m);
       }
     }
@@ -365,8 +365,7 @@ __global__ __launch_bounds__(kBlock, 2) void pwconv_stream_kernel(
 
   if (has_stat) {
     __syncthreads();
-    if (threadIdx.x < kSlots && k_stat[threadIdx.x] != 0u && s_base + threadIdx.x < cols / HW)
-      FQ_STAT_FLUSH_MAX(reinterpret_cast<unsigned*>(stat_out) + s_base + threadIdx.x, k_stat[threadIdx.x]);
+    mma_stat_flush(k_stat, stat_out, s_base, cols, HW);
   }
 }
 
