@@ -265,11 +265,17 @@ int fq_stem_conv7x7s2_pool(const float* x, const float* w_tap_major, const float
  *   acc  = sum over ky,kx (row-major) of fmaf(w[c][ky][kx], xq[..], acc), zero padding, + bias[c] if given;
  *   y    = act(acc * bn_scale[c] + bn_shift[c]) if bn_scale given else act(acc);
  *   stat_out[n] (may be NULL) <- max|y[n]|;  out_current_max (may be NULL) <- batch mean of in_stat when in_stat is given.
- * x: (n, c, h, w);  w: (c, 1, 3, 3);  y: (n, c, ho, wo), ho = (h - 1) / stride + 1.                                 */
+ * x: (n, c, h, w);  w: (c, 1, 3, 3);  y: (n, c, ho, wo), ho = (h - 1) / stride + 1.
+ * y == NULL: the layer's STATISTIC PASS - stat_out (required) and out_current_max are written exactly as above, from values
+ * that are bit for bit those the storing launch stores, and nothing else is.  Taken for stride 1, a quantised input and
+ * w % 4 == 0 (16-byte aligned x); every other call without y is refused.  x_codes_out (statistic pass only, may be NULL;
+ * in_width <= 8): int8 [n][c][h * w], planar like x, 16-byte aligned - receives the integer code the quantise-on-load made of
+ * every element of x, roundf(clip(x) / (max_/levels + eps)), as its low byte (two's complement for FQ_ACT_SIGNED codes, 0..255
+ * otherwise).  fq_pwconv_i8_stat (below) recomputes y from it.                                                           */
 int fq_dwconv3x3(const float* x, const float* w, const float* bias, float* y, int64_t n, int64_t c, int64_t h,
                  int64_t wdt, int stride, const float* in_stat, const float* in_thr, int in_width, unsigned in_flags,
                  float* out_current_max, const float* bn_scale, const float* bn_shift, int act, float* stat_out,
-                 fqStream_t stream);
+                 fqStream_t stream, void* x_codes_out);
 
 /* ---- pointwise (1x1) convolution on the integer codes -----------------------------------------------------------------
  * After fake-quantisation both operands of a convolution are integers times a scale: x_q = cx * sx (cx in [0, 2^w-1]
@@ -414,13 +420,23 @@ int fq_pwconv_i8_gap(const float* x, const int8_t* wcodes, const float* wscale, 
  * channels past cin hold the code of 0; n * 2 * ceil(cin / 32) * h * w * 16 bytes, 16-byte aligned.  fq_pwdw_fused(x_codes !=
  * NULL) reads that buffer INSTEAD of x (x may then be NULL and is never dereferenced) and quantises nothing on its input side;
  * every value it produces is the one it produces from x.  Contract: x_codes is what fq_pwconv_i8_stat wrote for the same x,
- * in_stat / in_thr, in_width and in_flags - the launch cannot check it.  NULL on either side: behave as without it.         */
-int fq_pwconv_i8_stat_supported(int64_t n, int64_t cin, int64_t cout, int64_t hw);
+ * in_stat / in_thr, in_width and in_flags - the launch cannot check it.  NULL on either side: behave as without it.
+ * A depthwise layer in FRONT of the pair.  When x itself is the output of a stride-1 fq_dwconv3x3 that ran as a statistic pass
+ * (y == NULL, x_codes_out kept), (A) recomputes it: front_codes != NULL makes fq_pwconv_i8_stat read that layer's input codes
+ * ([n][cin][front_h * front_wdt] int8), dequantise them with the threshold front_in_stat / front_in_thr, front_width,
+ * front_flags give (code * max_/levels), run fq_dwconv3x3's chain with front_w (cin, 1, 3, 3), front_bias, front_bn_scale /
+ * front_bn_shift and front_act on them - bit for bit the values that launch would have stored - and go on as above with those
+ * values as x: in_stat / in_thr are the statistic / threshold of the depthwise OUTPUT, x_codes_out receives ITS codes.  x is not
+ * dereferenced.  hw == front_h * front_wdt.  Shapes: fq_pwconv_i8_stat_supported(..., front_h, front_wdt) with both non-zero -
+ * cin 16 or 32, front_wdt % 4 == 0 and at most 256 (0, 0: the question for the launch without a front layer).              */
+int fq_pwconv_i8_stat_supported(int64_t n, int64_t cin, int64_t cout, int64_t hw, int64_t front_h, int64_t front_wdt);
 int fq_pwconv_i8_stat(const float* x, const int8_t* wcodes, const float* wscale, const int32_t* wsum, const float* bias,
                       int64_t n, int64_t cin, int64_t cin_pad, int64_t cout_pad, int64_t cout, int64_t hw,
                       const float* in_stat, const float* in_thr, int in_width, unsigned in_flags, float* out_current_max,
                       const float* bn_scale, const float* bn_shift, int act, float* stat_out, void* x_codes_out,
-                      fqStream_t stream);
+                      fqStream_t stream, const void* front_codes, const float* front_w, const float* front_bias,
+                      const float* front_bn_scale, const float* front_bn_shift, int front_act, const float* front_in_stat,
+                      const float* front_in_thr, int front_width, unsigned front_flags, int64_t front_h, int64_t front_wdt);
 int fq_pwdw_fused_supported(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w, int stride);
 /* Test hook: out[i] <- the fp32 quotient c[i] / d[0] as the two kernels above compute it (the fp32 correction step of
  * csrc/fq_common.h: fast_quot, or the fp64-reciprocal form when d[0] does not qualify; took_fast_path[0] says which) - must

@@ -56,18 +56,20 @@ EXPORTS = {
     "fq_stem_conv7x7s2_pool": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _int, _vp, _vp]),
     "fq_stem_conv7x7s2_pool_supported": (_int, [_i64, _i64]),
     "fq_stem_conv3x3s2_c16": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _int, _vp, _vp, _int, _uint, _vp]),
+    # ..., act, stat_out, stream, x_codes_out
     "fq_dwconv3x3": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _vp, _vp, _int, _uint, _vp, _vp, _vp, _int,
-                            _vp, _vp]),
+                            _vp, _vp, _vp]),
     "fq_dwconv3x3_c16": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _vp, _vp, _int, _uint, _vp, _vp, _vp, _int,
                                 _vp, _vp, _int, _uint, _vp]),
     "fq_weight_codes": (_int, [_vp, _i64, _i64, _int, _int, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "fq_pwconv_workspace_bytes": (ctypes.c_size_t, [_i64, _i64, _i64]),
     "fq_pwconv_i8": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _int, _uint, _vp, _vp,
                             _vp, _int, _vp, _vp, _vp]),
-    "fq_pwconv_i8_stat_supported": (_int, [_i64, _i64, _i64, _i64]),
-    # ..., act, stat_out, x_codes_out, stream
+    "fq_pwconv_i8_stat_supported": (_int, [_i64, _i64, _i64, _i64, _i64, _i64]),      # n, cin, cout, hw, front_h, front_w
+    # ..., act, stat_out, x_codes_out, stream, front_codes, front_w, front_bias, front_bn_scale, front_bn_shift, front_act,
+    # front_in_stat, front_in_thr, front_width, front_flags, front_h, front_wdt
     "fq_pwconv_i8_stat": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _int, _uint, _vp, _vp,
-                                 _vp, _int, _vp, _vp, _vp]),
+                                 _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _int, _uint, _i64, _i64]),
     "fq_pwdw_fused_supported": (_int, [_i64, _i64, _i64, _i64, _i64, _int]),
     # x, wcodes, wscale, wsum, pw_bias, n, cin, cin_pad, cout_pad, cout, h, w, in_stat, in_thr, in_width, in_flags, pw_bn_scale,
     # pw_bn_shift, pw_act, mid_stat, mid_thr, mid_width, mid_flags, mid_cur, dw_w, dw_bias, dw_stride, dw_bn_scale, dw_bn_shift,

@@ -743,6 +743,24 @@ __device__ __forceinline__ float lane_next(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x130, 0xF, 0xF, false));
 }
 
+// The 3x3 sum of one output: rows a, b, c (above, centre, below), each as left / centre / right.  The order of these nine
+// operations is the numerical contract of the unit (the oracle emulates exactly this chain).
+__device__ __forceinline__ float dw_taps(float w00, float w01, float w02, float w10, float w11, float w12, float w20,
+                                         float w21, float w22, float a0, float a1, float a2, float b0, float b1, float b2,
+                                         float c0, float c1, float c2) {
+  float acc = 0.0f;
+  acc = fmaf(w00, a0, acc);
+  acc = fmaf(w01, a1, acc);
+  acc = fmaf(w02, a2, acc);
+  acc = fmaf(w10, b0, acc);
+  acc = fmaf(w11, b1, acc);
+  acc = fmaf(w12, b2, acc);
+  acc = fmaf(w20, c0, acc);
+  acc = fmaf(w21, c1, acc);
+  acc = fmaf(w22, c2, acc);
+  return acc;
+}
+
 // Epilogue of the depthwise kernels.  EPI 0: bias / BN / activation decided at run time (hipcc turns the wave-uniform
 // branches into four selects per output); EPI 1 / 2: the fused-inference case - BN, no bias, ReLU / ReLU6 - in 3 / 4
 // instructions.  Same operations in the same order either way.

@@ -10,23 +10,7 @@ __device__ __forceinline__ f2 splat2(float v) { return (f2){v, v}; }
 // ---------------------------------------------------------------------------------------------------------------
 // What the five kernel forms below share.  Each thing is written here once.
 // ---------------------------------------------------------------------------------------------------------------
-// The 3x3 sum of one output: rows a, b, c (above, centre, below), each as left / centre / right.  The order of these nine
-// operations is the numerical contract of the unit (the oracle emulates exactly this chain).
-__device__ __forceinline__ float dw_taps(float w00, float w01, float w02, float w10, float w11, float w12, float w20,
-                                         float w21, float w22, float a0, float a1, float a2, float b0, float b1, float b2,
-                                         float c0, float c1, float c2) {
-  float acc = 0.0f;
-  acc = fmaf(w00, a0, acc);
-  acc = fmaf(w01, a1, acc);
-  acc = fmaf(w02, a2, acc);
-  acc = fmaf(w10, b0, acc);
-  acc = fmaf(w11, b1, acc);
-  acc = fmaf(w12, b2, acc);
-  acc = fmaf(w20, c0, acc);
-  acc = fmaf(w21, c1, acc);
-  acc = fmaf(w22, c2, acc);
-  return acc;
-}
+// (dw_taps, the 3x3 sum of one output, lives in fq_common.h: fq_pwconv_i8_stat recomputes a depthwise layer with it)
 // Two outputs as ONE chain of packed fp32 FMAs (v_pk_fma_f32: two IEEE FMAs per lane per instruction, same order)
 __device__ __forceinline__ f2 dw_taps2(float w00, float w01, float w02, float w10, float w11, float w12, float w20, float w21,
                                        float w22, f2 a0, f2 a1, f2 a2, f2 b0, f2 b1, f2 b2, f2 c0, f2 c1, f2 c2) {
@@ -931,7 +915,11 @@ __global__ __launch_bounds__(kBlock) void dwconv3x3_flat_kernel(
 // NT: nontemporal LOADS - an input beyond the 256 MB Infinity Cache is dead after this pass and should not displace the
 // output, which the consumer does find there (measured in the model: 64 @112x112 stride 2, 411 MB in / 103 MB out, 110 -> 99 us;
 // with nontemporal stores too, or on the 205 MB inputs of the stride-1 layers, the step gets slower)
-template <int S, bool QUANT, bool ONLINE, bool NT, int EPI>
+// NOSTORE (stride 1, quantised input): the layer's statistic pass - every output is computed as above and joins the maximum, none
+// is stored.  `y` then is no output: when not null it is the int8 buffer [n][c][h * w] that receives the CODE of every input
+// element as the quantise-on-load produced it (the low byte of the integer: two's complement for signed codes) - one dword per
+// lane and input row, written by the compute lane that owns the four columns (the halo lanes' copies are not written).
+template <int S, bool QUANT, bool ONLINE, bool NT, int EPI, bool NOSTORE = false>
 __global__ __launch_bounds__(kBlock) void dwconv3x3_cols4_kernel(
     const float* __restrict__ x, const float* __restrict__ wgt, const float* __restrict__ bias,
     float* __restrict__ y, DwColGeom g, int64_t total_segs, const float* __restrict__ in_stat, int n,
@@ -941,6 +929,7 @@ __global__ __launch_bounds__(kBlock) void dwconv3x3_cols4_kernel(
   // and hit the same DRAM pages; one load per step (a ring) spreads them ~700 cycles apart, and with thousands of
   // waves each streaming its own plane every access then opens a new page.
   constexpr int D = (S == 1) ? 4 : 2;
+  static_assert(!NOSTORE || (S == 1 && QUANT), "the statistic pass exists for stride 1 with a quantised input");
   __shared__ unsigned k_stat[kStatSlots];
   if (threadIdx.x < kStatSlots) k_stat[threadIdx.x] = 0u;
   // (deriving q after the first block's loads, as K2d does, was measured 3-5 % SLOWER here: the row bursts of these large
@@ -986,6 +975,17 @@ __global__ __launch_bounds__(kBlock) void dwconv3x3_cols4_kernel(
     };
     auto quant4 = [&](f4 v) -> f4 { return QUANT ? fq_code4(v, q) * q.scale : v; };
     auto finish = [&](float acc) -> float { return dw_finish<EPI>(acc, bias != nullptr, bch, has_bn, bsc, bsh, act); };
+    // statistic pass: input row `row` quantised, its codes kept (where there is such a row and a buffer)
+    unsigned* const cp = reinterpret_cast<unsigned*>(y) + (plane * (int64_t)plane_in + (ld_ok ? ic0 : 0)) / 4;
+    auto quant4_keep = [&](f4 v, int row) -> f4 {
+      const f4 k = fq_code4(v, q);
+      if (y != nullptr && is_out && row <= last_row) {
+        const unsigned b0 = (unsigned)(int)k.x & 255u, b1 = (unsigned)(int)k.y & 255u, b2 = (unsigned)(int)k.z & 255u,
+                       b3 = (unsigned)(int)k.w & 255u;
+        cp[(int64_t)row * rowq] = b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
+      }
+      return k * q.scale;
+    };
 
     if (S == 1) {
       // a, b, c: rows r-1, r, r+1 as (left, v.x, v.y, v.z, v.w, right)
@@ -994,13 +994,13 @@ __global__ __launch_bounds__(kBlock) void dwconv3x3_cols4_kernel(
 #pragma unroll
       for (int k = 0; k < D; ++k) raw[k] = ldrow(1 + k);
       {
-        const f4 v = quant4(ldrow(0));
+        const f4 v = NOSTORE ? quant4_keep(ldrow(0), 0) : quant4(ldrow(0));
         b[0] = lane_prev(v.w);
         b[1] = v.x; b[2] = v.y; b[3] = v.z; b[4] = v.w;
         b[5] = lane_next(v.x);
       }
       auto emit = [&](int r, f4 craw) {
-        const f4 v = quant4(craw);
+        const f4 v = NOSTORE ? quant4_keep(craw, r + 1) : quant4(craw);
         float c[6];
         c[0] = lane_prev(v.w);
         c[1] = v.x; c[2] = v.y; c[3] = v.z; c[4] = v.w;
@@ -1013,7 +1013,7 @@ __global__ __launch_bounds__(kBlock) void dwconv3x3_cols4_kernel(
         }
         const float mm = fmaxf(fmaxf(fabsf(o[0]), fabsf(o[1])), fmaxf(fabsf(o[2]), fabsf(o[3])));
         m = fmaxf(m, keep(mm, is_out));
-        if (is_out) {
+        if (!NOSTORE && is_out) {
           if (g.nts) __builtin_nontemporal_store((f4){o[0], o[1], o[2], o[3]}, reinterpret_cast<f4*>(yp + (int64_t)r * g.Wo));
           else *reinterpret_cast<f4*>(yp + (int64_t)r * g.Wo) = (f4){o[0], o[1], o[2], o[3]};
         }
@@ -1115,6 +1115,7 @@ struct DwCall {
   float levels, eps;
   int lo_neg;
   int64_t ho, wo;
+  void* x_codes_out;        // y == NULL (the statistic pass): where the codes of x go, or NULL
 };
 
 // The launch of every form: zeroes the statistic, opens the profile scope, turns (quant, online) and epi into template
@@ -1123,9 +1124,13 @@ template <class KernelFor, class... Geom>
 int dw_launch(const DwCall& d, int grid, size_t lds, KernelFor kernel_for, Geom... geom) {
   using std::integral_constant;
   if (d.stat_out && !d.prezeroed) FQ_HIP(hipMemsetAsync(d.stat_out, 0, d.n * sizeof(float), d.st));
-  ProfScope prof(FQ_KERNEL_DWCONV, 4.0 * ((double)d.n * d.c * d.h * d.wdt + (double)d.n * d.c * d.ho * d.wo), d.st);
+  // algorithmic bytes: the layer's; moved: the statistic pass reads x and writes at most one byte per element of it
+  const double in_bytes = 4.0 * (double)d.n * d.c * d.h * d.wdt, out_bytes = 4.0 * (double)d.n * d.c * d.ho * d.wo;
+  ProfScope prof(FQ_KERNEL_DWCONV, in_bytes + out_bytes, d.st,
+                 d.y ? -1.0 : in_bytes + (d.x_codes_out ? 0.25 * in_bytes : 0.0));
+  float* const y_arg = d.y ? d.y : static_cast<float*>(d.x_codes_out);      // (the statistic pass takes its code buffer there)
   auto launch = [&](auto kernel) {
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, d.st, d.x, d.w, d.bias, d.y, geom..., d.in_stat, (int)d.n,
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, d.st, d.x, d.w, d.bias, y_arg, geom..., d.in_stat, (int)d.n,
                        d.in_thr, d.levels, d.lo_neg, d.eps, d.out_current_max, d.bn_scale, d.bn_shift, d.act, d.stat_out);
   };
   auto with_epi = [&](auto quant_c, auto online_c) {
@@ -1256,7 +1261,7 @@ int dw_cols_grid(int64_t total_segs, const DwColGeom& cg) {
   return dw_grid(dw_blocks(total_segs, cg.segs), dw_wg_per_cu);
 }
 bool dw_cols4_applies(const DwCall& d, int form) {
-  const bool can4 = (d.wdt % 4 == 0) && aligned16(d.x) && aligned16(d.y) && ((d.h * d.wdt) % 4 == 0) &&
+  const bool can4 = (d.wdt % 4 == 0) && aligned16(d.x) && aligned16(d.y) && aligned16(d.x_codes_out) && ((d.h * d.wdt) % 4 == 0) &&
                     (d.stride == 1 || ((d.wdt / 2) % 2 == 0));
   return (form == 3 || form == 0) && can4;
 }
@@ -1276,6 +1281,14 @@ int dw_run_cols4(const DwCall& d) {
       return dwconv3x3_cols4_kernel<decltype(s)::value, q(), o(), decltype(nt_c)::value, e()>;
     }, cg, total_segs);
   };
+  if (d.y == nullptr) {       // the statistic pass (dwconv3x3_impl: stride 1, quantised input)
+    auto go_stat = [&](auto nt_c) {
+      return dw_launch(d, grid, 0, [](auto, auto o, auto e) {
+        return dwconv3x3_cols4_kernel<1, true, o(), decltype(nt_c)::value, e(), true>;
+      }, cg, total_segs);
+    };
+    return nt ? go_stat(std::true_type{}) : go_stat(std::false_type{});
+  }
   if (d.stride == 1) return nt ? go(dw_int<1>{}, std::true_type{}) : go(dw_int<1>{}, std::false_type{});
   return nt ? go(dw_int<2>{}, std::true_type{}) : go(dw_int<2>{}, std::false_type{});
 }
@@ -1354,8 +1367,12 @@ int dw_run_tiles(const DwCall& d) {
 static int dwconv3x3_impl(const float* x, const float* w, const float* bias, float* y, int64_t n, int64_t c, int64_t h,
                           int64_t wdt, int stride, const float* in_stat, const float* in_thr, int in_width, unsigned in_flags,
                           float* out_current_max, const float* bn_scale, const float* bn_shift, int act, float* stat_out,
-                          fqStream_t stream) {
-  FQ_REQUIRE(x && w && y, "fq_dwconv3x3: null pointer");
+                          fqStream_t stream, void* x_codes_out = nullptr) {
+  FQ_REQUIRE(x && w && (y || stat_out), "fq_dwconv3x3: null pointer");
+  FQ_REQUIRE(y || !x_codes_out || (in_width <= 8 && !(in_flags & kFlagRangeRecord) &&
+                                   ((in_flags & FQ_ACT_SIGNED) || !(in_flags & FQ_ACT_LO_NEG_MAX))),
+             "fq_dwconv3x3: x_codes_out keeps codes that fit a byte (at most 8 bits; unsigned levels with a clip range from 0)");
+  FQ_REQUIRE(!(y && x_codes_out), "fq_dwconv3x3: x_codes_out belongs to the statistic pass (y == NULL)");
   FQ_REQUIRE(n > 0 && c > 0 && h > 0 && wdt > 0 && n * c < (1ll << 31) && h * wdt < (1ll << 28),
              "fq_dwconv3x3: bad shape (n=%lld c=%lld h=%lld w=%lld)", (long long)n, (long long)c, (long long)h,
              (long long)wdt);
@@ -1371,7 +1388,7 @@ static int dwconv3x3_impl(const float* x, const float* w, const float* bias, flo
   static const int epi_on = env_int("FQ_DW_EPI", 1);    // 0: always the run-time epilogue (A/B)
 
   DwCall d = {};
-  d.x = x; d.w = w; d.bias = bias; d.y = y;
+  d.x = x; d.w = w; d.bias = bias; d.y = y; d.x_codes_out = x_codes_out;
   d.n = n, d.c = c, d.h = h, d.wdt = wdt, d.stride = stride;
   d.in_stat = in_stat, d.in_thr = in_thr, d.out_current_max = out_current_max;
   d.bn_scale = bn_scale, d.bn_shift = bn_shift, d.act = act, d.stat_out = stat_out;
@@ -1388,6 +1405,13 @@ static int dwconv3x3_impl(const float* x, const float* w, const float* bias, flo
   // 0 auto, 1 LDS tiles, 2 one column per lane, 3 four columns per lane, 4 whole planes, 5 flat.  A forced form that does
   // not take the shape falls through to the next one that does.
   static const int form = env_int("FQ_DW_FORM", 0);
+  if (y == nullptr) {         // the statistic pass: one form
+    FQ_REQUIRE(quant && stride == 1 && dw_cols4_applies(d, 3),
+               "fq_dwconv3x3: without y (statistic pass) only stride 1, a quantised input and rows of a multiple of 4 floats, "
+               "16-byte aligned, are taken (n=%lld c=%lld h=%lld w=%lld stride %d)", (long long)n, (long long)c, (long long)h,
+               (long long)wdt, stride);
+    return dw_run_cols4(d);
+  }
   if (dw_flat_applies(d, form)) return dw_run_flat(d);
   if (dw_planes_applies(d, form)) return dw_run_planes(d);
   if (dw_cols4_applies(d, form)) return dw_run_cols4(d);
@@ -1412,10 +1436,10 @@ extern "C" {
 int fq_dwconv3x3(const float* x, const float* w, const float* bias, float* y, int64_t n, int64_t c, int64_t h,
                  int64_t wdt, int stride, const float* in_stat, const float* in_thr, int in_width, unsigned in_flags,
                  float* out_current_max, const float* bn_scale, const float* bn_shift, int act, float* stat_out,
-                 fqStream_t stream) {
+                 fqStream_t stream, void* x_codes_out) {
   FQ_REQUIRE(!(in_flags & ~(FQ_ACT_SIGNED | FQ_ACT_LO_NEG_MAX | FQ_ACT_NO_ABS | FQ_ACT_NO_EPS)), "fq_dwconv3x3: unknown flags");
   return dwconv3x3_impl(x, w, bias, y, n, c, h, wdt, stride, in_stat, in_thr, in_width, in_flags, out_current_max, bn_scale,
-                        bn_shift, act, stat_out, stream);
+                        bn_shift, act, stat_out, stream, x_codes_out);
 }
 
 }  // extern "C"

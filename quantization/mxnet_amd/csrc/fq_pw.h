@@ -7,6 +7,17 @@
 
 namespace fqi {
 
+// fq_pwconv_i8_stat with a front layer: the stride-1 depthwise 3x3 whose output the call's x stands for (fakequant.h)
+struct PwFront {
+  const void* codes;             // [n][cin][h * wdt] int8: the codes of the depthwise layer's input
+  const float *w, *bias, *bn_scale, *bn_shift;
+  int act, epi;                  // epi: kEpi* (fq_common.h), the epilogue fq_dwconv3x3 would have chosen
+  const float *in_stat, *in_thr;
+  float levels;
+  bool is_signed;
+  int64_t h, wdt;
+};
+
 struct PwCall {
   const float* x;
   const int8_t* wcodes;          // [rows_pad][cin_pad] int8 (+ the fragment-major copy behind it, fq_weight_codes)
@@ -52,10 +63,12 @@ struct PwCall {
   void* eval_ws = nullptr;
   // fq_pwconv_i8_stat: where the statistic pass leaves the codes of x for fq_pwdw_fused ([n][2 ceil(cin / 32)][hw][16] bytes)
   void* x_codes_out = nullptr;
+  const PwFront* front = nullptr;   // fq_pwconv_i8_stat: x is not read but recomputed from this layer's input codes
 };
 
 // K2z  fq_pwdw.hip: the statistic-only pass (fq_pwconv_i8_stat): stat_out and out_current_max only, c.y is not touched
 bool pw_stat_shape_ok(int64_t n, int64_t cin, int64_t cout, int64_t hw);
+bool pw_stat_front_shape_ok(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w);      // ... with a front layer
 int pw_stat_launch(const PwCall& c);
 // K2s  fq_pw_short.hip: the closing 1x1 of a residual unit (a) with the unit's shortcut convolution (b) in the same launch
 bool pw_short_shape_ok(int64_t cin, int64_t cin2, int64_t cout);

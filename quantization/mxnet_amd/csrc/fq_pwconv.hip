@@ -238,7 +238,9 @@ int fq_pwconv_i8(const float* x, const int8_t* wcodes, const float* wscale, cons
 
 // The statistic-only pass in front of fq_pwdw_fused (round 6): the per-sample maxima fq_pwconv_i8 would leave in stat_out
 // (and its out_current_max) without computing, let alone storing, more of the output than its extreme sums (fq_pwdw.hip, K2z).
-int fq_pwconv_i8_stat_supported(int64_t n, int64_t cin, int64_t cout, int64_t hw) {
+int fq_pwconv_i8_stat_supported(int64_t n, int64_t cin, int64_t cout, int64_t hw, int64_t front_h, int64_t front_wdt) {
+  if (front_h != 0 || front_wdt != 0)
+    return (front_h > 0 && front_wdt > 0 && front_h * front_wdt == hw && pw_stat_front_shape_ok(n, cin, cout, front_h, front_wdt)) ? 1 : 0;
   return pw_stat_shape_ok(n, cin, cout, hw) ? 1 : 0;
 }
 
@@ -246,8 +248,10 @@ int fq_pwconv_i8_stat(const float* x, const int8_t* wcodes, const float* wscale,
                       int64_t n, int64_t cin, int64_t cin_pad, int64_t cout_pad, int64_t cout, int64_t hw,
                       const float* in_stat, const float* in_thr, int in_width, unsigned in_flags, float* out_current_max,
                       const float* bn_scale, const float* bn_shift, int act, float* stat_out, void* x_codes_out,
-                      fqStream_t stream) {
-  FQ_REQUIRE(x && wcodes && wscale && wsum && stat_out, "fq_pwconv_i8_stat: null pointer");
+                      fqStream_t stream, const void* front_codes, const float* front_w, const float* front_bias,
+                      const float* front_bn_scale, const float* front_bn_shift, int front_act, const float* front_in_stat,
+                      const float* front_in_thr, int front_width, unsigned front_flags, int64_t front_h, int64_t front_wdt) {
+  FQ_REQUIRE((x || front_codes) && wcodes && wscale && wsum && stat_out, "fq_pwconv_i8_stat: null pointer");
   FQ_REQUIRE(pw_stat_shape_ok(n, cin, cout, hw), "fq_pwconv_i8_stat: shape not taken (n=%lld cin=%lld cout=%lld hw=%lld): see "
              "fq_pwconv_i8_stat_supported", (long long)n, (long long)cin, (long long)cout, (long long)hw);
   FQ_REQUIRE(cin_pad >= cin && cin_pad % 64 == 0 && cin_pad <= 8192 && cout_pad >= cout && cout_pad % 32 == 0,
@@ -260,8 +264,30 @@ int fq_pwconv_i8_stat(const float* x, const int8_t* wcodes, const float* wscale,
   c.prezeroed = (act & FQ_STAT_PREZEROED) != 0;
   act &= ~FQ_STAT_PREZEROED;
   FQ_REQUIRE(act >= FQ_ACT_NONE && act <= FQ_ACT_RELU6, "fq_pwconv_i8_stat: unknown activation %d", act);
-  FQ_REQUIRE(aligned16(wcodes) && aligned16(x) && aligned16(x_codes_out),
+  FQ_REQUIRE(aligned16(wcodes) && (front_codes || aligned16(x)) && aligned16(x_codes_out),
              "fq_pwconv_i8_stat: x, wcodes and x_codes_out must be 16-byte aligned");
+  PwFront front = {};
+  if (front_codes != nullptr) {
+    FQ_REQUIRE(front_w && (front_in_stat || front_in_thr) && aligned16(front_codes), "fq_pwconv_i8_stat: the front layer needs "
+               "its weights, in_stat or in_thr, and 16-byte aligned codes");
+    FQ_REQUIRE(front_h * front_wdt == hw && pw_stat_front_shape_ok(n, cin, cout, front_h, front_wdt),
+               "fq_pwconv_i8_stat: front layer not taken (n=%lld cin=%lld cout=%lld %lldx%lld): see fq_pwconv_i8_stat_supported",
+               (long long)n, (long long)cin, (long long)cout, (long long)front_h, (long long)front_wdt);
+    FQ_REQUIRE(front_width >= 2 && front_width <= 8 && !(front_flags & ~(FQ_ACT_SIGNED | FQ_ACT_LO_NEG_MAX)) &&
+                   ((front_flags & FQ_ACT_SIGNED) || !(front_flags & FQ_ACT_LO_NEG_MAX)),
+               "fq_pwconv_i8_stat: the front layer's input codes are at most 8 bits wide, flags signed / lo_neg_max only");
+    FQ_REQUIRE((front_bn_scale == nullptr) == (front_bn_shift == nullptr) && front_act >= FQ_ACT_NONE && front_act <= FQ_ACT_RELU6,
+               "fq_pwconv_i8_stat: bad BatchNorm or activation of the front layer");
+    front.codes = front_codes; front.w = front_w; front.bias = front_bias; front.bn_scale = front_bn_scale;
+    front.bn_shift = front_bn_shift; front.act = front_act; front.in_stat = front_in_stat; front.in_thr = front_in_thr;
+    front.epi = (front_bn_scale != nullptr && front_bias == nullptr)
+                    ? (front_act == FQ_ACT_RELU ? kEpiBnRelu : front_act == FQ_ACT_RELU6 ? kEpiBnRelu6 : kEpiRuntime)
+                    : kEpiRuntime;
+    front.levels = act_levels(front_width, front_flags);
+    front.is_signed = (front_flags & FQ_ACT_SIGNED) != 0;
+    front.h = front_h; front.wdt = front_wdt;
+    c.front = &front;
+  }
   c.x = x; c.wcodes = wcodes + cout_pad * cin_pad; c.wscale = wscale; c.wsum = wsum; c.bias = bias; c.y = nullptr;
   c.n = n; c.cin = cin; c.cin_pad = cin_pad; c.cout = cout; c.hw = hw; c.stride = 1; c.h_in = c.w_in = c.w_out = 0;
   c.in_stat = in_stat; c.in_thr = in_thr;
@@ -275,7 +301,8 @@ int fq_pwconv_i8_stat(const float* x, const int8_t* wcodes, const float* wscale,
   // kept (whole 32-channel slabs, one byte per element)
   const double in_elems = (double)n * cin * hw, out_elems = (double)n * cout * hw;
   const double code_bytes = x_codes_out ? 32.0 * (double)((cin + 31) / 32) * n * hw : 0.0;
-  ProfScope prof(FQ_KERNEL_PWCONV, 4.0 * (in_elems + out_elems), c.st, 4.0 * in_elems + code_bytes);
+  // (a front layer: one byte per element of ITS input is read instead of x)
+  ProfScope prof(FQ_KERNEL_PWCONV, 4.0 * (in_elems + out_elems), c.st, (front_codes ? 1.0 : 4.0) * in_elems + code_bytes);
   return pw_stat_launch(c);
 }
 

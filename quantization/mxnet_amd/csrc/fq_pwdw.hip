@@ -483,30 +483,61 @@ struct PwStatGeom {
   FastDiv hw;
 };
 
-template <int KT>
+// FRONT (FEPI >= 0; fq_pwconv_i8_stat with a front layer): x is the output of a stride-1 depthwise 3x3 that was never stored.
+// Its INPUT arrives as planar int8 codes (fq_dwconv3x3's statistic pass kept them), and a workgroup recomputes x band by band:
+//   1  stencil, lane = (channel, four columns) as in fq_dwconv3x3's four-columns form (that is how the planar codes lie: one
+//      dword per lane and row, the horizontal neighbours by DPP from the adjacent lanes - a row of the plane is W / 4 <= 64
+//      lanes, so the plane's edge is the segment's edge and takes 0): dequantise (code * scale, once per element and band),
+//      the row-major fmaf chain, the layer's epilogue (kEpi* as there) - bit for bit what that kernel stores - then THIS
+//      launch's quantiser (the threshold is known: the depthwise pass left its statistic), and the code byte goes to an LDS
+//      band buffer in C16 order [16-channel block][pixel][16].  The transposition planar -> C16 happens here, on LDS bytes;
+//   2  the band buffer is read back as MFMA A fragments (one 16-byte LDS read per lane and 32-pixel tile) and everything from
+//      there on is the kernel's own: the fragment leaves as x_codes_out, max / min of the int32 sums, flush per sample.
+// A band is R <= kFrontRows output rows of one sample (all channels, whole rows): R + 2 input rows are dequantised for it.
+// FSIGNED: the input codes are two's complement bytes (FQ_ACT_SIGNED), else 0 .. 255.
+constexpr int kFrontRows = 8;
+struct PwFrontArgs {
+  const int8_t* codes;               // [n][Cin][H * W]
+  const float *w, *bias, *bn_scale, *bn_shift;
+  const float *in_stat, *in_thr;     // the depthwise layer's input quantiser
+  float levels;
+  int act;
+  int H, W, Q, segs, R, bands;       // Q = W / 4 lanes per row, `segs` rows (channels) per wavefront, R output rows per band
+};
+
+template <int KT, int FEPI = -1, bool FSIGNED = false>
 __global__ __launch_bounds__(kBlock, 3) void pw_stat_kernel(
     const float* __restrict__ x, const int8_t* __restrict__ wfrag, const float* __restrict__ wscale,
     const int* __restrict__ wsum, const float* __restrict__ bias, PwStatGeom g, const float* __restrict__ in_stat, int n,
     const float* __restrict__ in_thr, float levels, int lo_neg, float eps, float* __restrict__ cur_max_out,
     const float* __restrict__ bn_scale, const float* __restrict__ bn_shift, int act, float* __restrict__ stat_out,
-    int8_t* __restrict__ x_codes_out) {
+    int8_t* __restrict__ x_codes_out, PwFrontArgs fa) {
+  constexpr bool FRONT = FEPI >= 0;
+  static_assert(!FRONT || KT == 1, "the front layer is built for one 32-channel slab");
   extern __shared__ __attribute__((aligned(16))) unsigned char pst_smem[];
   v4i* ldsW = reinterpret_cast<v4i*>(pst_smem);                                           // [CT][KT][64]
   int* c_zs = reinterpret_cast<int*>(pst_smem + (size_t)g.CT * KT * 1024);                 // [CT * 32]
   float* c_k = reinterpret_cast<float*>(c_zs + g.CT * 32);                                 // [4][CT * 32]: w scale, bias, BN scale / shift
   int* accs = reinterpret_cast<int*>(c_k + 4 * g.CT * 32);                                 // [4 waves][CT][2][64]
+  float* dwk = reinterpret_cast<float*>(accs + 4 * g.CT * 128);                             // FRONT: [Cin][12] taps, bias, BN scale / shift
+  unsigned char* zbuf = reinterpret_cast<unsigned char*>(dwk + g.Cin * 12);                 // FRONT: [2][R * W][16] band of codes
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int h = lane >> 5, i32 = lane & 31;
   const unsigned HW = (unsigned)g.HW, cols = (unsigned)g.cols;
   const int64_t nwaves = (int64_t)gridDim.x * 4, wid = (int64_t)blockIdx.x * 4 + wave;
-  const int64_t t_begin = g.tiles * wid / nwaves, t_end = g.tiles * (wid + 1) / nwaves;
+  // the wavefront's 32-pixel tiles - FRONT: the WORKGROUP's bands (band b of sample s is number s * bands + b)
+  const int64_t n_bands = FRONT ? (int64_t)(g.cols / g.HW) * fa.bands : 0;
+  const int64_t t_begin = FRONT ? n_bands * blockIdx.x / gridDim.x : g.tiles * wid / nwaves;
+  const int64_t t_end = FRONT ? n_bands * (blockIdx.x + 1) / gridDim.x : g.tiles * (wid + 1) / nwaves;
   const int pl = 16 * ((i32 >> 2) & 1) + 4 * (i32 >> 3) + (i32 & 3);      // tile pixel of this lane's MFMA row
   int* my = accs + (size_t)wave * g.CT * 128;
   constexpr int kSlots = 8;
   __shared__ unsigned k_stat[kSlots];
   if (threadIdx.x < kSlots) k_stat[threadIdx.x] = 0u;
   unsigned s_base;                               // first sample of the workgroup's tile range
-  {
+  if constexpr (FRONT) {
+    s_base = (unsigned)((t_begin < n_bands ? t_begin : n_bands - 1) / fa.bands);
+  } else {
     const int64_t t0 = g.tiles * ((int64_t)blockIdx.x * 4) / nwaves;
     const unsigned j0 = (unsigned)(t0 < g.tiles ? t0 : g.tiles - 1) * 32u;
     s_base = fast_div(j0 < cols ? j0 : cols - 1, g.hw);
@@ -542,9 +573,14 @@ __global__ __launch_bounds__(kBlock, 3) void pw_stat_kernel(
   for (int b2 = 0; b2 < NB; ++b2)
 #pragma unroll
     for (int i = 0; i < 16; ++i) raw[b2][i] = 0.0f;
+  if constexpr (!FRONT) {
 #pragma unroll
-  for (int qq = 0; qq < NB - 1; ++qq) issue(t_begin + qq / KT, qq % KT, raw[qq]);
+    for (int qq = 0; qq < NB - 1; ++qq) issue(t_begin + qq / KT, qq % KT, raw[qq]);
+  }
   FQ_PIN();
+  // FRONT: the multiply-back scale of the depthwise layer's input quantiser (make_qparams: max_ / levels)
+  float fscale = 0.0f;
+  if constexpr (FRONT) fscale = input_threshold(fa.in_stat, n, fa.in_thr, nullptr, false) / fa.levels;
   const float max_ = input_threshold(in_stat, n, in_thr, cur_max_out, blockIdx.x == 0);
   const QParams q = make_qparams(max_, levels, lo_neg != 0, eps);
   const int ubias = 128 - g.zoff;
@@ -566,6 +602,14 @@ __global__ __launch_bounds__(kBlock, 3) void pw_stat_kernel(
     c_k[2 * nchs + i] = (okc && bn_scale != nullptr) ? bn_scale[i] : 1.0f;
     c_k[3 * nchs + i] = (okc && bn_scale != nullptr) ? bn_shift[i] : 0.0f;
   }
+  if constexpr (FRONT)
+    for (int i = threadIdx.x; i < g.Cin; i += kBlock) {
+#pragma unroll
+      for (int t = 0; t < 9; ++t) dwk[i * 12 + t] = fa.w[i * 9 + t];
+      dwk[i * 12 + 9] = fa.bias != nullptr ? fa.bias[i] : 0.0f;
+      dwk[i * 12 + 10] = fa.bn_scale != nullptr ? fa.bn_scale[i] : 1.0f;
+      dwk[i * 12 + 11] = fa.bn_scale != nullptr ? fa.bn_shift[i] : 0.0f;
+    }
   auto reset = [&]() __attribute__((always_inline)) {
     for (int ct = 0; ct < g.CT; ++ct) {
       my[ct * 128 + lane] = INT_MIN;
@@ -672,7 +716,7 @@ __global__ __launch_bounds__(kBlock, 3) void pw_stat_kernel(
       atomicMin(&my[ct * 128 + 64 + lane], lo);
     }
   };
-  unsigned cur = fast_div((unsigned)((t_begin < g.tiles ? t_begin : g.tiles - 1) * 32), g.hw);
+  unsigned cur = FRONT ? s_base : fast_div((unsigned)((t_begin < g.tiles ? t_begin : g.tiles - 1) * 32), g.hw);
   auto run_tile = [&](int64_t t, auto ph_c, auto nn_c) __attribute__((always_inline)) {
     constexpr int PH = decltype(ph_c)::value;                 // the tile's first slab sits in buffer (PH * KT) % NB
     const Pix px = pix_of(t);
@@ -715,8 +759,110 @@ __global__ __launch_bounds__(kBlock, 3) void pw_stat_kernel(
       if (U > 3 && t + 3 < t_end) run_tile(t + 3, integral_constant<int, 3 % U>{}, nn_c);
     }
   };
-  if (fq_nonneg(q) && fqx.ok) run_all(std::true_type{});
-  else run_all(std::false_type{});
+  // FRONT: band by band - recompute the depthwise values into the band buffer as codes, then the tiles of the band
+  auto run_front = [&](auto nn_c) __attribute__((always_inline)) {
+    constexpr bool NN = decltype(nn_c)::value;
+    constexpr int FE = FRONT ? FEPI : kEpiRuntime;
+    const int Q = fa.Q, W = fa.W, H = fa.H, NP = fa.R * fa.W;
+    const int seg = lane / Q, pos = lane - seg * Q;
+    const bool first = pos == 0, last = pos == Q - 1;
+    const bool has_fb = fa.bias != nullptr, has_fbn = fa.bn_scale != nullptr;
+    QParams qc = q;                               // compile-time epilogue, clip range from 0: ReLU / ReLU6 and the clip are one median
+    if (NN && FE != kEpiRuntime) qc.hi = FE == kEpiBnRelu6 ? fminf(q.hi, 6.0f) : q.hi;
+    const unsigned* xc32 = reinterpret_cast<const unsigned*>(fa.codes);
+    const int z4 = stored_zero4(ubias);
+    const v4i zero_frag = (v4i){z4, z4, z4, z4};
+    auto deq = [&](unsigned wd, int b) __attribute__((always_inline)) {
+      const int code = FSIGNED ? (int)(int8_t)(wd >> (8 * b)) : (int)((wd >> (8 * b)) & 255u);
+      return (float)code * fscale;
+    };
+    for (int64_t bt = t_begin; bt < t_end; ++bt) {
+      const unsigned smp = (unsigned)(bt / fa.bands);
+      const int r0 = (int)(bt - (int64_t)smp * fa.bands) * fa.R;
+      const int Rb = H - r0 < fa.R ? H - r0 : fa.R;
+      if (smp != cur) {
+        flush(cur);
+        cur = smp;
+      }
+      // ---- 1: the depthwise layer on rows r0 - 1 .. r0 + Rb of `segs` channels per wavefront and turn ----
+      for (int c0 = 0; c0 < g.Cin; c0 += 4 * fa.segs) {
+        const int c = c0 + wave * fa.segs + seg;
+        const bool c_ok = seg < fa.segs && c < g.Cin;
+        const int cc = c_ok ? c : 0;
+        const float* kc = dwk + cc * 12;
+        const float w00 = kc[0], w01 = kc[1], w02 = kc[2], w10 = kc[3], w11 = kc[4], w12 = kc[5], w20 = kc[6], w21 = kc[7],
+                    w22 = kc[8], bch = kc[9], bsc = kc[10], bsh = kc[11];
+        const unsigned* src = xc32 + ((int64_t)(smp * (unsigned)g.Cin + (unsigned)cc) * H) * Q + pos;
+        unsigned raw_c[kFrontRows + 2];           // (unconditional loads from clamped rows, masked: a row outside the plane is zero codes)
+#pragma unroll
+        for (int k = 0; k < kFrontRows + 2; ++k) {
+          const int t = r0 - 1 + k, tc = t < 0 ? 0 : (t > H - 1 ? H - 1 : t);
+          raw_c[k] = src[tc * Q] & ((t >= 0 && t < H) ? 0xFFFFFFFFu : 0u);
+        }
+        // this launch's code of one depthwise sum (the stored byte of the C16 layout)
+        auto zcode = [&](float acc) __attribute__((always_inline)) {
+          if constexpr (NN) {
+            const float v = FE == kEpiRuntime ? dw_finish<kEpiRuntime>(acc, has_fb, bch, has_fbn, bsc, bsh, fa.act)
+                                              : dw_finish<FE, false>(acc, false, 0.0f, true, bsc, bsh, 0);
+            int r;
+            const float Qv = fast_quot(fq_clip(v, qc), fqx);
+            asm("v_cvt_rpi_i32_f32 %0, %1" : "=v"(r) : "v"(Qv));
+            return (unsigned)r ^ (nn_xor & 255u);
+          } else {
+            const float v = dw_finish<FE>(acc, has_fb, bch, has_fbn, bsc, bsh, fa.act);
+            return (unsigned)(fq_code_int(v, q) + ubias) ^ 0x80u;
+          }
+        };
+        float a[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, b[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int k = 0; k < kFrontRows + 2; ++k) {
+          if (k <= Rb + 1) {                      // (the same for the whole workgroup)
+            float cv[6];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) cv[j + 1] = deq(raw_c[k], j);
+            const float lp = lane_prev(cv[4]), ln = lane_next(cv[1]);      // (taken by every lane, masked afterwards)
+            cv[0] = first ? 0.0f : lp;
+            cv[5] = last ? 0.0f : ln;
+            if (k >= 2) {                         // input row r0 + k - 1 closes output row r0 + k - 2
+              unsigned char* dst = zbuf + ((size_t)((cc >> 4) * NP + (k - 2) * W + 4 * pos) * 16 + (cc & 15));
+#pragma unroll
+              for (int j = 0; j < 4; ++j) {
+                const unsigned code = zcode(dw_taps(w00, w01, w02, w10, w11, w12, w20, w21, w22, a[j], a[j + 1], a[j + 2], b[j],
+                                                    b[j + 1], b[j + 2], cv[j], cv[j + 1], cv[j + 2]));
+                if (c_ok) dst[16 * j] = (unsigned char)code;
+              }
+            }
+#pragma unroll
+            for (int j = 0; j < 6; ++j) {
+              a[j] = b[j];
+              b[j] = cv[j];
+            }
+          }
+        }
+      }
+      __syncthreads();
+      // ---- 2: the band's pixels as 32-pixel tiles (the last one may be short: its lanes past the band repeat the last pixel) ----
+      const int npix = Rb * W, ntile = (npix + 31) >> 5;
+      for (int tl = wave; tl < ntile; tl += 4) {
+        int pp = tl * 32 + pl;
+        pp = pp < npix ? pp : npix - 1;
+        v4i f = *reinterpret_cast<const v4i*>(zbuf + ((size_t)(h * NP + pp) << 4));
+        if (g.Cin <= 16 && h == 1) f = zero_frag;            // (the half-slab past Cin: the code of 0)
+        if (wr_codes) buf_st_v4i(rcodes, ((smp * 2u + (unsigned)h) * HW + (unsigned)(r0 * W + pp)) * 16u, f);
+        afrag[0] = f;
+        const int valid = npix - tl * 32;
+        reduce_tile(0, valid < 32 ? valid : 32);
+      }
+      __syncthreads();                            // (the next band overwrites the buffer)
+    }
+  };
+  if constexpr (FRONT) {
+    if (fq_nonneg(q) && fqx.ok) run_front(std::true_type{});
+    else run_front(std::false_type{});
+  } else {
+    if (fq_nonneg(q) && fqx.ok) run_all(std::true_type{});
+    else run_all(std::false_type{});
+  }
   if (t_begin < t_end) flush(cur);
   __syncthreads();
   if (threadIdx.x < kSlots && k_stat[threadIdx.x] != 0u && s_base + threadIdx.x < cols / HW)
@@ -804,20 +950,48 @@ bool pw_stat_shape_ok(int64_t n, int64_t cin, int64_t cout, int64_t hw) {
   return lds <= 120 * 1024 && n * cin * hw * 4 < (1ll << 32);
 }
 
+// rows per band of the front-layer mode: as many as kFrontRows and 32 KiB of band buffer allow, whole 32-pixel tiles preferred
+static int pw_front_rows(int64_t h, int64_t w) {
+  int r = (int)(32768 / (32 * w));
+  r = r > kFrontRows ? kFrontRows : r;
+  r = r > h ? (int)h : r;
+  for (int k = r; k >= 1 && 2 * k > r; --k)
+    if ((k * w) % 32 == 0) return k;
+  return r;
+}
+
+bool pw_stat_front_shape_ok(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w) {
+  if (h < 1 || w < 4 || w % 4 != 0 || w / 4 > 64 || !(cin == 16 || cin == 32) || !pw_stat_shape_ok(n, cin, cout, h * w)) return false;
+  // (the depthwise statistic pass in front must take the plane too: fq_dwconv3x3 without y)
+  return pw_front_rows(h, w) >= 1 && n * cin * ((w / 4 + 61) / 62) < (1ll << 31) - 1024;
+}
+
 int pw_stat_launch(const PwCall& c) {
   const int kt = (int)((c.cin + 31) / 32), ct = (int)((c.cout + 31) / 32);
-  const size_t lds = (size_t)ct * kt * 1024 + 5 * (size_t)ct * 32 * 4 + 4 * (size_t)ct * 128 * 4;
+  size_t lds = (size_t)ct * kt * 1024 + 5 * (size_t)ct * 32 * 4 + 4 * (size_t)ct * 128 * 4;
+  PwFrontArgs fa = {};
+  if (c.front != nullptr) {
+    const PwFront& f = *c.front;
+    fa.codes = static_cast<const int8_t*>(f.codes);
+    fa.w = f.w; fa.bias = f.bias; fa.bn_scale = f.bn_scale; fa.bn_shift = f.bn_shift;
+    fa.in_stat = f.in_stat; fa.in_thr = f.in_thr; fa.levels = f.levels; fa.act = f.act;
+    fa.H = (int)f.h; fa.W = (int)f.wdt; fa.Q = fa.W / 4; fa.segs = 64 / fa.Q;
+    fa.R = pw_front_rows(f.h, f.wdt);
+    fa.bands = (fa.H + fa.R - 1) / fa.R;
+    lds += (size_t)c.cin * 12 * 4 + (size_t)32 * fa.R * fa.W;
+  }
   PwStatGeom g;
   g.Cin = (int)c.cin; g.KTS = (int)(c.cin_pad / 32); g.Cout = (int)c.cout; g.CT = ct; g.HW = (int)c.hw;
   g.cols = c.n * c.hw; g.tiles = (g.cols + 31) / 32; g.zoff = c.zoff;
   g.hw = fast_div_for((unsigned)c.hw);
   if (int rc = pw_zero_stat(c)) return rc;
   int per_cu = (int)((160 * 1024) / (lds + 1024));
-  per_cu = per_cu > 3 ? 3 : per_cu;
+  const int wg_cap = c.front != nullptr ? 4 : 3;        // (by registers: the front-layer instantiations fit four wavefronts per SIMD)
+  per_cu = per_cu > wg_cap ? wg_cap : per_cu;
   static const int wg_env = env_int("FQ_PWSTAT_WG_PER_CU", 0);
   if (wg_env > 0) per_cu = wg_env;
   int64_t grid = (int64_t)num_cu() * per_cu;
-  const int64_t need = (g.tiles + 3) / 4;
+  const int64_t need = c.front != nullptr ? c.n * fa.bands : (g.tiles + 3) / 4;
   if (grid > need) grid = need;
   static const int table_env = env_int("FQ_PWSTAT_TABLE", -1);
   g.table = table_env >= 0 ? table_env : (g.tiles < grid * 4 * 10 ? 1 : 0);
@@ -828,12 +1002,35 @@ int pw_stat_launch(const PwCall& c) {
     FQ_REQUIRE(attr_ok, "fq_pwconv_i8_stat: cannot raise the dynamic LDS limit");                                          \
     hipLaunchKernelGGL((pw_stat_kernel<KT_>), dim3((unsigned)grid), dim3(kBlock), lds, c.st, c.x, c.wcodes, c.wscale,       \
                        (const int*)c.wsum, c.bias, g, c.in_stat, (int)c.n, c.in_thr, c.levels, c.lo_neg, kEps,              \
-                       c.out_current_max, c.bn_scale, c.bn_shift, c.act, c.stat_out, (int8_t*)c.x_codes_out);              \
+                       c.out_current_max, c.bn_scale, c.bn_shift, c.act, c.stat_out, (int8_t*)c.x_codes_out, fa);          \
   } break;
-  switch (kt) {
-    FQ_PST_GO(1) FQ_PST_GO(2) FQ_PST_GO(4) FQ_PST_GO(8)
-    default: return fail(FQ_ERR_INVALID, "fq_pwconv_i8_stat: K / 32 = %d is not instantiated", kt);
+  // front layer: the depthwise epilogue at compile time where fq_dwconv3x3 has it so, the signedness of its input codes
+#define FQ_PST_FRONT(EPI_, SG_)                                                                                            \
+  {                                                                                                                        \
+    static const bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&pw_stat_kernel<1, EPI_, SG_>),          \
+                                                    hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024) == hipSuccess; \
+    FQ_REQUIRE(attr_ok, "fq_pwconv_i8_stat: cannot raise the dynamic LDS limit");                                          \
+    hipLaunchKernelGGL((pw_stat_kernel<1, EPI_, SG_>), dim3((unsigned)grid), dim3(kBlock), lds, c.st, c.x, c.wcodes,       \
+                       c.wscale, (const int*)c.wsum, c.bias, g, c.in_stat, (int)c.n, c.in_thr, c.levels, c.lo_neg, kEps,   \
+                       c.out_current_max, c.bn_scale, c.bn_shift, c.act, c.stat_out, (int8_t*)c.x_codes_out, fa);          \
   }
+#define FQ_PST_FRONT_S(EPI_)                                                                                               \
+  {                                                                                                                        \
+    if (c.front->is_signed) FQ_PST_FRONT(EPI_, true) else FQ_PST_FRONT(EPI_, false)                                        \
+  }
+  if (c.front != nullptr) {
+    FQ_REQUIRE(kt == 1, "fq_pwconv_i8_stat: a front layer needs cin <= 32");
+    if (c.front->epi == kEpiBnRelu) FQ_PST_FRONT_S(kEpiBnRelu)
+    else if (c.front->epi == kEpiBnRelu6) FQ_PST_FRONT_S(kEpiBnRelu6)
+    else FQ_PST_FRONT_S(kEpiRuntime)
+  } else {
+    switch (kt) {
+      FQ_PST_GO(1) FQ_PST_GO(2) FQ_PST_GO(4) FQ_PST_GO(8)
+      default: return fail(FQ_ERR_INVALID, "fq_pwconv_i8_stat: K / 32 = %d is not instantiated", kt);
+    }
+  }
+#undef FQ_PST_FRONT_S
+#undef FQ_PST_FRONT
 #undef FQ_PST_GO
   FQ_LAUNCH_CHECK();
   return FQ_OK;

@@ -592,10 +592,32 @@ def stem_conv_supported(cin, cout, kernel, stride, pad):
                                          (cout == 64 and k == (7, 7) and p == (3, 3)))
 
 
+def front_codes_shape(xshape):
+    """Shape of the int8 buffer in which `dwconv3x3(store=False, x_codes_out=)` keeps the codes of its (N, C, H, W) input for
+    `pwconv_i8_stat(front=)`: planar, one byte per element (include/fakequant.h at fq_dwconv3x3)."""
+    n, c, h, w = (int(v) for v in xshape)
+    return (n, c, h * w)
+
+
+def _check_front_codes(t, name, xshape, device):
+    _check(t, name, torch.int8)
+    if len(xshape) != 4 or tuple(t.shape) != front_codes_shape(xshape):
+        raise ValueError("%s must be int8 %s for a depthwise input %s; got %s"
+                         % (name, front_codes_shape(xshape) if len(xshape) == 4 else "(4-d x)", tuple(xshape), tuple(t.shape)))
+    if t.device != device:
+        raise ValueError("%s lives on %s, x on %s" % (name, t.device, device))
+    if t.data_ptr() % 16:
+        raise ValueError("%s must be 16-byte aligned" % name)
+    return t
+
+
 def dwconv3x3(x, w, bias=None, stride=1, in_stat=None, in_thr=None, width=8, flags=0, cur_out=None, bn_scale=None,
-              bn_shift=None, act=None, want_stat=True):
+              bn_shift=None, act=None, want_stat=True, store=True, x_codes_out=None):
     """Depthwise 3x3 (pad 1) with optional quantise-on-load of x (in_stat: online, in_thr: offline) and fused
-    BatchNorm/activation/per-sample-statistic epilogue.  Returns (y, stat (N,) or None)."""
+    BatchNorm/activation/per-sample-statistic epilogue.  Returns (y, stat (N,) or None).
+    `store=False`: the statistic pass of the layer - the output is computed, its per-sample maxima are taken and nothing of it
+    is stored; returns (None, stat).  `x_codes_out` (int8, `front_codes_shape(x.shape)`, with `store=False` only): also keep the
+    codes the quantise-on-load made of x, for `pwconv_i8_stat(front=)`."""
     _check(x, "x")
     _check(w, "w")
     if x.dim() != 4 or w.dim() != 4 or tuple(w.shape[1:]) != (1, 3, 3) or w.shape[0] != x.shape[1]:
@@ -606,11 +628,17 @@ def dwconv3x3(x, w, bias=None, stride=1, in_stat=None, in_thr=None, width=8, fla
             _check(t, name)
     n, c, h, wd = x.shape
     ho, wo = (h - 1) // stride + 1, (wd - 1) // stride + 1
-    y = torch.empty((n, c, ho, wo), dtype=torch.float32, device=x.device)
+    if not store and not want_stat:
+        raise ValueError("dwconv3x3(store=False) leaves nothing but the statistic: want_stat must be set")
+    if x_codes_out is not None:
+        if store:
+            raise ValueError("dwconv3x3 keeps the codes of x only in its statistic pass (store=False)")
+        _check_front_codes(x_codes_out, "x_codes_out", tuple(x.shape), x.device)
+    y = torch.empty((n, c, ho, wo), dtype=torch.float32, device=x.device) if store else None
     stat, zflag = _stat_target(n, x.device, want_stat)
     check_call(_lib_().fq_dwconv3x3(_ptr(x), _ptr(w), _ptr(bias), _ptr(y), n, c, h, wd, int(stride), _ptr(in_stat),
                                     _ptr(in_thr), int(width), int(flags), _ptr(cur_out), _ptr(bn_scale),
-                                    _ptr(bn_shift), _ACTS[act] | zflag, _ptr(stat), _stream(x)))
+                                    _ptr(bn_shift), _ACTS[act] | zflag, _ptr(stat), _stream(x), _ptr(x_codes_out)))
     return y, stat
 
 
@@ -649,8 +677,15 @@ def pwdw_supported(xshape, cout, stride):
     fq_pwconv_i8_stat and fq_pwdw_fused take."""
     n, cin, h, w = (int(v) for v in xshape)
     lib = _lib_()
-    return bool(lib.fq_pwconv_i8_stat_supported(n, cin, int(cout), h * w)) and \
+    return bool(lib.fq_pwconv_i8_stat_supported(n, cin, int(cout), h * w, 0, 0)) and \
         bool(lib.fq_pwdw_fused_supported(n, cin, int(cout), h, w, int(stride)))
+
+
+def pwconv_front_supported(xshape, cout):
+    """True when `pwconv_i8_stat(front=)` takes a 1x1 to `cout` channels whose (N, Cin, H, W) input is the output of a
+    stride-1 depthwise 3x3 recomputed in front of it - and `dwconv3x3(store=False, x_codes_out=)` that depthwise layer."""
+    n, cin, h, w = (int(v) for v in xshape)
+    return bool(_lib_().fq_pwconv_i8_stat_supported(n, cin, int(cout), h * w, h, w))
 
 
 def pair_codes_shape(xshape):
@@ -671,9 +706,13 @@ def _check_pair_codes(t, name, x):
 
 
 def pwconv_i8_stat(x, wcodes, wscale, wsum, bias=None, in_stat=None, in_thr=None, width=8, flags=0, cur_out=None,
-                   bn_scale=None, bn_shift=None, act=None, x_codes_out=None):
+                   bn_scale=None, bn_shift=None, act=None, x_codes_out=None, front=None):
     """The statistic-only pass of a fused 1x1 convolution (fq_pwconv_i8_stat): what `pwconv_i8` computes without storing it.
     `x_codes_out` (int8, `pair_codes_shape(x.shape)`): also keep the codes of x it multiplies with, for `pwdw_fused(x_codes=)`.
+    `front`: x is the output of a stride-1 depthwise 3x3 that was not stored - the launch recomputes it from the codes of that
+    layer's input and never reads x (only its shape counts).  A dict of the depthwise call: `x_codes` (what
+    `dwconv3x3(store=False, x_codes_out=)` kept), `w`, `bias`, `bn_scale`, `bn_shift`, `act`, and its input quantiser `in_stat`
+    / `in_thr`, `width`, `flags`; in_stat / in_thr of this call are the statistic / threshold of the depthwise OUTPUT.
     Returns the per-sample maxima max|y[n]| (N,)."""
     _check(x, "x")
     _check(wcodes, "wcodes", torch.int8)
@@ -692,12 +731,31 @@ def pwconv_i8_stat(x, wcodes, wscale, wsum, bias=None, in_stat=None, in_thr=None
         cur_out = torch.empty(1, dtype=torch.float32, device=x.device)
     if x_codes_out is not None:
         _check_pair_codes(x_codes_out, "x_codes_out", x)
+    f_args = (_ptr(None),) * 5 + (0, _ptr(None), _ptr(None), 0, 0, 0, 0)
+    if front is not None:
+        unknown = set(front) - {"x_codes", "w", "bias", "bn_scale", "bn_shift", "act", "in_stat", "in_thr", "width", "flags"}
+        if unknown or x.dim() != 4:
+            raise ValueError("pwconv_i8_stat(front=) wants x (N, Cin, H, W) and the keys of a depthwise call; got %s, %s"
+                             % (tuple(x.shape), sorted(unknown)))
+        fw = _check(front["w"], "front['w']")
+        if tuple(fw.shape) != (cin, 1, 3, 3):
+            raise ValueError("front['w'] must be (%d,1,3,3); got %s" % (cin, tuple(fw.shape)))
+        _check_front_codes(front["x_codes"], "front['x_codes']", tuple(x.shape), x.device)
+        for name in ("bias", "bn_scale", "bn_shift", "in_stat", "in_thr"):
+            if front.get(name) is not None:
+                _check(front[name], "front['%s']" % name)
+        if not pwconv_front_supported(x.shape, cout):
+            raise ValueError("pwconv_i8_stat(front=) does not take x %s -> %d channels: see pwconv_front_supported"
+                             % (tuple(x.shape), cout))
+        f_args = (_ptr(front["x_codes"]), _ptr(fw), _ptr(front.get("bias")), _ptr(front.get("bn_scale")),
+                  _ptr(front.get("bn_shift")), _ACTS[front.get("act")], _ptr(front.get("in_stat")), _ptr(front.get("in_thr")),
+                  int(front.get("width", 8)), int(front.get("flags", 0)), int(x.shape[2]), int(x.shape[3]))
     stat, zflag = _stat_target(n, x.device, True)
     hw = x.numel() // (n * cin)
     check_call(_lib_().fq_pwconv_i8_stat(_ptr(x), _ptr(wcodes), _ptr(wscale), _ptr(wsum), _ptr(bias), n, cin, cin_pad,
                                          wcodes.shape[0], cout, hw, _ptr(in_stat), _ptr(in_thr), int(width), int(flags), _ptr(cur_out),
                                          _ptr(bn_scale), _ptr(bn_shift), _ACTS[act] | zflag, _ptr(stat), _ptr(x_codes_out),
-                                         _stream(x)))
+                                         _stream(x), *f_args))
     return stat
 
 

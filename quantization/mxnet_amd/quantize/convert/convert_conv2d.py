@@ -52,7 +52,8 @@ class _InputView(object):
     changes no result), and the multi-GPU calibration hooks of dist.py."""
 
     def __init__(self, block, x):
-        self.t = contiguous(x._t)
+        # (a deferred input - the placeholder of a tensor that was not stored - has a shape, a device and a statistic only)
+        self.t = x._t if getattr(x, "_fq_deferred", None) is not None else contiguous(x._t)
         self.n = self.t.shape[0]
         self.cur, self.side = scalar_slot(block, self.t)
         rows = getattr(block, "_fq_stat_ws", None)
@@ -167,11 +168,58 @@ def depthwise_fused(block, x, weight_q, bias, plan):
             return out
         x = NDArray(codes16_to_fake_quant(c16_in))      # (the producer's hand-over cannot be honoured after all)
         plan = {}
-    y, stat = ops.dwconv3x3(contiguous(x._t), contiguous(weight_q._t), None if bias is None else bias._t,
-                            stride=block._kwargs["stride"][0], bn_scale=scale, bn_shift=shift, act=fz["act"], **plan)
+    call = dict(x=contiguous(x._t), w=contiguous(weight_q._t), bias=None if bias is None else bias._t,
+                stride=block._kwargs["stride"][0], bn_scale=scale, bn_shift=shift, act=fz["act"], **plan)
+    front = front_target(block, fz, x, plan) if c16_in is None else None
+    if front is not None:
+        # statistic only, and the codes of the input: the 1x1 convolution behind recomputes the values inside its own statistic
+        # pass (a fresh code buffer of the current stream per forward, like the pair's)
+        xcodes = torch.empty(ops.front_codes_shape(call["x"].shape), dtype=torch.int8, device=call["x"].device)
+        stat = _dwconv3x3(call, store=False, x_codes_out=xcodes)[1]
+        out = NDArray(_placeholder(tuple(call["x"].shape), call["x"].device))
+        out._fq_stat = stat
+        out._fq_deferred = dict(kind="front", consumer=front, call=call, x_codes=xcodes)
+        return out
+    y, stat = _dwconv3x3(call)
     out = NDArray(y)
     out._fq_stat = stat
     return out
+
+
+def _dwconv3x3(call, **more):
+    """ops.dwconv3x3 with the arguments `depthwise_fused` put together (kept in a deferred record to run the storing launch later)."""
+    kw = dict(call)
+    return ops.dwconv3x3(kw.pop("x"), **kw, **more)
+
+
+def front_target(block, fz, x, plan):
+    """The fused 1x1 convolution behind this depthwise block when the block may run as a statistic pass that keeps its input's
+    codes (fq_dwconv3x3 without y) and leave its values to that convolution's own statistic pass (fq_pwconv_i8_stat with a front
+    layer; quantize/fuse.py links `front_pw`): the 1x1 is the first half of a recompute pair that is taken in this very forward
+    (`recompute_target`), the forward is one of several batches in flight (`fuse.PAIR_FRONT`: where the saved bytes pay), this
+    block quantises its input ONLINE with stride 1 and without a folded fake-BN, and nothing observes
+    the tensor between the two (no hooks, no KL collection, no multi-GPU exchange of the 1x1's statistic).  Returns the 1x1 block
+    or None."""
+    from .. import fuse as _fuse
+    nxt = fz.get("front_pw")
+    # (FQ_PWDW_FRONT: 1 - among batches in flight, where it pays; 2 - in every forward)
+    if nxt is None or not _fuse.PAIR_CODES or not (int(_fuse.PAIR_FRONT) >= 2 or (_fuse.PAIR_FRONT and ops.in_flight())) \
+            or block._kwargs["stride"] != (1, 1) \
+            or block.quantize_args.fake_bn or "in_stat" not in plan or "in_thr" in plan or plan["width"] > 8:
+        return None
+    pz, a = nxt._fq_pw_fused, nxt.quantize_args
+    if not (nxt.enable_quantize and a.quantize_input and nxt.quantize_input and not nxt.quantize_input_offline
+            and a.in_width <= 8 and a.wt_width <= 8 and not getattr(nxt, "_fq_no_int8", False) and not a.fake_bn
+            and getattr(nxt, "_fq_global_stat", None) is None and getattr(nxt, "_fq_residual", None) is None):
+        return None
+    if any(_hooked(b) for b in (block, fz.get("bn"), fz.get("act_block"))):
+        return None
+    # the pair behind: the same question the 1x1 block will ask itself, with the only things it looks at in its input and plan
+    if recompute_target(nxt, pz, x, dict(in_stat=None), None) is None or handover_target(nxt) is not None:
+        return None
+    if not ops.pwconv_front_supported(tuple(x._t.shape), nxt._kwargs["num_filter"]):
+        return None
+    return nxt
 
 
 def _weight_rows_per_scale(block, args):
@@ -445,7 +493,13 @@ def _materialise(x):
     """The tensor a deferred NDArray stands for, computed after all (its consumer turned out not to be the linked depthwise
     block in a state that takes it): the storing launch with the arguments the statistic pass had."""
     d = x._fq_deferred
-    y, stat = ops.pwconv_i8(d["x"], *d["codes"], d["bias"], bn_scale=d["bn"][0], bn_shift=d["bn"][1], act=d["act"], **d["plan"])
+    if d.get("kind") == "front":                         # (a depthwise block in front of a pair: its storing launch)
+        y, stat = _dwconv3x3(d["call"])
+    else:
+        # (its own input may be a tensor that was not stored either: the depthwise block in front, `front`)
+        src = d["x"] if d.get("front") is None else _dwconv3x3(d["front"]["call"])[0]
+        y, stat = ops.pwconv_i8(src, *d["codes"], d["bias"], bn_scale=d["bn"][0], bn_shift=d["bn"][1], act=d["act"],
+                                **d["plan"])
     out = NDArray(y)
     out._fq_stat = stat
     return out
@@ -507,6 +561,12 @@ def pointwise_fused(block, F, x, weight_raw, weight_q, bias, plan, weights_quant
         and not getattr(block, "_fq_no_int8", False)
     held = _pointwise_weight_codes(block, args, weight_raw, weight_q) if on_codes else None
     on_codes = held is not None
+    front = getattr(x, "_fq_deferred", None)             # (only the record of a depthwise block in front reaches this function)
+    if front is not None:
+        from .. import fuse as _fuse
+        if not (on_codes and fz.get("kind") == "1x1" and _fuse.PAIR_CODES and getattr(block, "_fq_residual", None) is None
+                and handover_target(block) is None and recompute_target(block, fz, x, plan, None) is not None):
+            x, front = _materialise(x), None             # (the pair is not taken after all: the depthwise block's storing launch)
     res0 = getattr(block, "_fq_residual", None)
     if res0 is not None and res0.get("short") is not None and not (on_codes and fz.get("kind") == "1x1"):
         res0["t"], res0["short"] = materialise_shortcut_record(res0["short"]), None      # (no integer path here: the tensor after all)
@@ -529,7 +589,12 @@ def pointwise_fused(block, F, x, weight_raw, weight_q, bias, plan, weights_quant
         plan, c16_in = {}, None
     if on_codes:
         codes, scales, rowsum = held
-        x_arg = c16_in if c16_in is not None else contiguous(x._t)
+        if front is not None:
+            # (neither launch of the pair reads the fp32 tensor - the statistic pass recomputes it, the fused launch loads the
+            # codes that pass leaves - but both are told its shape by it: an allocation nothing is written to or read from)
+            x_arg = torch.empty(tuple(x._t.shape), dtype=torch.float32, device=x._t.device)
+        else:
+            x_arg = c16_in if c16_in is not None else contiguous(x._t)
         if fz.get("kind") == "3x3":
             out_codes = None if fz.get("sliced") else handover_target(block)
             y, stat = ops.conv3x3_i8(x_arg, codes, scales, rowsum, None if bias is None else bias._t,
@@ -630,14 +695,20 @@ def pointwise_fused(block, F, x, weight_raw, weight_q, bias, plan, weights_quant
                 # pair and forward (as the fused launch's output: safe with batches in flight and under graph capture)
                 xcodes = torch.empty(ops.pair_codes_shape(x_arg.shape), dtype=torch.int8, device=x_arg.device) \
                     if _fuse.PAIR_CODES else None
+                fkw = {}
+                if front is not None:
+                    c_ = front["call"]
+                    fkw = dict(front=dict(x_codes=front["x_codes"], w=c_["w"], bias=c_["bias"], bn_scale=c_["bn_scale"],
+                                          bn_shift=c_["bn_shift"], act=c_["act"], in_stat=c_["in_stat"], width=c_["width"],
+                                          flags=c_["flags"]))
                 stat = ops.pwconv_i8_stat(x_arg, codes, scales, rowsum, b_, bn_scale=scale, bn_shift=shift, act=fz["act"],
-                                          x_codes_out=xcodes, **plan)
+                                          x_codes_out=xcodes, **fkw, **plan)
                 xs = tuple(x_arg.shape)
                 res_ = NDArray(_placeholder((xs[0], block._kwargs["num_filter"], xs[2], xs[3]), x_arg.device))
                 res_._fq_stat = stat
                 res_._fq_deferred = dict(x=x_arg, codes=(codes, scales, rowsum), bias=b_, bn=(scale, shift), act=fz["act"],
                                          plan=dict(in_stat=plan["in_stat"], width=plan["width"], flags=plan["flags"],
-                                                   cur_out=plan.get("cur_out")), consumer=pair, x_codes=xcodes)
+                                                   cur_out=plan.get("cur_out")), consumer=pair, x_codes=xcodes, front=front)
                 return res_
             out = ops.pwconv_i8(x_arg, codes, scales, rowsum, None if bias is None else bias._t,
                                 bn_scale=scale, bn_shift=shift,
@@ -769,8 +840,14 @@ def _quantised_conv(self, F, x, weight, bias=None, input_max=None,
         raise RuntimeError("a subsampled trunk (fq_pwconv_i8_sub2) reached a block that is not one of its two readers")
 
     deferred = getattr(x, "_fq_deferred", None)
-    if deferred is not None and not (deferred["consumer"] is self and dw is not None and self.enable_quantize
-                                     and args.quantize_input and self.quantize_input and not self.quantize_input_offline):
+    online = self.enable_quantize and args.quantize_input and self.quantize_input and not self.quantize_input_offline
+    if deferred is not None and deferred.get("kind") == "front":
+        # the output of a depthwise block that ran as a statistic pass: this 1x1 block, online and taken over, asks
+        # `pointwise_fused` to recompute it - which materialises it should the pair not be taken after all
+        if not (deferred["consumer"] is self and pw is not None and online and getattr(self, "_fq_global_stat", None) is None):
+            x = _materialise(x)
+        deferred = None
+    if deferred is not None and not (deferred["consumer"] is self and dw is not None and online):
         x, deferred = _materialise(x), None              # (not the consumer the pair was made for: the stored tensor after all)
 
     weight_q = weight

@@ -169,6 +169,13 @@ RECOMPUTE_MAX_CIN = int(_os.environ.get("FQ_RECOMPUTE_MAX_CIN", "128"))      # (
 # FQ_PWDW_CODES=0: the recomputing launch reads the fp32 input again and quantises it again instead of loading the codes the
 # statistic pass kept for it (A/B; results identical either way)
 PAIR_CODES = _os.environ.get("FQ_PWDW_CODES", "1") != "0"
+# FQ_PWDW_FRONT: a stride-1 depthwise 3x3 in FRONT of a recompute pair runs as a statistic pass that keeps its input's codes, and
+# the pair's statistic pass recomputes the depthwise values from them (convert_conv2d.front_target; results identical either way).
+# 1 (default): in forwards declared as batches in flight (`ops.batches_in_flight()`: bench.py, the CLI's evaluation) - there the
+# step follows its bytes and the change pays (+7 %), while one batch alone on the GPU only breaks even (MobileNet1.0) or loses
+# (MobileNet0.5): DESIGN 3.7; an ordinary forward - calibration, a single evaluation - keeps the stored tensor, and every launch's
+# fp32 input stays observable there.  2: in every forward (A/B of one batch at a time).  0: never.
+PAIR_FRONT = int(_os.environ.get("FQ_PWDW_FRONT", "1"))
 # Subsampled trunk (round 6, fq_pwconv_i8_sub2): the closing 1x1 of a ResNet-v1 stage stores only the pixels its two readers -
 # the next stage's first 1x1 and shortcut 1x1, both stride 2 without padding - look at (FQ_SUBSAMPLE=0: the whole tensor; A/B)
 SUBSAMPLE = _os.environ.get("FQ_SUBSAMPLE", "1") != "0"
@@ -615,6 +622,11 @@ def fuse_inference(net, depthwise=True, pointwise_int8=True, stem=True, residual
             if hasattr(b, "_fq_dw_fused"):
                 if getattr(nxt, "_fq_pw_fused", None) is not None and nxt._fq_pw_fused.get("kind") == "1x1":
                     fz["next"] = nxt
+                    # ... and, when that 1x1 opens a recompute pair, the depthwise layer in front of the pair
+                    # (convert_conv2d.front_target decides per forward)
+                    if b._kwargs["stride"] == (1, 1):
+                        fz["front_pw"] = nxt
+                        nxt._fq_pw_fused["front_dw"] = b
             elif getattr(nxt, "_fq_pw_fused", None) is not None and not nxt._fq_pw_fused.get("sliced"):
                 fz["next"] = nxt
             elif getattr(nxt, "_fq_dw_fused", None) is not None and fz.get("kind") == "1x1":

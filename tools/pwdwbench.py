@@ -1,9 +1,12 @@
 """The recompute pair alone on the GPU (round 6): fq_pwconv_i8 + fq_dwconv3x3 (two launches, the tensor between them written and
 read) against fq_pwconv_i8_stat + fq_pwdw_fused, on MobileNet1.0's pointwise -> depthwise pairs at batch 128.
 
-    python tools/pwdwbench.py [--batch 128] [--reps 30] [--pairs 1,2,3,4,5] [--codes 0]
+    python tools/pwdwbench.py [--batch 128] [--reps 30] [--pairs 1,2,3,4,5] [--codes 0] [--front 1]
 
 --codes 1 (default): the statistic pass keeps the int8 codes of x and the fused launch loads them; 0: both read the fp32 x.
+--front 1: ONLY the table of the depthwise layer in front of the first pair - fq_dwconv3x3 (storing) + fq_pwconv_i8_stat against
+fq_dwconv3x3 without y (statistic pass, input codes kept) + fq_pwconv_i8_stat with that layer recomputed in front - on
+MobileNet1.0's and MobileNet0.5's dw1 -> pw1 at the batch size.
 
 Per pair: time of each launch (HIP events on the launch stream, median over reps, all launches back to back), bytes each form
 moves, and the resulting TB/s.  Values are checked bit-equal before timing."""
@@ -35,16 +38,68 @@ def timed(fn, reps):
     return float(np.median(ts))
 
 
+FRONTS = {"mobilenet1.0": (32, 64, 112), "mobilenet0.5": (16, 32, 112)}
+
+
+def front_table(n, reps, dev):
+    print("front          shape              stored: dw + stat = total (us)        recomputed: dw-stat + stat = total (us)   "
+          "MB moved stored / recomputed   speed-up")
+    for name, (cin, cout, hw) in FRONTS.items():
+        y0 = torch.relu(torch.randn(n, cin, hw, hw, device=dev)) * 1.7
+        dww = ops.weight_fake_quant(torch.randn(cin, 1, 3, 3, device=dev) * 0.3, cin, 8)
+        codes, scales, rowsum = ops.weight_codes(torch.randn(cout, cin, device=dev) * 0.2, cout, 8)
+        scA, shA = torch.rand(cin, device=dev) + 0.5, torch.randn(cin, device=dev) * 0.3
+        scB, shB = torch.rand(cout, device=dev) + 0.5, torch.randn(cout, device=dev) * 0.3
+        s0 = ops.absmax_per_sample(y0)
+        curA, curB = torch.zeros(1, device=dev), torch.zeros(1, device=dev)
+        if not ops.pwconv_front_supported(y0.shape, cout):
+            print("%-14s %s: shape not taken" % (name, (n, cin, cout, hw)))
+            continue
+        st = {}
+        zc = [torch.empty(ops.pair_codes_shape(y0.shape), dtype=torch.int8, device=dev) for _ in range(2)]
+        yc = torch.empty(ops.front_codes_shape(y0.shape), dtype=torch.int8, device=dev)
+        dwk = dict(stride=1, in_stat=s0, cur_out=curA, bn_scale=scA, bn_shift=shA, act="relu")
+        pwk = dict(cur_out=curB, bn_scale=scB, bn_shift=shB, act="relu")
+
+        def dw():
+            st["z"], st["zs"] = ops.dwconv3x3(y0, dww, None, **dwk)
+
+        def sa():
+            st["ps"] = ops.pwconv_i8_stat(st["z"], codes, scales, rowsum, None, in_stat=st["zs"], x_codes_out=zc[0], **pwk)
+
+        def ds():
+            st["zs1"] = ops.dwconv3x3(y0, dww, None, store=False, x_codes_out=yc, **dwk)[1]
+
+        def sf():
+            st["ps1"] = ops.pwconv_i8_stat(st["z"], codes, scales, rowsum, None, in_stat=st["zs1"], x_codes_out=zc[1],
+                                           front=dict(x_codes=yc, w=dww, bn_scale=scA, bn_shift=shA, act="relu", in_stat=s0), **pwk)
+        dw(); sa(); ds(); sf()
+        torch.cuda.synchronize()
+        ok = torch.equal(st["zs"], st["zs1"]) and torch.equal(st["ps"], st["ps1"]) and torch.equal(zc[0], zc[1])
+        t_dw, t_sa, t_ds, t_sf = timed(dw, reps), timed(sa, reps), timed(ds, reps), timed(sf, reps)
+        yb = 4e-6 * n * cin * hw * hw                                    # the depthwise input = its output, fp32
+        zcb = 32e-6 * n * ((cin + 31) // 32) * hw * hw                    # the pair's code buffer
+        mb2, mb1 = 2 * yb + yb + zcb, yb + yb / 4 + yb / 4 + zcb
+        print("%-14s %3d->%3d @%3dx%-3d   %6.1f + %6.1f = %6.1f (%4.2f TB/s)        %6.1f + %6.1f = %6.1f (%4.2f TB/s)          "
+              "%6.0f / %5.0f            %5.2fx  %s" % (name, cin, cout, hw, hw, t_dw, t_sa, t_dw + t_sa, mb2 / (t_dw + t_sa), t_ds,
+                                                    t_sf, t_ds + t_sf, mb1 / (t_ds + t_sf), mb2, mb1,
+                                                    (t_dw + t_sa) / (t_ds + t_sf), "bit-equal" if ok else "VALUES DIFFER"))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=128)
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--pairs", default="1,2,3,4,5")
     ap.add_argument("--codes", type=int, default=1)
+    ap.add_argument("--front", type=int, default=0)
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
     n = a.batch
+    if a.front:
+        front_table(n, a.reps, dev)
+        return
     print("pair  shape                          two launches: pw + dw = total (us)   recompute: stat + fused = total (us)   "
           "MB moved two / fused   speed-up")
     tot2 = tot1 = 0.0
