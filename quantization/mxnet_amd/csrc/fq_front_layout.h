@@ -1,0 +1,102 @@
+// libfakequant - the band buffer of the front-layer statistic pass (fq_pwdw.hip: pw_stat_kernel with FEPI >= 0) and the rows
+// a band gets.  Plain C++ as well as HIP: tests/front_layout_main.cpp compiles this file alone and walks every admitted shape.
+//
+// The buffer holds the codes of one band - R rows of W = 4 Q pixels, Cin channels - between the two phases of the kernel:
+//   1  lane (seg, pos) of a wavefront owns channel front_channel(c0, wave, segs, seg) and the four columns 4 pos .. 4 pos + 3 of
+//      a row; per row it writes four bytes, column j of all lanes in one wave-instruction;
+//   2  lane (i32, h) reads the 16 channels 16 h .. 16 h + 15 of pixel 32 tile + mfma_row_pixel(i32): its MFMA A fragment.
+// LDS has 32 banks of 4 bytes, a wave-instruction is served as lanes 0-31 and 32-63, and two lanes conflict when they touch
+// DIFFERENT dwords of one bank.  In C16 order ([16-channel block][pixel][16 bytes]) the lanes of phase 1 are 64 bytes apart:
+// two banks for up to 32 lanes.  Here instead
+//   byte(c, p) = 4 * ((c >> 2) * pl + front_slot(p)) + (c & 3),      front_slot(p) = (p & 3) * js + (p >> 2)
+// - four-channel planes of dwords, inside a plane the four columns j = p & 3 de-interleaved:
+//   phase 1: the lanes of a row segment write CONSECUTIVE dwords (p >> 2 = row * Q + pos), four neighbouring channels the four
+//            bytes of one dword; a half-wave meets at most three planes, each a run of at most 32 dwords: never more than two
+//            dwords on a bank (pl = 16 mod 32 keeps two planes of short rows apart);
+//   phase 2: the 32 pixels of a tile are 8 consecutive p >> 2 for each of the four j: four runs of 8 dwords, js apart - with
+//            js = 8 mod 16 they fall on 32 different banks.  The fragment is four dword reads, one per plane 4 h .. 4 h + 3.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+
+#if defined(__HIPCC__)
+#define FQ_FL_FN __host__ __device__ __forceinline__
+#else
+#define FQ_FL_FN inline
+#endif
+
+namespace fqi {
+
+constexpr int kFrontRows = 8;                  // most rows of a band (the kernel keeps kFrontRows + 2 input rows in registers)
+constexpr int kFrontBandBytes = 32768;         // most codes of a band: rows * W * 32 channels
+constexpr int kStatLdsPerCU = 160 * 1024, kStatLdsMax = 120 * 1024;
+
+struct FrontLayout {
+  int js;                                      // dwords between the column planes j = 0 .. 3 (>= rows * Q, = 8 mod 16)
+  int pl;                                      // dwords between the four-channel planes (= 16 mod 32)
+};
+
+FQ_FL_FN FrontLayout front_layout(int q, int rows) {
+  FrontLayout l;
+  l.js = rows * q + ((8 - rows * q) & 15);
+  l.pl = 4 * l.js + 16;
+  return l;
+}
+
+// pixel p of the band (row-major, rows of 4 Q pixels) -> its dword inside a four-channel plane.  THE map: both phases call it.
+FQ_FL_FN int front_slot(FrontLayout l, int p) { return (p & 3) * l.js + (p >> 2); }
+
+FQ_FL_FN int front_byte(FrontLayout l, int c, int p) { return (((c >> 2) * l.pl + front_slot(l, p)) << 2) + (c & 3); }
+
+inline size_t front_band_bytes(int q, int rows, int cin) { return (size_t)((cin + 3) / 4) * front_layout(q, rows).pl * 4; }
+
+// phase 1: the channel of segment `seg` of wavefront `wave` in the turn that starts at channel c0 (4 * segs channels per turn)
+FQ_FL_FN int front_channel(int c0, int wave, int segs, int seg) { return c0 + wave * segs + seg; }
+
+// the tile pixel of MFMA row i32 (row 8 g + 4 h + i holds pixel 16 h + 4 g + i: a lane's 16 registers are 16 consecutive pixels)
+FQ_FL_FN int mfma_row_pixel(int i32) { return 16 * ((i32 >> 2) & 1) + 4 * (i32 >> 3) + (i32 & 3); }
+
+// persistent workgroups of the statistic pass per CU: by LDS, at most `cap` (registers)
+inline int stat_wg_per_cu(size_t lds, int cap) {
+  const int by_lds = (int)((size_t)kStatLdsPerCU / (lds + 1024));
+  return by_lds > cap ? cap : (by_lds < 1 ? 1 : by_lds);
+}
+
+// Rows per band.  A band of R rows dequantises R + 2 input rows, and the n * ceil(h / R) bands go round by round over the
+// workgroups launched (stat_wg_per_cu of them per CU, fewer when there are fewer bands).  The kernel is bound by its vector
+// instructions, which the workgroups of a CU share: the cost of a choice is the rows the busiest CU dequantises,
+// rounds * ceil(workgroups / CUs) * (R + 2).  On a full chip that is pwdw_plan's rounds * (R + 2); on a chip that the bands
+// do not fill it does NOT divide by the fill as pwdw_plan does - that prefers many short bands, and measured at batch 32 four
+// rows per band lose to eight (49.8 against 47.3 us, 44.1 against 39.9 on 16 channels: profiles/front_stat_alone.txt).  Among
+// equal costs a band of whole 32-pixel tiles wins, then the longer one.  MobileNet's 112 x 112 plane at batch 128 on 256 CUs:
+// R = 8 is 1792 bands on 1024 workgroups - two rounds of 10 rows where the mean is 1.75 - and R = 7 is 2048 bands, two rounds of 9.
+// `lds_fixed`: what the launch needs beside the band buffer; `forced` > 0: that many rows (clamped), the tuning knob.
+// 0 when no band fits (the caller refuses the shape).
+inline int front_rows_pick(int64_t n, int64_t h, int64_t w, int cin, size_t lds_fixed, int num_cu, int wg_cap, int forced = 0) {
+  const int q = (int)(w / 4);
+  int rmax = (int)(kFrontBandBytes / (32 * w));
+  rmax = rmax > kFrontRows ? kFrontRows : rmax;
+  rmax = rmax > h ? (int)h : rmax;
+  while (rmax >= 1 && lds_fixed + front_band_bytes(q, rmax, cin) > (size_t)kStatLdsMax) --rmax;
+  if (rmax < 1) return 0;
+  if (forced > 0) return forced < rmax ? forced : rmax;
+  double best = 1e30;
+  int best_r = rmax;
+  bool best_whole = false;
+  for (int r = rmax; r >= 1; --r) {
+    const int64_t wgs = n * ((h + r - 1) / r);
+    const int64_t slots = (int64_t)num_cu * stat_wg_per_cu(lds_fixed + front_band_bytes(q, r, cin), wg_cap);
+    const int64_t grid = wgs < slots ? wgs : slots, rounds = (wgs + grid - 1) / grid;
+    const double cost = (double)(rounds * ((grid + num_cu - 1) / num_cu) * (r + 2));
+    const bool whole = (r * w) % 32 == 0;
+    if (cost < best - 1e-9 || (cost < best + 1e-9 && whole && !best_whole)) {
+      best = cost;
+      best_r = r;
+      best_whole = whole;
+    }
+  }
+  return best_r;
+}
+
+}  // namespace fqi

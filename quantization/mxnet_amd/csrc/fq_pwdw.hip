@@ -25,6 +25,8 @@
 // leave as whole rows, 16 bytes per lane.
 #include "fq_pw.h"
 
+#include "fq_front_layout.h"
+
 #include <climits>
 
 namespace {
@@ -490,12 +492,13 @@ struct PwStatGeom {
 //      lanes, so the plane's edge is the segment's edge and takes 0): dequantise (code * scale, once per element and band),
 //      the row-major fmaf chain, the layer's epilogue (kEpi* as there) - bit for bit what that kernel stores - then THIS
 //      launch's quantiser (the threshold is known: the depthwise pass left its statistic), and the code byte goes to an LDS
-//      band buffer in C16 order [16-channel block][pixel][16].  The transposition planar -> C16 happens here, on LDS bytes;
-//   2  the band buffer is read back as MFMA A fragments (one 16-byte LDS read per lane and 32-pixel tile) and everything from
-//      there on is the kernel's own: the fragment leaves as x_codes_out, max / min of the int32 sums, flush per sample.
-// A band is R <= kFrontRows output rows of one sample (all channels, whole rows): R + 2 input rows are dequantised for it.
-// FSIGNED: the input codes are two's complement bytes (FQ_ACT_SIGNED), else 0 .. 255.
-constexpr int kFrontRows = 8;
+//      band buffer of four-channel planes (fq_front_layout.h: the order in which no store and no read meets a bank conflict).
+//      The transposition planar -> C16 happens here, on LDS bytes;
+//   2  the band buffer is read back as MFMA A fragments (four dword LDS reads per lane and 32-pixel tile: the 16 channels of the
+//      lane's pixel) and everything from there on is the kernel's own: the fragment leaves as x_codes_out, max / min of the
+//      int32 sums, flush per sample.
+// A band is R <= kFrontRows output rows of one sample (all channels, whole rows): R + 2 input rows are dequantised for it
+// (front_rows_pick chooses R).  FSIGNED: the input codes are two's complement bytes (FQ_ACT_SIGNED), else 0 .. 255.
 struct PwFrontArgs {
   const int8_t* codes;               // [n][Cin][H * W]
   const float *w, *bias, *bn_scale, *bn_shift;
@@ -503,6 +506,7 @@ struct PwFrontArgs {
   float levels;
   int act;
   int H, W, Q, segs, R, bands;       // Q = W / 4 lanes per row, `segs` rows (channels) per wavefront, R output rows per band
+  FrontLayout lay;                   // the band buffer's strides for (Q, R)
 };
 
 template <int KT, int FEPI = -1, bool FSIGNED = false>
@@ -520,7 +524,7 @@ __global__ __launch_bounds__(kBlock, 3) void pw_stat_kernel(
   float* c_k = reinterpret_cast<float*>(c_zs + g.CT * 32);                                 // [4][CT * 32]: w scale, bias, BN scale / shift
   int* accs = reinterpret_cast<int*>(c_k + 4 * g.CT * 32);                                 // [4 waves][CT][2][64]
   float* dwk = reinterpret_cast<float*>(accs + 4 * g.CT * 128);                             // FRONT: [Cin][12] taps, bias, BN scale / shift
-  unsigned char* zbuf = reinterpret_cast<unsigned char*>(dwk + g.Cin * 12);                 // FRONT: [2][R * W][16] band of codes
+  unsigned char* zbuf = reinterpret_cast<unsigned char*>(dwk + g.Cin * 12);                 // FRONT: [Cin / 4][lay.pl] dwords, band of codes
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int h = lane >> 5, i32 = lane & 31;
   const unsigned HW = (unsigned)g.HW, cols = (unsigned)g.cols;
@@ -529,7 +533,7 @@ __global__ __launch_bounds__(kBlock, 3) void pw_stat_kernel(
   const int64_t n_bands = FRONT ? (int64_t)(g.cols / g.HW) * fa.bands : 0;
   const int64_t t_begin = FRONT ? n_bands * blockIdx.x / gridDim.x : g.tiles * wid / nwaves;
   const int64_t t_end = FRONT ? n_bands * (blockIdx.x + 1) / gridDim.x : g.tiles * (wid + 1) / nwaves;
-  const int pl = 16 * ((i32 >> 2) & 1) + 4 * (i32 >> 3) + (i32 & 3);      // tile pixel of this lane's MFMA row
+  const int pl = mfma_row_pixel(i32);                                     // tile pixel of this lane's MFMA row
   int* my = accs + (size_t)wave * g.CT * 128;
   constexpr int kSlots = 8;
   __shared__ unsigned k_stat[kSlots];
@@ -763,7 +767,7 @@ __global__ __launch_bounds__(kBlock, 3) void pw_stat_kernel(
   auto run_front = [&](auto nn_c) __attribute__((always_inline)) {
     constexpr bool NN = decltype(nn_c)::value;
     constexpr int FE = FRONT ? FEPI : kEpiRuntime;
-    const int Q = fa.Q, W = fa.W, H = fa.H, NP = fa.R * fa.W;
+    const int Q = fa.Q, W = fa.W, H = fa.H;
     const int seg = lane / Q, pos = lane - seg * Q;
     const bool first = pos == 0, last = pos == Q - 1;
     const bool has_fb = fa.bias != nullptr, has_fbn = fa.bn_scale != nullptr;
@@ -786,7 +790,7 @@ __global__ __launch_bounds__(kBlock, 3) void pw_stat_kernel(
       }
       // ---- 1: the depthwise layer on rows r0 - 1 .. r0 + Rb of `segs` channels per wavefront and turn ----
       for (int c0 = 0; c0 < g.Cin; c0 += 4 * fa.segs) {
-        const int c = c0 + wave * fa.segs + seg;
+        const int c = front_channel(c0, wave, fa.segs, seg);
         const bool c_ok = seg < fa.segs && c < g.Cin;
         const int cc = c_ok ? c : 0;
         const float* kc = dwk + cc * 12;
@@ -814,6 +818,11 @@ __global__ __launch_bounds__(kBlock, 3) void pw_stat_kernel(
           }
         };
         float a[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, b[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        // the lane's byte of band pixel (row 0, column 4 pos); a column / a row further on are front_byte's own strides (the map
+        // is linear in the row and in the column of a four-column group) - one running address instead of 32
+        unsigned dst = (unsigned)front_byte(fa.lay, cc, 4 * pos);
+        const unsigned jstep = (unsigned)(front_byte(fa.lay, 0, 1) - front_byte(fa.lay, 0, 0));
+        const unsigned rstep = (unsigned)(front_byte(fa.lay, 0, 4 * Q) - front_byte(fa.lay, 0, 0));
 #pragma unroll
         for (int k = 0; k < kFrontRows + 2; ++k) {
           if (k <= Rb + 1) {                      // (the same for the whole workgroup)
@@ -824,13 +833,14 @@ __global__ __launch_bounds__(kBlock, 3) void pw_stat_kernel(
             cv[0] = first ? 0.0f : lp;
             cv[5] = last ? 0.0f : ln;
             if (k >= 2) {                         // input row r0 + k - 1 closes output row r0 + k - 2
-              unsigned char* dst = zbuf + ((size_t)((cc >> 4) * NP + (k - 2) * W + 4 * pos) * 16 + (cc & 15));
 #pragma unroll
               for (int j = 0; j < 4; ++j) {
                 const unsigned code = zcode(dw_taps(w00, w01, w02, w10, w11, w12, w20, w21, w22, a[j], a[j + 1], a[j + 2], b[j],
                                                     b[j + 1], b[j + 2], cv[j], cv[j + 1], cv[j + 2]));
-                if (c_ok) dst[16 * j] = (unsigned char)code;
+                if (c_ok) zbuf[dst + j * jstep] = (unsigned char)code;
               }
+              dst += rstep;
+              asm volatile("" : "+v"(dst));
             }
 #pragma unroll
             for (int j = 0; j < 6; ++j) {
@@ -846,7 +856,11 @@ __global__ __launch_bounds__(kBlock, 3) void pw_stat_kernel(
       for (int tl = wave; tl < ntile; tl += 4) {
         int pp = tl * 32 + pl;
         pp = pp < npix ? pp : npix - 1;
-        v4i f = *reinterpret_cast<const v4i*>(zbuf + ((size_t)(h * NP + pp) << 4));
+        // channels 16 h .. 16 h + 15 of pixel pp: byte 0 of planes 4 h .. 4 h + 3 (the half-slab past Cin has no planes)
+        const unsigned* zp = reinterpret_cast<const unsigned*>(zbuf + front_byte(fa.lay, g.Cin <= 16 ? 0 : 16 * h, pp));
+        v4i f;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) f[u] = (int)zp[u * fa.lay.pl];
         if (g.Cin <= 16 && h == 1) f = zero_frag;            // (the half-slab past Cin: the code of 0)
         if (wr_codes) buf_st_v4i(rcodes, ((smp * 2u + (unsigned)h) * HW + (unsigned)(r0 * W + pp)) * 16u, f);
         afrag[0] = f;
@@ -942,33 +956,36 @@ PwDwPlan pwdw_plan(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w, i
 
 namespace fqi {
 
+// LDS of the statistic pass beside a front layer's: weight fragments, per-channel constants, the wavefronts' max / min
+static size_t pw_stat_lds(int kt, int ct) { return (size_t)ct * kt * 1024 + 5 * (size_t)ct * 32 * 4 + 4 * (size_t)ct * 128 * 4; }
+
 bool pw_stat_shape_ok(int64_t n, int64_t cin, int64_t cout, int64_t hw) {
   if (n <= 0 || cin <= 0 || cout <= 0 || hw < 32 || hw >= (1ll << 30) || n * hw >= (1ll << 31) - 512) return false;
   const int kt = (int)((cin + 31) / 32), ct = (int)((cout + 31) / 32);
   if (!(kt == 1 || kt == 2 || kt == 4 || kt == 8) || cin % 16 != 0) return false;
-  const size_t lds = (size_t)ct * kt * 1024 + 5 * (size_t)ct * 32 * 4 + 4 * (size_t)ct * 128 * 4;
-  return lds <= 120 * 1024 && n * cin * hw * 4 < (1ll << 32);
+  return pw_stat_lds(kt, ct) <= (size_t)kStatLdsMax && n * cin * hw * 4 < (1ll << 32);
 }
 
-// rows per band of the front-layer mode: as many as kFrontRows and 32 KiB of band buffer allow, whole 32-pixel tiles preferred
-static int pw_front_rows(int64_t h, int64_t w) {
-  int r = (int)(32768 / (32 * w));
-  r = r > kFrontRows ? kFrontRows : r;
-  r = r > h ? (int)h : r;
-  for (int k = r; k >= 1 && 2 * k > r; --k)
-    if ((k * w) % 32 == 0) return k;
-  return r;
+constexpr int kFrontWgCap = 4;          // (by registers: the front-layer instantiations fit four wavefronts per SIMD)
+
+// rows per band of the front-layer mode (front_rows_pick, fq_front_layout.h); FQ_PWSTAT_FRONT_ROWS forces them and is read at
+// every call, so that a test can vary it inside one process
+static int pw_front_rows(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w) {
+  const char* e = getenv("FQ_PWSTAT_FRONT_ROWS");
+  static const int wg_env = env_int("FQ_PWSTAT_WG_PER_CU", 0);
+  const size_t fixed = pw_stat_lds(1, (int)((cout + 31) / 32)) + (size_t)cin * 12 * 4;
+  return front_rows_pick(n, h, w, (int)cin, fixed, num_cu(), wg_env > 0 ? wg_env : kFrontWgCap, e != nullptr ? atoi(e) : 0);
 }
 
 bool pw_stat_front_shape_ok(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w) {
   if (h < 1 || w < 4 || w % 4 != 0 || w / 4 > 64 || !(cin == 16 || cin == 32) || !pw_stat_shape_ok(n, cin, cout, h * w)) return false;
   // (the depthwise statistic pass in front must take the plane too: fq_dwconv3x3 without y)
-  return pw_front_rows(h, w) >= 1 && n * cin * ((w / 4 + 61) / 62) < (1ll << 31) - 1024;
+  return pw_front_rows(n, cin, cout, h, w) >= 1 && n * cin * ((w / 4 + 61) / 62) < (1ll << 31) - 1024;
 }
 
 int pw_stat_launch(const PwCall& c) {
   const int kt = (int)((c.cin + 31) / 32), ct = (int)((c.cout + 31) / 32);
-  size_t lds = (size_t)ct * kt * 1024 + 5 * (size_t)ct * 32 * 4 + 4 * (size_t)ct * 128 * 4;
+  size_t lds = pw_stat_lds(kt, ct);
   PwFrontArgs fa = {};
   if (c.front != nullptr) {
     const PwFront& f = *c.front;
@@ -976,18 +993,18 @@ int pw_stat_launch(const PwCall& c) {
     fa.w = f.w; fa.bias = f.bias; fa.bn_scale = f.bn_scale; fa.bn_shift = f.bn_shift;
     fa.in_stat = f.in_stat; fa.in_thr = f.in_thr; fa.levels = f.levels; fa.act = f.act;
     fa.H = (int)f.h; fa.W = (int)f.wdt; fa.Q = fa.W / 4; fa.segs = 64 / fa.Q;
-    fa.R = pw_front_rows(f.h, f.wdt);
+    fa.R = pw_front_rows(c.n, c.cin, c.cout, f.h, f.wdt);
+    FQ_REQUIRE(fa.R >= 1, "fq_pwconv_i8_stat: no band of the front layer fits the LDS");
     fa.bands = (fa.H + fa.R - 1) / fa.R;
-    lds += (size_t)c.cin * 12 * 4 + (size_t)32 * fa.R * fa.W;
+    fa.lay = front_layout(fa.Q, fa.R);
+    lds += (size_t)c.cin * 12 * 4 + front_band_bytes(fa.Q, fa.R, (int)c.cin);
   }
   PwStatGeom g;
   g.Cin = (int)c.cin; g.KTS = (int)(c.cin_pad / 32); g.Cout = (int)c.cout; g.CT = ct; g.HW = (int)c.hw;
   g.cols = c.n * c.hw; g.tiles = (g.cols + 31) / 32; g.zoff = c.zoff;
   g.hw = fast_div_for((unsigned)c.hw);
   if (int rc = pw_zero_stat(c)) return rc;
-  int per_cu = (int)((160 * 1024) / (lds + 1024));
-  const int wg_cap = c.front != nullptr ? 4 : 3;        // (by registers: the front-layer instantiations fit four wavefronts per SIMD)
-  per_cu = per_cu > wg_cap ? wg_cap : per_cu;
+  int per_cu = stat_wg_per_cu(lds, c.front != nullptr ? kFrontWgCap : 3);
   static const int wg_env = env_int("FQ_PWSTAT_WG_PER_CU", 0);
   if (wg_env > 0) per_cu = wg_env;
   int64_t grid = (int64_t)num_cu() * per_cu;

@@ -1,0 +1,103 @@
+// Stand-alone walk over the band buffer of the front-layer statistic pass (csrc/fq_front_layout.h), compiled and run by
+// tests/test_front_layout.py.  Plays both phases of pw_stat_kernel's front mode on the host, lane by lane, with the functions the
+// kernel itself calls, and prints per (Q, R, Cin, rows of the band) what the test asserts:
+//   map   Q R CIN RB  bijection(0/1)  inside(0/1)  store_ways  read_ways
+// store_ways / read_ways: the most DISTINCT dwords any wave-instruction of phase 1 / phase 2 puts on one of the 32 LDS banks
+// ((address / 4) mod 32), lanes 0-31 and 32-63 taken separately.
+//   rows  N CIN COUT H W CUS  R
+// the rows per band front_rows_pick chooses for a shape on a chip of CUS compute units.
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <set>
+#include <vector>
+
+#include "fq_front_layout.h"
+
+using namespace fqi;
+
+static int worst_bank(const std::vector<int>& dwords) {
+  std::set<int> per_bank[32];
+  for (int d : dwords) per_bank[d & 31].insert(d);
+  size_t w = 0;
+  for (const auto& s : per_bank) w = std::max(w, s.size());
+  return (int)w;
+}
+
+static void walk(int q, int rows, int cin, int rb) {
+  const FrontLayout lay = front_layout(q, rows);
+  const int w = 4 * q, segs = 64 / q, npix = rb * w;
+  const size_t bytes = front_band_bytes(q, rows, cin);
+  std::vector<int> hits(bytes, 0);
+  bool inside = true;
+  int store_ways = 0, read_ways = 0;
+  // phase 1: per channel turn, wavefront, output row and column j one byte store of all lanes
+  for (int c0 = 0; c0 < cin; c0 += 4 * segs)
+    for (int wave = 0; wave < 4; ++wave)
+      for (int row = 0; row < rb; ++row)
+        for (int j = 0; j < 4; ++j)
+          for (int half = 0; half < 2; ++half) {
+            std::vector<int> dwords;
+            for (int lane = 32 * half; lane < 32 * half + 32; ++lane) {
+              const int seg = lane / q, pos = lane - seg * q;
+              const int c = front_channel(c0, wave, segs, seg);
+              if (!(seg < segs && c < cin)) continue;
+              const int a = front_byte(lay, c, 4 * (row * q + pos) + j);
+              if (a < 0 || (size_t)a >= bytes) {
+                inside = false;
+                continue;
+              }
+              ++hits[a];
+              dwords.push_back(a >> 2);
+            }
+            store_ways = std::max(store_ways, worst_bank(dwords));
+          }
+  // every (channel, pixel) of the band exactly one byte, through front_byte directly: a bijection onto cin * npix bytes
+  bool bij = true;
+  std::set<int> seen;
+  for (int c = 0; c < cin; ++c)
+    for (int p = 0; p < npix; ++p) {
+      const int a = front_byte(lay, c, p);
+      if (a < 0 || (size_t)a >= bytes || hits[a] != 1 || !seen.insert(a).second) bij = false;
+    }
+  long total = 0;
+  for (int v : hits) total += v;
+  if (total != (long)cin * npix || seen.size() != (size_t)cin * npix) bij = false;
+  std::set<int> slots;                           // and the pixel -> slot map alone: one slot each, inside a plane
+  for (int p = 0; p < npix; ++p) {
+    const int s = front_slot(lay, p);
+    if (s < 0 || s >= lay.pl || !slots.insert(s).second) bij = false;
+  }
+  // phase 2: per tile and plane u one dword read of all lanes; lane (i32, h) reads plane 4 h + u of pixel 32 tile + its row pixel
+  for (int tl = 0; tl < (npix + 31) / 32; ++tl)
+    for (int u = 0; u < 4; ++u)
+      for (int h = 0; h < 2; ++h) {
+        std::vector<int> dwords;
+        for (int i32 = 0; i32 < 32; ++i32) {
+          const int pp = std::min(tl * 32 + mfma_row_pixel(i32), npix - 1);
+          const int a = front_byte(lay, cin <= 16 ? 0 : 16 * h, pp) + 4 * u * lay.pl;
+          if (a < 0 || (size_t)a + 4 > bytes) inside = false;
+          dwords.push_back(a >> 2);
+        }
+        read_ways = std::max(read_ways, worst_bank(dwords));
+      }
+  printf("map %d %d %d %d %d %d %d %d\n", q, rows, cin, rb, bij ? 1 : 0, inside ? 1 : 0, store_ways, read_ways);
+}
+
+int main(int argc, char** argv) {
+  for (int q = 4; q <= 64; ++q)
+    for (int rows = 1; rows <= kFrontRows; ++rows)
+      for (int cin = 16; cin <= 32; cin += 16) {
+        walk(q, rows, cin, rows);
+        if (rows > 1) walk(q, rows, cin, 1);                  // the short last band of a plane
+        if (rows > 2) walk(q, rows, cin, rows - 1);
+      }
+  // rows N CIN COUT H W CUS: the LDS beside the band buffer as pw_stat_launch counts it (one 32-channel slab)
+  for (int i = 1; i + 5 < argc; i += 6) {
+    const long n = atol(argv[i]), cin = atol(argv[i + 1]), cout = atol(argv[i + 2]), h = atol(argv[i + 3]), w = atol(argv[i + 4]);
+    const int cus = atoi(argv[i + 5]), ct = (int)((cout + 31) / 32);
+    const size_t fixed = (size_t)ct * 1024 + 5 * (size_t)ct * 32 * 4 + 4 * (size_t)ct * 128 * 4 + (size_t)cin * 12 * 4;
+    printf("rows %ld %ld %ld %ld %ld %d %d\n", n, cin, cout, h, w, cus, front_rows_pick(n, h, w, (int)cin, fixed, cus, 4));
+  }
+  return 0;
+}

@@ -4,6 +4,9 @@ between consecutive runs, so single runs say nothing: every round runs every var
 mean / median / min / max images/s and the mean of the PAIRED ratios against the first variant (same round = same mood).
 
     python tools/ab.py [--rounds 5] [--args "bench.py args"] "label" "label|ENV=V ENV2=V" "label||--streams 2" ...
+
+A run whose exit status is not 0 ends the whole comparison at once (exit status 1, the tail of that run's stderr printed):
+nothing is started on a GPU that a child may just have faulted.
 """
 import json
 import os
@@ -35,8 +38,16 @@ def main():
         for label, env, vargs in variants:
             res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full"] + extra.split() + vargs, env=dict(base_env, **env),
                                  capture_output=True, text=True, cwd=ROOT)
+            if res.returncode != 0:
+                # a child that died may have left the GPU in a bad state: nothing more is started on it
+                print("round %d  %-32s exit status %d - stopping.  Last lines of its stderr:" % (r + 1, label, res.returncode), flush=True)
+                print("\n".join(res.stderr.strip().splitlines()[-20:]), flush=True)
+                sys.exit(1)
             try:
-                v = json.loads(res.stdout.strip().splitlines()[-1])["value"]
+                line = json.loads(res.stdout.strip().splitlines()[-1])
+                v = line["value"]
+                if r == 0 and label == variants[0][0] and line.get("box"):
+                    print("box (first run): " + " ".join("%s=%s" % (k, line["box"][k]) for k in sorted(line["box"]) if k != "what"), flush=True)
             except Exception:
                 v = float("nan")
             vals[label].append(v)

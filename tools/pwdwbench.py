@@ -35,6 +35,7 @@ def timed(fn, reps):
         b.record()
         b.synchronize()
         ts.append(a.elapsed_time(b) * 1e3)
+    timed.sd = float(np.std(ts))                       # (of the call just made: front_table prints it beside the medians)
     return float(np.median(ts))
 
 
@@ -76,7 +77,11 @@ def front_table(n, reps, dev):
         dw(); sa(); ds(); sf()
         torch.cuda.synchronize()
         ok = torch.equal(st["zs"], st["zs1"]) and torch.equal(st["ps"], st["ps1"]) and torch.equal(zc[0], zc[1])
-        t_dw, t_sa, t_ds, t_sf = timed(dw, reps), timed(sa, reps), timed(ds, reps), timed(sf, reps)
+        ts, sds = [], []
+        for fn in (dw, sa, ds, sf):
+            ts.append(timed(fn, reps))
+            sds.append(timed.sd)
+        t_dw, t_sa, t_ds, t_sf = ts
         yb = 4e-6 * n * cin * hw * hw                                    # the depthwise input = its output, fp32
         zcb = 32e-6 * n * ((cin + 31) // 32) * hw * hw                    # the pair's code buffer
         mb2, mb1 = 2 * yb + yb + zcb, yb + yb / 4 + yb / 4 + zcb
@@ -84,6 +89,8 @@ def front_table(n, reps, dev):
               "%6.0f / %5.0f            %5.2fx  %s" % (name, cin, cout, hw, hw, t_dw, t_sa, t_dw + t_sa, mb2 / (t_dw + t_sa), t_ds,
                                                     t_sf, t_ds + t_sf, mb1 / (t_ds + t_sf), mb2, mb1,
                                                     (t_dw + t_sa) / (t_ds + t_sf), "bit-equal" if ok else "VALUES DIFFER"))
+        print("%-14s sd over the %d repetitions (us): dw %.2f  stat %.2f  dw-stat %.2f  stat with the front layer %.2f"
+              % ("", reps, sds[0], sds[1], sds[2], sds[3]))
 
 
 def main():
