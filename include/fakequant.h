@@ -428,7 +428,17 @@ int fq_pwconv_i8_gap(const float* x, const int8_t* wcodes, const float* wscale, 
  * front_bn_shift and front_act on them - bit for bit the values that launch would have stored - and go on as above with those
  * values as x: in_stat / in_thr are the statistic / threshold of the depthwise OUTPUT, x_codes_out receives ITS codes.  x is not
  * dereferenced.  hw == front_h * front_wdt.  Shapes: fq_pwconv_i8_stat_supported(..., front_h, front_wdt) with both non-zero -
- * cin 16 or 32, front_wdt % 4 == 0 and at most 256 (0, 0: the question for the launch without a front layer).              */
+ * cin 16, 32, 64 or 128, front_wdt % 4 == 0 and at most 256 (0, 0: the question for the launch without a front layer).
+ * A chain of two pairs.  When the depthwise layer of a pair has stride 1 and z feeds the 1x1 of the NEXT pair, z need not be
+ * stored either: fq_pwdw_fused with the trailing mid_codes_out != NULL (and y == NULL) is (B) in statistic mode - the same
+ * recomputation and the same chain, stat_out[n] <- max|z[n]| and mid_current_max as above, no z - and keeps the codes of y it
+ * has just made for the stencil: mid_codes_out, int8
+ * [n][cout][h * w], the low byte of the code (0 .. 255, or two's complement under FQ_ACT_SIGNED) - the buffer fq_dwconv3x3's
+ * statistic pass keeps of ITS input, so the next pair's (A) takes it as front_codes with mid_stat / mid_thr, mid_width and
+ * mid_flags as the front layer's input quantiser.  Every byte of the buffer is written (bytes that two strips or two bands of
+ * the launch both compute are written by both, with the same value).  Needs x_codes; shapes: fq_pwdw_fused_supported with the
+ * trailing stat_mode = 1 - those of fq_pwdw_fused at stride 1 with w % 4 == 0; mid_width <= 8 and no FQ_ACT_LO_NEG_MAX without
+ * FQ_ACT_SIGNED (the codes fit a byte).  Libraries from fq_version() 102 on.                                                                                                              */
 int fq_pwconv_i8_stat_supported(int64_t n, int64_t cin, int64_t cout, int64_t hw, int64_t front_h, int64_t front_wdt);
 int fq_pwconv_i8_stat(const float* x, const int8_t* wcodes, const float* wscale, const int32_t* wsum, const float* bias,
                       int64_t n, int64_t cin, int64_t cin_pad, int64_t cout_pad, int64_t cout, int64_t hw,
@@ -437,7 +447,7 @@ int fq_pwconv_i8_stat(const float* x, const int8_t* wcodes, const float* wscale,
                       fqStream_t stream, const void* front_codes, const float* front_w, const float* front_bias,
                       const float* front_bn_scale, const float* front_bn_shift, int front_act, const float* front_in_stat,
                       const float* front_in_thr, int front_width, unsigned front_flags, int64_t front_h, int64_t front_wdt);
-int fq_pwdw_fused_supported(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w, int stride);
+int fq_pwdw_fused_supported(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w, int stride, int stat_mode);
 /* Test hook: out[i] <- the fp32 quotient c[i] / d[0] as the two kernels above compute it (the fp32 correction step of
  * csrc/fq_common.h: fast_quot, or the fp64-reciprocal form when d[0] does not qualify; took_fast_path[0] says which) - must
  * equal the IEEE fp32 division bit for bit wherever a code depends on it (tests/test_gpu_pwdw.py).                         */
@@ -448,7 +458,7 @@ int fq_pwdw_fused(const float* x, const int8_t* wcodes, const float* wscale, con
                   const float* pw_bn_shift, int pw_act, const float* mid_stat, const float* mid_thr, int mid_width,
                   unsigned mid_flags, float* mid_current_max, const float* dw_w, const float* dw_bias, int dw_stride,
                   const float* dw_bn_scale, const float* dw_bn_shift, int dw_act, float* y, float* stat_out,
-                  const void* x_codes, fqStream_t stream);
+                  const void* x_codes, fqStream_t stream, void* mid_codes_out);
 
 /* ---- int8 hand-over between fused convolutions under OFFLINE input quantisation (round 3) ------------------------------
  * When the consumer quantises its input with a STORED threshold (`--quantize-input-offline`: convert_conv2d.py:58 takes

@@ -4,7 +4,8 @@
 // The buffer holds the codes of one band - R rows of W = 4 Q pixels, Cin channels - between the two phases of the kernel:
 //   1  lane (seg, pos) of a wavefront owns channel front_channel(c0, wave, segs, seg) and the four columns 4 pos .. 4 pos + 3 of
 //      a row; per row it writes four bytes, column j of all lanes in one wave-instruction;
-//   2  lane (i32, h) reads the 16 channels 16 h .. 16 h + 15 of pixel 32 tile + mfma_row_pixel(i32): its MFMA A fragment.
+//   2  lane (i32, h) reads the 16 channels 32 kt + 16 h .. + 15 of pixel 32 tile + mfma_row_pixel(i32): its MFMA A fragment of
+//      slab kt (Cin / 32 slabs: one for 16 and 32 channels, two and four for 64 and 128).
 // LDS has 32 banks of 4 bytes, a wave-instruction is served as lanes 0-31 and 32-63, and two lanes conflict when they touch
 // DIFFERENT dwords of one bank.  In C16 order ([16-channel block][pixel][16 bytes]) the lanes of phase 1 are 64 bytes apart:
 // two banks for up to 32 lanes.  Here instead
@@ -14,7 +15,8 @@
 //            bytes of one dword; a half-wave meets at most three planes, each a run of at most 32 dwords: never more than two
 //            dwords on a bank (pl = 16 mod 32 keeps two planes of short rows apart);
 //   phase 2: the 32 pixels of a tile are 8 consecutive p >> 2 for each of the four j: four runs of 8 dwords, js apart - with
-//            js = 8 mod 16 they fall on 32 different banks.  The fragment is four dword reads, one per plane 4 h .. 4 h + 3.
+//            js = 8 mod 16 they fall on 32 different banks.  The fragment is four dword reads, one per plane 8 kt + 4 h .. + 3
+//            (a plane further on moves every lane by the same pl dwords: what holds for one plane holds for all).
 #pragma once
 
 #include <cstddef>
@@ -29,7 +31,8 @@
 namespace fqi {
 
 constexpr int kFrontRows = 8;                  // most rows of a band (the kernel keeps kFrontRows + 2 input rows in registers)
-constexpr int kFrontBandBytes = 32768;         // most codes of a band: rows * W * 32 channels
+constexpr int kFrontBandBytes = 32768;         // most codes of a band PER 32-CHANNEL SLAB: rows * W * 32 (64 and 128 channels:
+                                               // two and four times as much, and the LDS limit below decides)
 constexpr int kStatLdsPerCU = 160 * 1024, kStatLdsMax = 120 * 1024;
 
 struct FrontLayout {
@@ -71,6 +74,11 @@ inline int stat_wg_per_cu(size_t lds, int cap) {
 // rows per band lose to eight (49.8 against 47.3 us, 44.1 against 39.9 on 16 channels: profiles/front_stat_alone.txt).  Among
 // equal costs a band of whole 32-pixel tiles wins, then the longer one.  MobileNet's 112 x 112 plane at batch 128 on 256 CUs:
 // R = 8 is 1792 bands on 1024 workgroups - two rounds of 10 rows where the mean is 1.75 - and R = 7 is 2048 bands, two rounds of 9.
+// The rule takes the vector instructions for the bound, which holds while something hides a latency: a band so large that only
+// ONE workgroup fits a CU leaves each SIMD a single wavefront, and every load of phase 1 and every fragment read of phase 2 is
+// waited for in full (128 channels at 56 x 56, batch 128: 7 rows - one workgroup per CU, 36 by the rule - take 125 us, 5 rows -
+// two per CU, 42 by the rule - 102 us: profiles/pair_chain_alone.txt).  So where some band leaves room for two workgroups, no
+// longer band is considered.
 // `lds_fixed`: what the launch needs beside the band buffer; `forced` > 0: that many rows (clamped), the tuning knob.
 // 0 when no band fits (the caller refuses the shape).
 inline int front_rows_pick(int64_t n, int64_t h, int64_t w, int cin, size_t lds_fixed, int num_cu, int wg_cap, int forced = 0) {
@@ -81,6 +89,11 @@ inline int front_rows_pick(int64_t n, int64_t h, int64_t w, int cin, size_t lds_
   while (rmax >= 1 && lds_fixed + front_band_bytes(q, rmax, cin) > (size_t)kStatLdsMax) --rmax;
   if (rmax < 1) return 0;
   if (forced > 0) return forced < rmax ? forced : rmax;
+  {
+    int r2 = rmax;
+    while (r2 >= 1 && stat_wg_per_cu(lds_fixed + front_band_bytes(q, r2, cin), wg_cap) < 2) --r2;
+    if (r2 >= 1) rmax = r2;
+  }
   double best = 1e30;
   int best_r = rmax;
   bool best_whole = false;

@@ -54,7 +54,12 @@ template <int KT, int S> struct PwDwRing {
 // (ReLU6 when `relu6`) behind both convolutions, unsigned activations (both clip ranges start at 0)
 // CODES 1: the input arrives as the codes the statistic pass left behind (`xc`: [n][2 KT][H * W][16] bytes, a lane's A fragment
 // of a pixel and a slab is one 16-byte vector of it) - x is not read, nothing is quantised on the input side
-template <int KT, int CW, int S, int LZ, int FAST, int CODES>
+// NS 1 (stride 1, code input): the STATISTIC mode of the launch - the depthwise output is computed, its per-sample maximum is
+// taken from the finished sums and nothing of it is stored (no LDS row buffer, no barrier per row); instead the codes of the
+// pointwise output, which the launch has just made for the stencil, leave as planar int8 (`y` is that buffer: [n][Cout][H * W]
+// bytes, 0 .. 255 or two's complement, what fq_dwconv3x3's statistic pass keeps of ITS input) for the front layer of the next
+// pair's statistic pass (pw_stat_kernel below), which recomputes the depthwise values from them.
+template <int KT, int CW, int S, int LZ, int FAST, int CODES, int NS = 0>
 __global__ __launch_bounds__(512) void pwdw_kernel(
     const float* __restrict__ x, const int8_t* __restrict__ xc, const int8_t* __restrict__ wfrag, const float* __restrict__ wscale,
     const int* __restrict__ wsum, const float* __restrict__ bias1, PwDwGeom g, const float* __restrict__ in_stat, int n,
@@ -64,6 +69,7 @@ __global__ __launch_bounds__(512) void pwdw_kernel(
     const float* __restrict__ bias2, const float* __restrict__ bn2_scale, const float* __restrict__ bn2_shift, int act2,
     float* __restrict__ y, float* __restrict__ stat_out) {
   constexpr int NB = CODES ? 1 : PwDwRing<KT, S>::NB, NR = CODES ? PwDwRing<KT, S>::NR : 1;
+  static_assert(!NS || (S == 1 && CODES == 1), "the statistic mode is built for stride 1 on code input");
   extern __shared__ __attribute__((aligned(16))) unsigned char pwdw_smem[];
   __shared__ float red[8];
   const int CT = g.ctg * CW;
@@ -73,7 +79,7 @@ __global__ __launch_bounds__(512) void pwdw_kernel(
   // stride 1 keeps two open sums per pixel: the depthwise layer's per-channel constants stay in LDS there (13 floats per channel:
   // an odd stride, every lane its own bank) and are read where they are used
   constexpr bool kDwLds = S == 1;
-  float* ldsK = rowbuf + 2 * rb_stride;                                                          // [Cout][13]
+  float* ldsK = NS ? reinterpret_cast<float*>(pwdw_smem + (size_t)CT * KT * 1024) : rowbuf + 2 * rb_stride;   // [Cout][13]
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int h = lane >> 5, i32 = lane & 31;
@@ -108,6 +114,26 @@ __global__ __launch_bounds__(512) void pwdw_kernel(
   const int t_first = S == 1 ? ro0 - 1 : 2 * ro0 - 1;
   const int t_last = S == 1 ? ro1 : 2 * (ro1 - 1) + 1;            // inclusive (may be H: a zero row)
   float* yb = y + (int64_t)smp * g.Cout * g.Ho * g.Wo;
+  // NS: where this lane's codes of a row go.  A lane holds the 16 columns c0 + 16 h - 1 .. c0 + 16 h + 14 of its channel, one
+  // column off a dword boundary, and permlane32_swap brings the column on either side.  c0 is even, W a multiple of four:
+  //   c0 = 0 mod 4:  own pixels 1 .. 12 are three aligned dwords at column c0 + 16 h; pixels 13 .. 15 and the upper half's
+  //                  pixel 0 a fourth one for the lower half, pixels 13, 14 an aligned pair for the upper half (column c0 + 30 is
+  //                  the next strip's);
+  //   c0 = 2 mod 4:  own pixels 3 .. 14 are three aligned dwords at column c0 + 2 + 16 h; the lower half's pixel 15 and pixels
+  //                  0 .. 2 a fourth one for the upper half, pixels 1, 2 an aligned pair for the lower half (column c0 - 1 is the
+  //                  previous strip's).
+  // Strips alternate between the two (c0 = 30 s), the anchored last one (c0 = W - 30) and the narrow plane (c0 = -2) are of the
+  // second kind: every column of the plane is written, the ones two strips share by both with the same byte, and the stencil's
+  // zero columns left and right of the plane (c0 - 1 < 0, c0 + 30 = W) by none.  Whole dwords / pairs lie inside a row or
+  // outside it (masked); the buffer descriptor covers this sample's planes only.
+  const bool ns_par2 = (c0 & 2) != 0;
+  const int ns_col3 = c0 + 16 * h + (ns_par2 ? 2 : 0);                       // the three dwords
+  const int ns_colx = ns_par2 ? (h ? c0 + 14 : c0) : c0 + 16 * h + 12;       // the fourth dword (ns_x4) or the pair
+  const bool ns_x4 = ns_par2 ? h == 1 : h == 0;
+  const bool ns_ok3 = ns_col3 >= 0 && ns_col3 + 12 <= g.W;
+  const bool ns_okx = ns_colx >= 0 && ns_colx + (ns_x4 ? 4 : 2) <= g.W;
+  const fq_rsrc rsy = make_rsrc(NS ? reinterpret_cast<int8_t*>(y) + (int64_t)smp * g.Cout * HW : nullptr,
+                                NS ? (int64_t)g.Cout * HW : 0);
 
   // slab q of the band = (row t_first + q / KT, 32-channel slab q % KT); buffer q % NB
   float raw[NB][16];
@@ -262,6 +288,7 @@ __global__ __launch_bounds__(512) void pwdw_kernel(
         auto finish_store = [&](const float (&sum)[NO]) __attribute__((always_inline)) {
           if (!emits) return;
           float* dst = rbuf + (ct * 32 + i32) * g.pitch + obase;
+          float mrow = 0.0f;                        // NS: the row's maximum over this lane's true outputs
           const float b2 = kDwLds ? kc[9] : k_b2[j], bsc2 = kDwLds ? kc[10] : k_bsc2[j], bsh2 = kDwLds ? kc[11] : k_bsh2[j];
 #pragma unroll
           for (int k = 0; k < NO; ++k) {
@@ -273,7 +300,12 @@ __global__ __launch_bounds__(512) void pwdw_kernel(
               o = o + bsh2;
               o = __builtin_amdgcn_fmed3f(o, 0.0f, top);      // = min(max(o, 0), top), a NaN gives 0 either way
             }
-            if (S == 1 && k == 0) {
+            if constexpr (NS != 0) {
+              // (own pixel 0 is an output of the upper half only, pixel 15 of the lower half only; the narrow plane's columns
+              // left of the image - pixels 0 .. LZ of the lower half - are none)
+              const bool is_out = k == 0 ? h == 1 : (k == NO - 1 ? h == 0 : (LZ == 0 || k > LZ || h == 1));
+              mrow = fmaxf(mrow, is_out ? fabsf(o) : 0.0f);
+            } else if (S == 1 && k == 0) {
               if (h == 1) dst[k] = o;
             } else if (k == NO - 1) {
               if (h == 0) dst[k] = o;
@@ -281,6 +313,7 @@ __global__ __launch_bounds__(512) void pwdw_kernel(
               dst[k] = o;
             }
           }
+          if constexpr (NS != 0) m = fmaxf(m, mrow);
         };
         if (!row_ok) {
           // a row of zero padding adds nothing to any sum (every product is +-0 and the sums are never -0): the row it
@@ -301,6 +334,7 @@ __global__ __launch_bounds__(512) void pwdw_kernel(
           continue;
         }
         float e[18];                                // dequantised pointwise outputs: e[k + 1] = own pixel k, e[0] / e[17] the neighbours'
+        float cf[NS ? 18 : 1];                      // NS: their codes (whole numbers), the same places
         {
           // (the re-centring term zoff * rowsum joins AFTER the multiplication: as the accumulator's initial value it is a
           // loop-invariant 16-register splat per channel tile, which the compiler keeps alive across the whole row loop)
@@ -322,13 +356,55 @@ __global__ __launch_bounds__(512) void pwdw_kernel(
                 v = v + k_bsh1[j];
               }
               v = act_rt(v, act1);
-              e[k + 1] = NN ? truncf(fast_quot(fq_clip(v, q2), fq2) + 0.49999997f) * q2.scale : fq_code(v, q2) * q2.scale;
+              const float code = NN ? truncf(fast_quot(fq_clip(v, q2), fq2) + 0.49999997f) : fq_code(v, q2);
+              e[k + 1] = code * q2.scale;
+              if constexpr (NS != 0) cf[k + 1] = code;
             } else {
               v = v * k_bsc1[j];
               v = v + k_bsh1[j];
               // clip(relu(v), 0, hi) = med3(v, 0, hi); the quotient is non-negative: roundf = trunc(Q + pred(0.5))
-              if (NN) e[k + 1] = truncf(fast_quot(fq_clip(v, qc), fq2) + 0.49999997f) * q2.scale;
-              else e[k + 1] = fq_code(act_rt(v, relu6 ? FQ_ACT_RELU6 : FQ_ACT_RELU), q2) * q2.scale;
+              const float code = NN ? truncf(fast_quot(fq_clip(v, qc), fq2) + 0.49999997f)
+                                    : fq_code(act_rt(v, relu6 ? FQ_ACT_RELU6 : FQ_ACT_RELU), q2);
+              e[k + 1] = code * q2.scale;
+              if constexpr (NS != 0) cf[k + 1] = code;
+            }
+          }
+          if constexpr (NS != 0) {
+            // the codes leave (above: which columns go where).  NN: they are 0 .. 255 and v_cvt_pk_u8_f32 puts one into its
+            // byte; else the low byte of the integer (two's complement for a signed quantiser)
+            const auto sc = __builtin_amdgcn_permlane32_swap(__float_as_uint(cf[1]), __float_as_uint(cf[16]), false, false);
+            cf[0] = __uint_as_float(sc[0]);
+            cf[17] = __uint_as_float(sc[1]);
+            auto pk4 = [&](float a, float b, float c, float d) __attribute__((always_inline)) {
+              if constexpr (NN) {
+                unsigned u = __builtin_amdgcn_cvt_pk_u8_f32(a, 0, 0u);
+                u = __builtin_amdgcn_cvt_pk_u8_f32(b, 1, u);
+                u = __builtin_amdgcn_cvt_pk_u8_f32(c, 2, u);
+                return (int)__builtin_amdgcn_cvt_pk_u8_f32(d, 3, u);
+              } else {
+                return (int)(((unsigned)(int)a & 255u) | (((unsigned)(int)b & 255u) << 8) | (((unsigned)(int)c & 255u) << 16) |
+                             ((unsigned)(int)d << 24));
+              }
+            };
+            typedef int v3i __attribute__((ext_vector_type(3)));
+            typedef unsigned v3u __attribute__((ext_vector_type(3)));
+            v3i d3;
+            int dx;
+            if (ns_par2) {
+              d3 = (v3i){pk4(cf[4], cf[5], cf[6], cf[7]), pk4(cf[8], cf[9], cf[10], cf[11]), pk4(cf[12], cf[13], cf[14], cf[15])};
+              dx = pk4(h ? cf[0] : cf[2], h ? cf[1] : cf[3], cf[2], cf[3]);
+            } else {
+              d3 = (v3i){pk4(cf[2], cf[3], cf[4], cf[5]), pk4(cf[6], cf[7], cf[8], cf[9]), pk4(cf[10], cf[11], cf[12], cf[13])};
+              dx = pk4(cf[14], cf[15], cf[16], cf[17]);
+            }
+            const unsigned rowb = (unsigned)((ct * 32 + i32) * HW + t * g.W);
+            if (ns_ok3) {
+              __builtin_amdgcn_raw_buffer_store_b96(__builtin_bit_cast(v3u, d3), rsy, (int)(rowb + (unsigned)ns_col3), 0, 0);
+              asm volatile("s_nop 1" : : "v"(d3));         // (fq_common.h at buf_st_v4f: the data registers of a wide store)
+            }
+            if (ns_okx) {
+              if (ns_x4) __builtin_amdgcn_raw_buffer_store_b32((unsigned)dx, rsy, (int)(rowb + (unsigned)ns_colx), 0, 0);
+              else __builtin_amdgcn_raw_buffer_store_b16((unsigned short)dx, rsy, (int)(rowb + (unsigned)ns_colx), 0, 0);
             }
           }
           // the zero padding of the depthwise layer: columns left / right of the image
@@ -404,7 +480,7 @@ __global__ __launch_bounds__(512) void pwdw_kernel(
         FQ_PIN();                                   // (one channel tile after the other: their registers need not coexist)
       }
       // ---- a finished output row leaves: LDS row buffer -> whole rows, 16 / 8 / 4 bytes per lane; its maximum on the way ----
-      if (emits) {
+      if (NS == 0 && emits) {
         __syncthreads();
         const unsigned per_row = g.qv.d;                      // vectors per channel row
         const int vecs = g.Cout * (int)per_row;
@@ -494,9 +570,9 @@ struct PwStatGeom {
 //      launch's quantiser (the threshold is known: the depthwise pass left its statistic), and the code byte goes to an LDS
 //      band buffer of four-channel planes (fq_front_layout.h: the order in which no store and no read meets a bank conflict).
 //      The transposition planar -> C16 happens here, on LDS bytes;
-//   2  the band buffer is read back as MFMA A fragments (four dword LDS reads per lane and 32-pixel tile: the 16 channels of the
-//      lane's pixel) and everything from there on is the kernel's own: the fragment leaves as x_codes_out, max / min of the
-//      int32 sums, flush per sample.
+//   2  the band buffer is read back as MFMA A fragments (four dword LDS reads per lane, slab and 32-pixel tile: the 16 channels
+//      32 kt + 16 h .. + 15 of the lane's pixel are planes 8 kt + 4 h .. + 3) and everything from there on is the kernel's own:
+//      the fragment leaves as x_codes_out (block 2 kt + h), max / min of the int32 sums, flush per sample.
 // A band is R <= kFrontRows output rows of one sample (all channels, whole rows): R + 2 input rows are dequantised for it
 // (front_rows_pick chooses R).  FSIGNED: the input codes are two's complement bytes (FQ_ACT_SIGNED), else 0 .. 255.
 struct PwFrontArgs {
@@ -517,7 +593,7 @@ __global__ __launch_bounds__(kBlock, 3) void pw_stat_kernel(
     const float* __restrict__ bn_scale, const float* __restrict__ bn_shift, int act, float* __restrict__ stat_out,
     int8_t* __restrict__ x_codes_out, PwFrontArgs fa) {
   constexpr bool FRONT = FEPI >= 0;
-  static_assert(!FRONT || KT == 1, "the front layer is built for one 32-channel slab");
+  static_assert(!FRONT || KT <= 4, "the front layer is built for up to four 32-channel slabs");
   extern __shared__ __attribute__((aligned(16))) unsigned char pst_smem[];
   v4i* ldsW = reinterpret_cast<v4i*>(pst_smem);                                           // [CT][KT][64]
   int* c_zs = reinterpret_cast<int*>(pst_smem + (size_t)g.CT * KT * 1024);                 // [CT * 32]
@@ -856,14 +932,18 @@ __global__ __launch_bounds__(kBlock, 3) void pw_stat_kernel(
       for (int tl = wave; tl < ntile; tl += 4) {
         int pp = tl * 32 + pl;
         pp = pp < npix ? pp : npix - 1;
-        // channels 16 h .. 16 h + 15 of pixel pp: byte 0 of planes 4 h .. 4 h + 3 (the half-slab past Cin has no planes)
+        // channels 32 kt + 16 h .. + 15 of pixel pp: byte 0 of planes 8 kt + 4 h .. + 3 (the half-slab past Cin has no planes)
         const unsigned* zp = reinterpret_cast<const unsigned*>(zbuf + front_byte(fa.lay, g.Cin <= 16 ? 0 : 16 * h, pp));
-        v4i f;
 #pragma unroll
-        for (int u = 0; u < 4; ++u) f[u] = (int)zp[u * fa.lay.pl];
-        if (g.Cin <= 16 && h == 1) f = zero_frag;            // (the half-slab past Cin: the code of 0)
-        if (wr_codes) buf_st_v4i(rcodes, ((smp * 2u + (unsigned)h) * HW + (unsigned)(r0 * W + pp)) * 16u, f);
-        afrag[0] = f;
+        for (int kt = 0; kt < KT; ++kt) {
+          v4i f;
+#pragma unroll
+          for (int u = 0; u < 4; ++u) f[u] = (int)zp[(8 * kt + u) * fa.lay.pl];
+          if (KT == 1 && g.Cin <= 16 && h == 1) f = zero_frag;     // (the half-slab past Cin: the code of 0)
+          if (wr_codes)
+            buf_st_v4i(rcodes, ((smp * (unsigned)(2 * KT) + (unsigned)(2 * kt + h)) * HW + (unsigned)(r0 * W + pp)) * 16u, f);
+          afrag[kt] = f;
+        }
         const int valid = npix - tl * 32;
         reduce_tile(0, valid < 32 ? valid : 32);
       }
@@ -925,7 +1005,9 @@ PwDwPlan pwdw_plan(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w, i
   // row buffers by LDS) in as few rounds as possible, a band re-computing the one or two pointwise rows above / below it.
   // (MobileNet1.0 at batch 128: 14 rows per band on the 56-row outputs - 512 workgroups - and 7 on the 28-row ones; measured
   // with 14 / 10 / 7: profiles/r6_pwdw_bands.txt)
-  static const int rb_env = env_int("FQ_PWDW_RB", 0);
+  // (FQ_PWDW_RB forces them; read at every call, like FQ_PWSTAT_FRONT_ROWS, so that a test can vary it inside one process)
+  const char* rb_e = getenv("FQ_PWDW_RB");
+  const int rb_env = rb_e != nullptr ? atoi(rb_e) : 0;
   {
     const int waves = p.threads / 64;
     int occ = (int)((160 * 1024) / (p.lds + 512));
@@ -973,12 +1055,14 @@ constexpr int kFrontWgCap = 4;          // (by registers: the front-layer instan
 static int pw_front_rows(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w) {
   const char* e = getenv("FQ_PWSTAT_FRONT_ROWS");
   static const int wg_env = env_int("FQ_PWSTAT_WG_PER_CU", 0);
-  const size_t fixed = pw_stat_lds(1, (int)((cout + 31) / 32)) + (size_t)cin * 12 * 4;
+  const size_t fixed = pw_stat_lds((int)((cin + 31) / 32), (int)((cout + 31) / 32)) + (size_t)cin * 12 * 4;
   return front_rows_pick(n, h, w, (int)cin, fixed, num_cu(), wg_env > 0 ? wg_env : kFrontWgCap, e != nullptr ? atoi(e) : 0);
 }
 
 bool pw_stat_front_shape_ok(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w) {
-  if (h < 1 || w < 4 || w % 4 != 0 || w / 4 > 64 || !(cin == 16 || cin == 32) || !pw_stat_shape_ok(n, cin, cout, h * w)) return false;
+  if (h < 1 || w < 4 || w % 4 != 0 || w / 4 > 64 || !(cin == 16 || cin == 32 || cin == 64 || cin == 128) ||
+      !pw_stat_shape_ok(n, cin, cout, h * w))
+    return false;
   // (the depthwise statistic pass in front must take the plane too: fq_dwconv3x3 without y)
   return pw_front_rows(n, cin, cout, h, w) >= 1 && n * cin * ((w / 4 + 61) / 62) < (1ll << 31) - 1024;
 }
@@ -1022,30 +1106,35 @@ int pw_stat_launch(const PwCall& c) {
                        c.out_current_max, c.bn_scale, c.bn_shift, c.act, c.stat_out, (int8_t*)c.x_codes_out, fa);          \
   } break;
   // front layer: the depthwise epilogue at compile time where fq_dwconv3x3 has it so, the signedness of its input codes
-#define FQ_PST_FRONT(EPI_, SG_)                                                                                            \
+#define FQ_PST_FRONT(KT_, EPI_, SG_)                                                                                       \
   {                                                                                                                        \
-    static const bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&pw_stat_kernel<1, EPI_, SG_>),          \
+    static const bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&pw_stat_kernel<KT_, EPI_, SG_>),        \
                                                     hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024) == hipSuccess; \
     FQ_REQUIRE(attr_ok, "fq_pwconv_i8_stat: cannot raise the dynamic LDS limit");                                          \
-    hipLaunchKernelGGL((pw_stat_kernel<1, EPI_, SG_>), dim3((unsigned)grid), dim3(kBlock), lds, c.st, c.x, c.wcodes,       \
+    hipLaunchKernelGGL((pw_stat_kernel<KT_, EPI_, SG_>), dim3((unsigned)grid), dim3(kBlock), lds, c.st, c.x, c.wcodes,     \
                        c.wscale, (const int*)c.wsum, c.bias, g, c.in_stat, (int)c.n, c.in_thr, c.levels, c.lo_neg, kEps,   \
                        c.out_current_max, c.bn_scale, c.bn_shift, c.act, c.stat_out, (int8_t*)c.x_codes_out, fa);          \
   }
-#define FQ_PST_FRONT_S(EPI_)                                                                                               \
+#define FQ_PST_FRONT_S(KT_, EPI_)                                                                                          \
   {                                                                                                                        \
-    if (c.front->is_signed) FQ_PST_FRONT(EPI_, true) else FQ_PST_FRONT(EPI_, false)                                        \
+    if (c.front->is_signed) FQ_PST_FRONT(KT_, EPI_, true) else FQ_PST_FRONT(KT_, EPI_, false)                              \
+  }
+#define FQ_PST_FRONT_E(KT_)                                                                                                \
+  {                                                                                                                        \
+    if (c.front->epi == kEpiBnRelu) FQ_PST_FRONT_S(KT_, kEpiBnRelu)                                                        \
+    else if (c.front->epi == kEpiBnRelu6) FQ_PST_FRONT_S(KT_, kEpiBnRelu6)                                                 \
+    else FQ_PST_FRONT_S(KT_, kEpiRuntime)                                                                                  \
   }
   if (c.front != nullptr) {
-    FQ_REQUIRE(kt == 1, "fq_pwconv_i8_stat: a front layer needs cin <= 32");
-    if (c.front->epi == kEpiBnRelu) FQ_PST_FRONT_S(kEpiBnRelu)
-    else if (c.front->epi == kEpiBnRelu6) FQ_PST_FRONT_S(kEpiBnRelu6)
-    else FQ_PST_FRONT_S(kEpiRuntime)
+    FQ_REQUIRE(kt == 1 || kt == 2 || kt == 4, "fq_pwconv_i8_stat: a front layer needs cin <= 128");
+    if (kt == 1) FQ_PST_FRONT_E(1) else if (kt == 2) FQ_PST_FRONT_E(2) else FQ_PST_FRONT_E(4)
   } else {
     switch (kt) {
       FQ_PST_GO(1) FQ_PST_GO(2) FQ_PST_GO(4) FQ_PST_GO(8)
       default: return fail(FQ_ERR_INVALID, "fq_pwconv_i8_stat: K / 32 = %d is not instantiated", kt);
     }
   }
+#undef FQ_PST_FRONT_E
 #undef FQ_PST_FRONT_S
 #undef FQ_PST_FRONT
 #undef FQ_PST_GO
@@ -1067,18 +1156,31 @@ int fq_debug_fast_quotient(const float* c, int64_t n, const float* d, float* out
   return FQ_OK;
 }
 
-int fq_pwdw_fused_supported(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w, int stride) {
+int fq_pwdw_fused_supported(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w, int stride, int stat_mode) {
+  if (stat_mode != 0 && !(stride == 1 && w % 4 == 0 && n * cout * h * w < (1ll << 31))) return 0;
   return pwdw_plan(n, cin, cout, h, w, stride).ok ? 1 : 0;
 }
 
-int fq_pwdw_fused(const float* x, const int8_t* wcodes, const float* wscale, const int32_t* wsum, const float* pw_bias,
-                  int64_t n, int64_t cin, int64_t cin_pad, int64_t cout_pad, int64_t cout, int64_t h, int64_t w,
-                  const float* in_stat, const float* in_thr, int in_width, unsigned in_flags, const float* pw_bn_scale,
-                  const float* pw_bn_shift, int pw_act, const float* mid_stat, const float* mid_thr, int mid_width,
-                  unsigned mid_flags, float* mid_current_max, const float* dw_w, const float* dw_bias, int dw_stride,
-                  const float* dw_bn_scale, const float* dw_bn_shift, int dw_act, float* y, float* stat_out,
-                  const void* x_codes, fqStream_t stream) {
-  FQ_REQUIRE((x || x_codes) && wcodes && wscale && wsum && dw_w && y, "fq_pwdw_fused: null pointer");
+}  // extern "C"
+
+// fq_pwdw_fused: y, or mid_codes_out instead of y - the statistic mode, NS of pwdw_kernel
+static int pwdw_fused_impl(const float* x, const int8_t* wcodes, const float* wscale, const int32_t* wsum, const float* pw_bias,
+                           int64_t n, int64_t cin, int64_t cin_pad, int64_t cout_pad, int64_t cout, int64_t h, int64_t w,
+                           const float* in_stat, const float* in_thr, int in_width, unsigned in_flags, const float* pw_bn_scale,
+                           const float* pw_bn_shift, int pw_act, const float* mid_stat, const float* mid_thr, int mid_width,
+                           unsigned mid_flags, float* mid_current_max, const float* dw_w, const float* dw_bias, int dw_stride,
+                           const float* dw_bn_scale, const float* dw_bn_shift, int dw_act, float* y, void* mid_codes_out,
+                           float* stat_out, const void* x_codes, fqStream_t stream) {
+  const bool ns = mid_codes_out != nullptr;
+  FQ_REQUIRE((x || x_codes) && wcodes && wscale && wsum && dw_w && (y || ns), "fq_pwdw_fused: null pointer");
+  if (ns) {
+    FQ_REQUIRE(y == nullptr && stat_out && x_codes && dw_stride == 1 && aligned16(mid_codes_out),
+               "fq_pwdw_fused: the statistic mode (mid_codes_out) wants y == NULL, stat_out, x_codes, stride 1 and a 16-byte aligned buffer");
+    FQ_REQUIRE(w % 4 == 0 && mid_width <= 8 && ((mid_flags & FQ_ACT_SIGNED) || !(mid_flags & FQ_ACT_LO_NEG_MAX)) &&
+                   n * cout * h * w < (1ll << 31) && cout * h * w < (1ll << 31) - 64,
+               "fq_pwdw_fused: statistic mode: shape or quantiser not taken (rows of whole dwords, codes that fit a byte): see "
+               "fq_pwdw_fused_supported(..., stat_mode = 1)");
+  }
   FQ_REQUIRE(in_stat != nullptr || in_thr != nullptr, "fq_pwdw_fused: give in_stat (online) or in_thr (offline)");
   FQ_REQUIRE(mid_stat != nullptr || mid_thr != nullptr, "fq_pwdw_fused: give mid_stat (the per-sample maxima of the pointwise "
              "output, from fq_pwconv_i8_stat) or mid_thr (a stored threshold)");
@@ -1093,7 +1195,7 @@ int fq_pwdw_fused(const float* x, const int8_t* wcodes, const float* wscale, con
   dw_act &= ~FQ_STAT_PREZEROED;
   FQ_REQUIRE(pw_act >= FQ_ACT_NONE && pw_act <= FQ_ACT_RELU6 && dw_act >= FQ_ACT_NONE && dw_act <= FQ_ACT_RELU6,
              "fq_pwdw_fused: unknown activation");
-  FQ_REQUIRE(aligned16(wcodes) && (x_codes ? aligned16(x_codes) : aligned16(x)) && aligned16(y),
+  FQ_REQUIRE(aligned16(wcodes) && (x_codes ? aligned16(x_codes) : aligned16(x)) && (ns || aligned16(y)),
              "fq_pwdw_fused: x (x_codes when given), wcodes and y must be 16-byte aligned");
   const PwDwPlan p = pwdw_plan(n, cin, cout, h, w, dw_stride);
   FQ_REQUIRE(p.ok, "fq_pwdw_fused: shape not taken (n=%lld cin=%lld cout=%lld %lldx%lld stride %d): see fq_pwdw_fused_supported",
@@ -1122,32 +1224,45 @@ int fq_pwdw_fused(const float* x, const int8_t* wcodes, const float* wscale, con
   // what the layer's arithmetic needs); moved: what the launch really reads and writes
   const double in_elems = (double)n * cin * h * w, mid_elems = (double)n * cout * h * w, out_elems = (double)n * cout * ho * wo;
   // (code input: 16 bytes per pixel and 16-channel block of whole 32-channel slabs instead of 4 per element)
+  // (the statistic mode stands for the same layer - the algorithmic bytes stay the layer's, DESIGN 3.7 - and moves the codes
+  // of its input out, the halo rows of every band twice, where the storing mode moves the output)
   const double in_moved = x_codes ? 32.0 * p.kt * (double)n * h * w : 4.0 * in_elems;
-  ProfScope prof(FQ_KERNEL_DWCONV, 4.0 * (mid_elems + out_elems), st, in_moved + 4.0 * out_elems);
+  const double out_moved = ns ? (double)n * cout * w * (h + 2.0 * (p.bands - 1)) : 4.0 * out_elems;
+  ProfScope prof(FQ_KERNEL_DWCONV, 4.0 * (mid_elems + out_elems), st, in_moved + out_moved);
   const int8_t* xc = static_cast<const int8_t*>(x_codes);
   const unsigned grid = (unsigned)(n * p.bands);
-#define FQ_PWDW_GO(KT_, CW_, S_, LZ_, F_, C_)                                                                               \
+  // (the statistic mode has no row buffers: weight fragments and the depthwise layer's constants only)
+  const size_t lds = ns ? (size_t)(cout / 32) * p.kt * 1024 + (size_t)cout * 13 * 4 : p.lds;
+  float* const y_arg = ns ? static_cast<float*>(mid_codes_out) : y;
+#define FQ_PWDW_GO(KT_, CW_, S_, LZ_, F_, C_, NS_)                                                                          \
   {                                                                                                                        \
-    static const bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&pwdw_kernel<KT_, CW_, S_, LZ_, F_, C_>), \
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) == hipSuccess; \
+    static const bool attr_ok =                                                                                            \
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&pwdw_kernel<KT_, CW_, S_, LZ_, F_, C_, NS_>),                    \
+                            hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) == hipSuccess;                         \
     FQ_REQUIRE(attr_ok, "fq_pwdw_fused: cannot raise the dynamic LDS limit");                                              \
-    hipLaunchKernelGGL((pwdw_kernel<KT_, CW_, S_, LZ_, F_, C_>), dim3(grid), dim3((unsigned)p.threads), p.lds, st, x, xc,   \
-                       wfrag, wscale, (const int*)wsum, pw_bias, g, in_stat, (int)n, in_thr, levels1, lo1, kEps,            \
+    hipLaunchKernelGGL((pwdw_kernel<KT_, CW_, S_, LZ_, F_, C_, NS_>), dim3(grid), dim3((unsigned)p.threads), lds, st, x,    \
+                       xc, wfrag, wscale, (const int*)wsum, pw_bias, g, in_stat, (int)n, in_thr, levels1, lo1, kEps,        \
                        pw_bn_scale, pw_bn_shift, pw_act, mid_stat, mid_thr, levels2, lo2, mid_current_max, dw_w, dw_bias,   \
-                       dw_bn_scale, dw_bn_shift, dw_act, y, stat_out);                                                     \
+                       dw_bn_scale, dw_bn_shift, dw_act, y_arg, stat_out);                                                 \
   }
 #define FQ_PWDW_C(KT_, CW_, S_, LZ_, F_)                                                                                    \
   {                                                                                                                        \
-    if (xc != nullptr) FQ_PWDW_GO(KT_, CW_, S_, LZ_, F_, 1) else FQ_PWDW_GO(KT_, CW_, S_, LZ_, F_, 0)                       \
+    if (xc != nullptr) FQ_PWDW_GO(KT_, CW_, S_, LZ_, F_, 1, 0) else FQ_PWDW_GO(KT_, CW_, S_, LZ_, F_, 0, 0)                 \
   }
 #define FQ_PWDW_F(KT_, CW_, S_, LZ_)                                                                                        \
   {                                                                                                                        \
     if (fast == 1) FQ_PWDW_C(KT_, CW_, S_, LZ_, 1) else FQ_PWDW_C(KT_, CW_, S_, LZ_, 0)                                     \
   }
+#define FQ_PWDW_N(KT_, CW_, LZ_)                                                                                            \
+  {                                                                                                                        \
+    if (fast == 1) FQ_PWDW_GO(KT_, CW_, 1, LZ_, 1, 1, 1) else FQ_PWDW_GO(KT_, CW_, 1, LZ_, 0, 1, 1)                         \
+  }
 #define FQ_PWDW_S(KT_, CW_)                                                                                                 \
   {                                                                                                                        \
     if (dw_stride == 2) FQ_PWDW_F(KT_, CW_, 2, 0)                                                                          \
-    else if (p.lz == 0) FQ_PWDW_F(KT_, CW_, 1, 0) else FQ_PWDW_F(KT_, CW_, 1, 2)                                            \
+    else if (ns) {                                                                                                         \
+      if (p.lz == 0) FQ_PWDW_N(KT_, CW_, 0) else FQ_PWDW_N(KT_, CW_, 2)                                                    \
+    } else if (p.lz == 0) FQ_PWDW_F(KT_, CW_, 1, 0) else FQ_PWDW_F(KT_, CW_, 1, 2)                                          \
   }
 #define FQ_PWDW_K(KT_)                                                                                                      \
   case KT_:                                                                                                                \
@@ -1159,11 +1274,26 @@ int fq_pwdw_fused(const float* x, const int8_t* wcodes, const float* wscale, con
   }
 #undef FQ_PWDW_K
 #undef FQ_PWDW_S
+#undef FQ_PWDW_N
 #undef FQ_PWDW_F
 #undef FQ_PWDW_C
 #undef FQ_PWDW_GO
   FQ_LAUNCH_CHECK();
   return FQ_OK;
+}
+
+extern "C" {
+
+int fq_pwdw_fused(const float* x, const int8_t* wcodes, const float* wscale, const int32_t* wsum, const float* pw_bias,
+                  int64_t n, int64_t cin, int64_t cin_pad, int64_t cout_pad, int64_t cout, int64_t h, int64_t w,
+                  const float* in_stat, const float* in_thr, int in_width, unsigned in_flags, const float* pw_bn_scale,
+                  const float* pw_bn_shift, int pw_act, const float* mid_stat, const float* mid_thr, int mid_width,
+                  unsigned mid_flags, float* mid_current_max, const float* dw_w, const float* dw_bias, int dw_stride,
+                  const float* dw_bn_scale, const float* dw_bn_shift, int dw_act, float* y, float* stat_out,
+                  const void* x_codes, fqStream_t stream, void* mid_codes_out) {
+  return pwdw_fused_impl(x, wcodes, wscale, wsum, pw_bias, n, cin, cin_pad, cout_pad, cout, h, w, in_stat, in_thr, in_width,
+                         in_flags, pw_bn_scale, pw_bn_shift, pw_act, mid_stat, mid_thr, mid_width, mid_flags, mid_current_max,
+                         dw_w, dw_bias, dw_stride, dw_bn_scale, dw_bn_shift, dw_act, y, mid_codes_out, stat_out, x_codes, stream);
 }
 
 }  // extern "C"

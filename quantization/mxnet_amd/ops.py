@@ -678,7 +678,7 @@ def pwdw_supported(xshape, cout, stride):
     n, cin, h, w = (int(v) for v in xshape)
     lib = _lib_()
     return bool(lib.fq_pwconv_i8_stat_supported(n, cin, int(cout), h * w, 0, 0)) and \
-        bool(lib.fq_pwdw_fused_supported(n, cin, int(cout), h, w, int(stride)))
+        bool(lib.fq_pwdw_fused_supported(n, cin, int(cout), h, w, int(stride), 0))
 
 
 def pwconv_front_supported(xshape, cout):
@@ -759,13 +759,27 @@ def pwconv_i8_stat(x, wcodes, wscale, wsum, bias=None, in_stat=None, in_thr=None
     return stat
 
 
+def pwdw_chain_supported(xshape, cout):
+    """True when `pwdw_fused(store=False, mid_codes_out=)` takes the pair (1x1 to `cout` channels, depthwise 3x3 of stride 1) on
+    an (N, Cin, H, W) input."""
+    n, cin, h, w = (int(v) for v in xshape)
+    lib = _lib_()
+    # (False under an older build of the library loaded through FQ_LIB_PATH, which ignores the trailing arguments: the storing
+    # launch remains)
+    return lib.fq_version() >= 102 and bool(lib.fq_pwdw_fused_supported(n, cin, int(cout), h, w, 1, 1))
+
+
 def pwdw_fused(x, wcodes, wscale, wsum, dw_w, pw_bias=None, in_stat=None, in_thr=None, width=8, flags=0, pw_bn_scale=None,
                pw_bn_shift=None, pw_act=None, mid_stat=None, mid_thr=None, mid_width=8, mid_flags=0, mid_cur_out=None,
-               dw_bias=None, stride=1, dw_bn_scale=None, dw_bn_shift=None, dw_act=None, want_stat=True, x_codes=None):
+               dw_bias=None, stride=1, dw_bn_scale=None, dw_bn_shift=None, dw_act=None, want_stat=True, x_codes=None,
+               store=True, mid_codes_out=None):
     """A fused 1x1 convolution and the depthwise 3x3 behind it in one launch (fq_pwdw_fused): the values of `pwconv_i8`
     followed by `dwconv3x3` with quantise-on-load, without the tensor between them.  `mid_stat`: the per-sample maxima of the
     1x1 output (`pwconv_i8_stat`), or `mid_thr`: a stored threshold.  `x_codes`: what `pwconv_i8_stat(x_codes_out=)` wrote for
-    this x and this in_stat / in_thr / width / flags - the launch reads it instead of x.  Returns (z, stat or None)."""
+    this x and this in_stat / in_thr / width / flags - the launch reads it instead of x.  Returns (z, stat or None).
+    `store=False` with `mid_codes_out` (int8, `front_codes_shape` of the 1x1 OUTPUT; stride 1, `x_codes` given): the statistic
+    mode (y == NULL) - z is computed, its per-sample maxima are taken, nothing of it is stored, and the codes of the
+    1x1 output are kept for `pwconv_i8_stat(front=)` of the pair behind; returns (None, stat)."""
     _check(x, "x")
     _check(wcodes, "wcodes", torch.int8)
     _check(wscale, "wscale")
@@ -788,14 +802,24 @@ def pwdw_fused(x, wcodes, wscale, wsum, dw_w, pw_bias=None, in_stat=None, in_thr
     if x_codes is not None:
         _check_pair_codes(x_codes, "x_codes", x)
     ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
-    y = torch.empty((n, cout, ho, wo), dtype=torch.float32, device=x.device)
+    if (mid_codes_out is None) == (not store):
+        raise ValueError("pwdw_fused keeps the codes of the 1x1 output in its statistic mode only: store=False and mid_codes_out "
+                         "go together")
+    if not store:
+        if not want_stat or stride != 1 or x_codes is None:
+            raise ValueError("pwdw_fused(store=False) wants want_stat, stride 1 and x_codes")
+        _check_front_codes(mid_codes_out, "mid_codes_out", (n, cout, h, w), x.device)
+        if not pwdw_chain_supported(x.shape, cout):
+            raise ValueError("pwdw_fused(store=False) does not take x %s -> %d channels: see pwdw_chain_supported"
+                             % (tuple(x.shape), cout))
+    y = torch.empty((n, cout, ho, wo), dtype=torch.float32, device=x.device) if store else None
     stat, zflag = _stat_target(n, x.device, want_stat)
     check_call(_lib_().fq_pwdw_fused(_ptr(x), _ptr(wcodes), _ptr(wscale), _ptr(wsum), _ptr(pw_bias), n, cin, cin_pad, cout_pad,
                                      cout, h, w, _ptr(in_stat), _ptr(in_thr), int(width), int(flags), _ptr(pw_bn_scale),
                                      _ptr(pw_bn_shift), _ACTS[pw_act], _ptr(mid_stat), _ptr(mid_thr), int(mid_width),
                                      int(mid_flags), _ptr(mid_cur_out), _ptr(dw_w), _ptr(dw_bias), int(stride),
                                      _ptr(dw_bn_scale), _ptr(dw_bn_shift), _ACTS[dw_act] | zflag, _ptr(y), _ptr(stat),
-                                     _ptr(x_codes), _stream(x)))
+                                     _ptr(x_codes), _stream(x), _ptr(mid_codes_out)))
     return y, stat
 
 

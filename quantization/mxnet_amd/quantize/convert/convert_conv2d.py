@@ -192,18 +192,19 @@ def _dwconv3x3(call, **more):
     return ops.dwconv3x3(kw.pop("x"), **kw, **more)
 
 
-def front_target(block, fz, x, plan):
+def front_target(block, fz, x, plan, level=None):
     """The fused 1x1 convolution behind this depthwise block when the block may run as a statistic pass that keeps its input's
     codes (fq_dwconv3x3 without y) and leave its values to that convolution's own statistic pass (fq_pwconv_i8_stat with a front
     layer; quantize/fuse.py links `front_pw`): the 1x1 is the first half of a recompute pair that is taken in this very forward
     (`recompute_target`), the forward is one of several batches in flight (`fuse.PAIR_FRONT`: where the saved bytes pay), this
     block quantises its input ONLINE with stride 1 and without a folded fake-BN, and nothing observes
     the tensor between the two (no hooks, no KL collection, no multi-GPU exchange of the 1x1's statistic).  Returns the 1x1 block
-    or None."""
+    or None.  `level`: the knob that decides in place of `fuse.PAIR_FRONT` (`chain_target`: `fuse.PAIR_CHAIN`)."""
     from .. import fuse as _fuse
     nxt = fz.get("front_pw")
-    # (FQ_PWDW_FRONT: 1 - among batches in flight, where it pays; 2 - in every forward)
-    if nxt is None or not _fuse.PAIR_CODES or not (int(_fuse.PAIR_FRONT) >= 2 or (_fuse.PAIR_FRONT and ops.in_flight())) \
+    level = int(_fuse.PAIR_FRONT) if level is None else int(level)
+    # (FQ_PWDW_FRONT / FQ_PWDW_CHAIN: 1 - among batches in flight, where it pays; 2 - in every forward)
+    if nxt is None or not _fuse.PAIR_CODES or not (level >= 2 or (level and ops.in_flight())) \
             or block._kwargs["stride"] != (1, 1) \
             or block.quantize_args.fake_bn or "in_stat" not in plan or "in_thr" in plan or plan["width"] > 8:
         return None
@@ -489,20 +490,41 @@ def recompute_target(block, fz, x, plan, c16_in):
     return nxt
 
 
+def _front_tensor(front):
+    """(tensor, statistic) of a depthwise block that ran as a statistic pass: its storing launch - fq_dwconv3x3 with the
+    arguments that pass had or, for the second half of a recompute pair (`chain_target`), the storing fused launch."""
+    return front["store"]() if front.get("store") is not None else _dwconv3x3(front["call"])
+
+
 def _materialise(x):
     """The tensor a deferred NDArray stands for, computed after all (its consumer turned out not to be the linked depthwise
     block in a state that takes it): the storing launch with the arguments the statistic pass had."""
     d = x._fq_deferred
     if d.get("kind") == "front":                         # (a depthwise block in front of a pair: its storing launch)
-        y, stat = _dwconv3x3(d["call"])
+        y, stat = _front_tensor(d)
     else:
         # (its own input may be a tensor that was not stored either: the depthwise block in front, `front`)
-        src = d["x"] if d.get("front") is None else _dwconv3x3(d["front"]["call"])[0]
+        src = d["x"] if d.get("front") is None else _front_tensor(d["front"])[0]
         y, stat = ops.pwconv_i8(src, *d["codes"], d["bias"], bn_scale=d["bn"][0], bn_shift=d["bn"][1], act=d["act"],
                                 **d["plan"])
     out = NDArray(y)
     out._fq_stat = stat
     return out
+
+
+def chain_target(block, fz, x, d, width):
+    """The fused 1x1 convolution behind the depthwise block of a recompute pair when that block's output need not be stored
+    either: the fused launch runs in its statistic mode (fq_pwdw_fused with mid_codes_out) and keeps the codes of ITS depthwise input - the 1x1
+    output it has just recomputed - and the next pair's statistic pass recomputes the depthwise values from them, exactly as
+    behind a depthwise block that stands alone (`front_target`, whose conditions these are, with `fuse.PAIR_CHAIN` as the knob).
+    On top: this pair hands its input over as codes and both kernels take the shape.  Returns the 1x1 block or None."""
+    from .. import fuse as _fuse
+    if d.get("x_codes") is None or fz.get("front_pw") is None:
+        return None
+    nxt = front_target(block, fz, x, dict(in_stat=x._fq_stat, width=width), level=_fuse.PAIR_CHAIN)
+    if nxt is None or not ops.pwdw_chain_supported(tuple(d["x"].shape), block._kwargs["num_filter"]):
+        return None
+    return nxt
 
 
 def depthwise_recompute(block, x, weight_q, bias, flags, width):
@@ -519,16 +541,33 @@ def depthwise_recompute(block, x, weight_q, bias, flags, width):
     if rows is not None and rows.device == src.device and rows.numel() >= n:
         rows[:n].copy_(stat)                              # (calibration under dist.py reads the statistic matrix back)
     p = d["plan"]
-    z, zstat = ops.pwdw_fused(src, *d["codes"], contiguous(weight_q._t), pw_bias=d["bias"], in_stat=p["in_stat"],
+    dw_w, dw_b = contiguous(weight_q._t), None if bias is None else bias._t
+
+    def fused(**more):
+        return ops.pwdw_fused(src, *d["codes"], dw_w, pw_bias=d["bias"], in_stat=p["in_stat"],
                               width=p["width"], flags=p["flags"], pw_bn_scale=d["bn"][0], pw_bn_shift=d["bn"][1],
                               pw_act=d["act"], mid_stat=stat, mid_width=width, mid_flags=flags, mid_cur_out=cur,
-                              dw_bias=None if bias is None else bias._t, stride=block._kwargs["stride"][0],
-                              dw_bn_scale=scale, dw_bn_shift=shift, dw_act=fz["act"], x_codes=d.get("x_codes"))
+                              dw_bias=dw_b, stride=block._kwargs["stride"][0],
+                              dw_bn_scale=scale, dw_bn_shift=shift, dw_act=fz["act"], x_codes=d.get("x_codes"), **more)
+    chain = chain_target(block, fz, x, d, width)
+    if chain is not None:
+        # statistic only, and the codes of the 1x1 output: the next pair's statistic pass recomputes this block's values from them
+        # (a fresh code buffer of the current stream per forward, like the pair's); any other reader gets the storing launch
+        oshape = tuple(x._t.shape)
+        ycodes = torch.empty(ops.front_codes_shape(oshape), dtype=torch.int8, device=src.device)
+        zstat = fused(store=False, mid_codes_out=ycodes)[1]
+        out = NDArray(_placeholder(oshape, src.device))
+        out._fq_stat = zstat
+        out._fq_deferred = dict(kind="front", consumer=chain, x_codes=ycodes, store=fused,
+                                call=dict(w=dw_w, bias=dw_b, bn_scale=scale, bn_shift=shift, act=fz["act"], in_stat=stat,
+                                          width=width, flags=flags))
+    else:
+        z, zstat = fused()
+        out = NDArray(z)
+        out._fq_stat = zstat
     if not side:
         block._fq_last_n = n
         block.current_input_max = DeviceScalar(cur)
-    out = NDArray(z)
-    out._fq_stat = zstat
     return out
 
 

@@ -176,6 +176,13 @@ PAIR_CODES = _os.environ.get("FQ_PWDW_CODES", "1") != "0"
 # (MobileNet0.5): DESIGN 3.7; an ordinary forward - calibration, a single evaluation - keeps the stored tensor, and every launch's
 # fp32 input stays observable there.  2: in every forward (A/B of one batch at a time).  0: never.
 PAIR_FRONT = int(_os.environ.get("FQ_PWDW_FRONT", "1"))
+# FQ_PWDW_CHAIN: the same one link further on - the stride-1 depthwise 3x3 that is the SECOND half of a recompute pair and feeds
+# the 1x1 of the next pair (MobileNet1.0: pair 2 -> pair 3, the 128-channel 56 x 56 tensor) is not stored either: the fused launch
+# runs in its statistic mode and keeps the codes of its own depthwise input (fq_pwdw_fused with mid_codes_out), the next pair's statistic pass
+# recomputes the depthwise values from them (convert_conv2d.chain_target; results identical either way).  Levels as
+# FQ_PWDW_FRONT: 1 - in forwards declared as batches in flight, 2 - in every forward, 0 - never.  DESIGN 3.7 has the measurements
+# behind the default.
+PAIR_CHAIN = int(_os.environ.get("FQ_PWDW_CHAIN", "1"))
 # Subsampled trunk (round 6, fq_pwconv_i8_sub2): the closing 1x1 of a ResNet-v1 stage stores only the pixels its two readers -
 # the next stage's first 1x1 and shortcut 1x1, both stride 2 without padding - look at (FQ_SUBSAMPLE=0: the whole tensor; A/B)
 SUBSAMPLE = _os.environ.get("FQ_SUBSAMPLE", "1") != "0"

@@ -1,12 +1,16 @@
 """The recompute pair alone on the GPU (round 6): fq_pwconv_i8 + fq_dwconv3x3 (two launches, the tensor between them written and
 read) against fq_pwconv_i8_stat + fq_pwdw_fused, on MobileNet1.0's pointwise -> depthwise pairs at batch 128.
 
-    python tools/pwdwbench.py [--batch 128] [--reps 30] [--pairs 1,2,3,4,5] [--codes 0] [--front 1]
+    python tools/pwdwbench.py [--batch 128] [--reps 30] [--pairs 1,2,3,4,5] [--codes 0] [--front 1] [--chain 1]
 
 --codes 1 (default): the statistic pass keeps the int8 codes of x and the fused launch loads them; 0: both read the fp32 x.
 --front 1: ONLY the table of the depthwise layer in front of the first pair - fq_dwconv3x3 (storing) + fq_pwconv_i8_stat against
 fq_dwconv3x3 without y (statistic pass, input codes kept) + fq_pwconv_i8_stat with that layer recomputed in front - on
 MobileNet1.0's and MobileNet0.5's dw1 -> pw1 at the batch size.
+--chain 1: ONLY the link between two pairs, pair 2 -> pair 3 - fq_pwdw_fused (storing z) + fq_pwconv_i8_stat reading it against
+fq_pwdw_fused in statistic mode (mid_codes_out: the codes of its depthwise input kept, no z) + fq_pwconv_i8_stat with the depthwise
+layer recomputed in front - on MobileNet1.0's and MobileNet0.5's shapes, the four launches alternating repetition by repetition.
+Under a library without the statistic mode (FQ_LIB_PATH = the parent's) the stored pair alone is timed.
 
 Per pair: time of each launch (HIP events on the launch stream, median over reps, all launches back to back), bytes each form
 moves, and the resulting TB/s.  Values are checked bit-equal before timing."""
@@ -93,6 +97,81 @@ def front_table(n, reps, dev):
               % ("", reps, sds[0], sds[1], sds[2], sds[3]))
 
 
+CHAINS = {"mobilenet1.0": (64, 128, 128, 56), "mobilenet0.5": (32, 64, 64, 56)}
+
+
+def chain_table(n, reps, dev):
+    has_new = ops.pwdw_chain_supported((n, 64, 56, 56), 128)
+    print("chain          shape                   stored: fused + stat = total (us)        chained: fused-stat + stat = total (us)   "
+          "MB moved stored / chained   speed-up")
+    for name, (cin, cmid, cout, hw) in CHAINS.items():
+        x = torch.relu(torch.randn(n, cin, hw, hw, device=dev)) * 1.7
+        w1 = ops.weight_codes(torch.randn(cmid, cin, device=dev) * 0.2, cmid, 8)
+        w2 = ops.weight_codes(torch.randn(cout, cmid, device=dev) * 0.2, cout, 8)
+        dww = ops.weight_fake_quant(torch.randn(cmid, 1, 3, 3, device=dev) * 0.3, cmid, 8)
+        bn = [(torch.rand(c, device=dev) + 0.5, torch.randn(c, device=dev) * 0.3) for c in (cmid, cmid, cout)]
+        xstat = ops.absmax_per_sample(x)
+        cur = [torch.zeros(1, device=dev) for _ in range(3)]
+        xc = torch.empty(ops.pair_codes_shape(x.shape), dtype=torch.int8, device=dev)
+        ystat = ops.pwconv_i8_stat(x, *w1, None, in_stat=xstat, cur_out=cur[0], bn_scale=bn[0][0], bn_shift=bn[0][1], act="relu",
+                                   x_codes_out=xc)
+        zshape = (n, cmid, hw, hw)
+        zc = [torch.empty(ops.pair_codes_shape(zshape), dtype=torch.int8, device=dev) for _ in range(2)]
+        yc = torch.empty(ops.front_codes_shape(zshape), dtype=torch.int8, device=dev)
+        fk = dict(in_stat=xstat, pw_bn_scale=bn[0][0], pw_bn_shift=bn[0][1], pw_act="relu", mid_stat=ystat, mid_cur_out=cur[1],
+                  stride=1, dw_bn_scale=bn[1][0], dw_bn_shift=bn[1][1], dw_act="relu", x_codes=xc)
+        pk = dict(cur_out=cur[2], bn_scale=bn[2][0], bn_shift=bn[2][1], act="relu")
+        st = {}
+
+        def fs():
+            st["z"], st["zs"] = ops.pwdw_fused(x, *w1, dww, **fk)
+
+        def sa():
+            st["ps"] = ops.pwconv_i8_stat(st["z"], *w2, None, in_stat=st["zs"], x_codes_out=zc[0], **pk)
+
+        def fn():
+            st["zs1"] = ops.pwdw_fused(x, *w1, dww, store=False, mid_codes_out=yc, **fk)[1]
+
+        def sf():
+            st["ps1"] = ops.pwconv_i8_stat(st["z"], *w2, None, in_stat=st["zs1"], x_codes_out=zc[1],
+                                           front=dict(x_codes=yc, w=dww, bn_scale=bn[1][0], bn_shift=bn[1][1], act="relu",
+                                                      in_stat=ystat), **pk)
+        fns = [fs, sa] + ([fn, sf] if has_new else [])
+        for f in fns:
+            f()
+        torch.cuda.synchronize()
+        ok = not has_new or (torch.equal(st["zs"], st["zs1"]) and torch.equal(st["ps"], st["ps1"]) and torch.equal(zc[0], zc[1]))
+        for _ in range(3):
+            for f in fns:
+                f()
+        ts = [[] for _ in fns]
+        for _ in range(reps):                              # alternating: every repetition times each launch once
+            for i, f in enumerate(fns):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                f()
+                b.record()
+                b.synchronize()
+                ts[i].append(a.elapsed_time(b) * 1e3)
+        med = [float(np.median(t)) for t in ts]
+        sds = [float(np.std(t)) for t in ts]
+        zb = 4e-6 * n * cmid * hw * hw                                    # z in fp32
+        xcb = 32e-6 * n * ((cin + 31) // 32) * hw * hw                    # the first pair's code buffer (read, with halo rows)
+        zcb = 32e-6 * n * ((cmid + 31) // 32) * hw * hw                   # the second pair's code buffer (written)
+        mb2, mb1 = xcb + zb + zb + zcb, xcb + zb / 4 + zb / 4 + zcb
+        if not has_new:
+            print("%-14s %3d->%3d->%3d @%3dx%-3d   %6.1f + %6.1f = %6.1f (%4.2f TB/s)        (this library has no statistic mode)"
+                  % (name, cin, cmid, cout, hw, hw, med[0], med[1], med[0] + med[1], mb2 / (med[0] + med[1])))
+            continue
+        print("%-14s %3d->%3d->%3d @%3dx%-3d   %6.1f + %6.1f = %6.1f (%4.2f TB/s)        %6.1f + %6.1f = %6.1f (%4.2f TB/s)          "
+              "%6.0f / %5.0f            %5.2fx  %s" % (name, cin, cmid, cout, hw, hw, med[0], med[1], med[0] + med[1],
+                                                    mb2 / (med[0] + med[1]), med[2], med[3], med[2] + med[3],
+                                                    mb1 / (med[2] + med[3]), mb2, mb1, (med[0] + med[1]) / (med[2] + med[3]),
+                                                    "bit-equal" if ok else "VALUES DIFFER"))
+        print("%-14s sd over the %d repetitions (us): fused %.2f  stat %.2f  fused-stat %.2f  stat with the front layer %.2f"
+              % ("", reps, sds[0], sds[1], sds[2], sds[3]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=128)
@@ -100,12 +179,16 @@ def main():
     ap.add_argument("--pairs", default="1,2,3,4,5")
     ap.add_argument("--codes", type=int, default=1)
     ap.add_argument("--front", type=int, default=0)
+    ap.add_argument("--chain", type=int, default=0)
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
     n = a.batch
     if a.front:
         front_table(n, a.reps, dev)
+        return
+    if a.chain:
+        chain_table(n, a.reps, dev)
         return
     print("pair  shape                          two launches: pw + dw = total (us)   recompute: stat + fused = total (us)   "
           "MB moved two / fused   speed-up")
