@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import poison
+import regimes as R
 from test_gpu_pwdw import N, _eq, _t
 
 pytestmark = pytest.mark.gpu
@@ -58,7 +59,10 @@ def _declined_threshold():
     raise AssertionError("no threshold found whose divisor has an all-ones significand")
 
 
-def _make(case, mode, seed=0):
+def _make(case, mode, seed=0, regime=None):
+    """`regime`: a value regime of tests/regimes.py on the depthwise layer's input as drawn (both quantisers in front of the
+    stored 1x1 threshold work online: `saturated` has no threshold to be stored in); `allones_divisor` is stored as the 1x1's
+    threshold."""
     n, cin, cout, h, w = case
     rng = np.random.default_rng(seed + 31 * cin + 7 * h + w)
     k = dict(case=case, mode=mode, s_front="s8_front" in mode or "s8_both" in mode, s_pw="s8_pw" in mode or "s8_both" in mode)
@@ -86,6 +90,14 @@ def _make(case, mode, seed=0):
     if k["s_pw"]:
         k["actA"] = None                                    # signed values reach the 1x1: its clip range is [-max, max]
     k["thrB"] = _declined_threshold() if "no_fast_quot" in mode else None
+    if regime is not None:
+        assert regime != "saturated"
+        k["y0"], _, rthr = R.apply(regime, k["y0"], k["s_front"])
+        if regime == "allones_divisor":
+            k["thrB"] = float(R.allones_threshold(k["s_pw"]))
+            assert R.has_allones_significand(R.divisor(k["thrB"], k["s_pw"]))
+        else:
+            R.check(regime, k["y0"], R.stored_threshold(k["y0"]), k["s_front"])
     return k
 
 
@@ -147,13 +159,13 @@ def _reference(case, mode, dev, ops):
     return _REFERENCE[key]
 
 
-def _compare(got, want, k):
+def _compare(got, want, k, regime=None):
     _eq(got["zstat"], want["zstat"], "per-sample statistic of the depthwise output")
     _eq(got["curA"], want["curA"], "current_input_max of the depthwise block")
     _eq(got["pstat"], want["pstat"], "statistic of the 1x1 output")
     _eq(got["curB"], want["curB"], "current_input_max of the 1x1 block")
     _eq(got["buf"], want["buf"], "code buffer of the depthwise output (every byte, the half-slab past Cin included)")
-    assert not k["y0"][-1].any() and np.abs(want["z"]).max() > 0 and want["pstat"].max() > 0
+    assert not k["y0"][-1].any() and (regime is not None or (np.abs(want["z"]).max() > 0 and want["pstat"].max() > 0))
 
 
 def _input_codes(k):

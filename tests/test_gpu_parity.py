@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from oracle import fq_oracle as O
+import regimes as R
 
 pytestmark = pytest.mark.gpu
 
@@ -380,14 +381,17 @@ def test_dwconv3x3_vs_oracle(dev, ops, shape, stride, mode):
     _dwconv_case(dev, ops, shape, stride, mode)
 
 
-def _dwconv_case(dev, ops, shape, stride, mode, twin=False):
-    """`twin`: also bit for bit against the host twin's true fmaf chain (the poisoned runs of tests/test_gpu_poison.py)."""
+def _dwconv_case(dev, ops, shape, stride, mode, twin=False, regime=None):
+    """`twin`: also bit for bit against the host twin's true fmaf chain (the poisoned runs of tests/test_gpu_poison.py).
+    `regime`: a value regime of tests/regimes.py on the data as drawn; the host twin is then the bit-for-bit reference."""
     rng = np.random.default_rng(sum(shape) * 7 + stride)
     n, c, h, w = shape
     x = (rng.standard_normal(shape) * 2).astype(np.float32)
     if "signed" not in mode:
         x = np.maximum(x, 0)
     wt = (rng.standard_normal((c, 1, 3, 3)) * 0.5).astype(np.float32)
+    x, _, rthr = R.apply(regime, x, "signed" in mode, width=4 if mode == "offline_signed" else 8)
+    twin = twin or regime is not None
     kw, okw = {}, {}
     if mode in ("online", "bn_relu_online"):
         stat = O.absmax_per_sample(x)
@@ -397,6 +401,11 @@ def _dwconv_case(dev, ops, shape, stride, mode, twin=False):
         thr = np.float32(1.7)
         kw.update(in_thr=T(np.float32([thr]), dev), width=4, flags=ops.act_flags(signed=True))
         okw.update(in_max=thr, signed=True, width=4)
+    if "in_max" in okw:
+        _regime_threshold(regime, rthr, kw, okw, dev, x)
+        R.check(regime, x, okw["in_max"], okw["signed"], width=okw["width"])
+    else:
+        assert regime not in ("saturated", "allones_divisor"), "a layer without a quantiser has no threshold"
     if mode == "bn_relu_online":
         sc = rng.uniform(0.3, 1.5, c).astype(np.float32)
         sh = rng.standard_normal(c).astype(np.float32)
@@ -412,14 +421,15 @@ def _dwconv_case(dev, ops, shape, stride, mode, twin=False):
     got = N(y)
     assert got.shape == want.shape
     np.testing.assert_allclose(got, want, rtol=1e-6, atol=1e-6)
-    assert (got != want).mean() < 1e-3                         # fmaf emulation differs only at double-rounding ties
+    if regime is None:
+        assert (got != want).mean() < 1e-3                     # fmaf emulation differs only at double-rounding ties
     _eq(N(stat_out), O.absmax_per_sample(got), "statistic of the produced output")
-    if "online" in mode:
+    if "in_stat" in kw:
         assert N(cur)[0] == okw["in_max"]
     if twin:
         from oracle import host as H
         hkw = dict(okw)
-        if "online" in mode:
+        if "in_stat" in kw:
             hkw.update(in_max=None, in_stat=stat)
         hy, hstat = H.dwconv3x3(x, wt, stride=stride, want_stat=True, **hkw)
         _eq(got, hy, "host twin")
@@ -430,7 +440,7 @@ def _dwconv_case(dev, ops, shape, stride, mode, twin=False):
                                                                 offline_threshold=okw["in_max"])[0]
     ref = TF.conv2d(torch.from_numpy(xq).double(), torch.from_numpy(wt).double(), None, stride=stride, padding=1,
                     groups=c).numpy()
-    if mode == "plain":
+    if mode == "plain" and regime is None:                    # (an absolute tolerance made for Gaussian data)
         np.testing.assert_allclose(got, ref, rtol=1e-5, atol=1e-5)
 
 
@@ -565,7 +575,19 @@ def test_pwconv_i8_every_form_vs_oracle(dev, ops, form, case, mode):
     _pwconv_case(dev, ops, case, mode, form=form)
 
 
-def _pwconv_case(dev, ops, case, mode, form=None):
+def _regime_threshold(regime, rthr, kw, okw, dev, x=None):
+    """A regime's own input threshold in the place of the driver's (or of its online statistic); a regime without one under
+    a driver that works with a stored threshold: the batch mean of `x`'s per-sample maxima, stored."""
+    if regime in R.INPUT and rthr is None and "in_stat" not in kw:
+        rthr = R.stored_threshold(x)
+    if regime is not None and rthr is not None:
+        kw.pop("in_stat", None)
+        kw["in_thr"] = T(np.float32([rthr]), dev)
+        okw["in_max"] = np.float32(rthr)
+
+
+def _pwconv_case(dev, ops, case, mode, form=None, regime=None):
+    """`regime`: a value regime of tests/regimes.py, applied to the data as drawn (tests/test_gpu_value_regimes.py)."""
     n, cin, cout, h, w = case
     rng = np.random.default_rng(sum(case))
     x = (rng.standard_normal((n, cin, h, w)) * 2).astype(np.float32)
@@ -574,6 +596,7 @@ def _pwconv_case(dev, ops, case, mode, form=None):
     wt = (rng.standard_normal((cout, cin, 1, 1)) * rng.uniform(0.05, 1.0, (cout, 1, 1, 1))).astype(np.float32)
     per_channel = "channel" in mode
     wt_width = 4 if "w4" in mode else 8
+    x, wt, rthr = R.apply(regime, x, not mode.startswith("online"), wt, 1 if per_channel else cout)
     codes, scales, rowsum = ops.weight_codes(T(wt, dev), 1 if per_channel else cout, wt_width)
     ocodes, oscales = O.weight_codes(wt, 1 if per_channel else cout, wt_width)
     _eq(N(codes)[:cout, :cin], ocodes.astype(np.int8), "weight codes")
@@ -593,6 +616,9 @@ def _pwconv_case(dev, ops, case, mode, form=None):
         stat = O.absmax_per_sample(x)
         kw.update(in_stat=T(stat, dev), width=8, flags=ops.act_flags(signed=True, lo_neg_max=False))
         okw.update(in_max=O.batch_mean(stat), signed=True, width=8, lo_neg_max=False)
+    _regime_threshold(regime, rthr, kw, okw, dev, x)
+    R.check(regime, x, okw["in_max"], okw["signed"], lo_neg_max=okw.get("lo_neg_max"), w=wt, rps=1 if per_channel else cout,
+            wt_width=wt_width)
     if "bn_relu" in mode:
         sc = rng.uniform(0.3, 1.5, cout).astype(np.float32)
         sh = rng.standard_normal(cout).astype(np.float32)
@@ -608,6 +634,8 @@ def _pwconv_case(dev, ops, case, mode, form=None):
     got = N(y)
     _eq(got, want, "pointwise int8 convolution (exact integer sums)")
     _eq(N(stat_out), O.absmax_per_sample(got), "statistic")
+    if regime is not None:
+        return                                               # (what follows is about Gaussian data under a threshold near its maximum)
     # the same layer through the reference's formulation (fp32 conv of the dequantised tensors): equal up to fp32 conv noise
     wq = O.weight_fake_quant(wt, "channel" if per_channel else "layer", wt_width)[0]
     xq = O.ste_forward(x, O.act_scale(okw["in_max"], okw["signed"], okw["width"]), okw["in_max"],
@@ -627,7 +655,7 @@ PW_RES_CASES = [("split", (2, 256, 1024, 14, 14)), ("split", (3, 512, 2048, 7, 7
 
 @pytest.mark.parametrize("form,case", PW_RES_CASES, ids=["%s-%dx%d->%d@%dx%d" % ((f,) + c) for f, c in PW_RES_CASES])
 @pytest.mark.parametrize("mode", ["online_u8_bn_relu", "offline_s8_channel_w4_bn_none"])
-def test_pwconv_i8_residual_vs_oracle(dev, ops, form, case, mode):
+def test_pwconv_i8_residual_vs_oracle(dev, ops, form, case, mode, regime=None):
     """The tail of a residual unit in the epilogue of its last 1x1 convolution: y = act(BN(conv) + shortcut) (ResNet: ReLU,
     MobileNetV2: no activation); partial channel tiles (24, 64 channels) included."""
     n, cin, cout, h, w = case
@@ -640,6 +668,9 @@ def test_pwconv_i8_residual_vs_oracle(dev, ops, form, case, mode):
     per_channel = "channel" in mode
     wt_width = 4 if "w4" in mode else 8
     rps = 1 if per_channel else cout
+    x, wt, rthr = R.apply(regime, x, "s8" in mode, wt, rps)
+    if regime in ("eps_scale", "tiny", "subnormal", "huge"):
+        res = R.apply(regime, res, True)[0]                  # the shortcut of such a unit carries such values as well
     codes, scales, rowsum = ops.weight_codes(T(wt, dev), rps, wt_width)
     kw, okw = {}, {}
     if mode.startswith("online"):
@@ -650,6 +681,8 @@ def test_pwconv_i8_residual_vs_oracle(dev, ops, form, case, mode):
         thr = np.float32(2.3)
         kw.update(in_thr=T(np.float32([thr]), dev), width=8, flags=ops.act_flags(signed=True))
         okw.update(in_max=thr, signed=True, width=8)
+    _regime_threshold(regime, rthr, kw, okw, dev, x)
+    R.check(regime, x, okw["in_max"], okw["signed"], w=wt, rps=rps, wt_width=wt_width)
     act = "relu" if "relu" in mode else None
     sc = rng.uniform(0.3, 1.5, cout).astype(np.float32)
     sh = rng.standard_normal(cout).astype(np.float32)
@@ -699,7 +732,7 @@ PW_S2_CASES = [(2, 256, 512, 14, 14), (3, 512, 1024, 7, 7), (2, 64, 128, 9, 11),
 
 @pytest.mark.parametrize("case", PW_S2_CASES, ids=["%dx%d->%d@%dx%d" % c for c in PW_S2_CASES])
 @pytest.mark.parametrize("mode", ["online_u8_bn_relu", "offline_s8_channel_w4"])
-def test_pwconv_i8_stride2_vs_oracle(dev, ops, case, mode):
+def test_pwconv_i8_stride2_vs_oracle(dev, ops, case, mode, regime=None):
     """The shortcut / first 1x1 convolutions of the ResNet stages: stride 2, no padding, odd and even planes.  The batch
     statistic is the one of the WHOLE input (what the reference's fake-quant in front of the convolution sees)."""
     n, cin, cout, h, w = case
@@ -711,6 +744,7 @@ def test_pwconv_i8_stride2_vs_oracle(dev, ops, case, mode):
     per_channel = "channel" in mode
     wt_width = 4 if "w4" in mode else 8
     rps = 1 if per_channel else cout
+    x, wt, rthr = R.apply(regime, x, "s8" in mode, wt, rps)
     codes, scales, rowsum = ops.weight_codes(T(wt, dev), rps, wt_width)
     kw, okw = {}, {}
     if mode.startswith("online"):
@@ -721,6 +755,8 @@ def test_pwconv_i8_stride2_vs_oracle(dev, ops, case, mode):
         thr = np.float32(2.3)
         kw.update(in_thr=T(np.float32([thr]), dev), width=8, flags=ops.act_flags(signed=True))
         okw.update(in_max=thr, signed=True, width=8)
+    _regime_threshold(regime, rthr, kw, okw, dev, x)
+    R.check(regime, x, okw["in_max"], okw["signed"], w=wt, rps=rps, wt_width=wt_width)
     if "bn_relu" in mode:
         sc = rng.uniform(0.3, 1.5, cout).astype(np.float32)
         sh = rng.standard_normal(cout).astype(np.float32)
@@ -777,7 +813,7 @@ C3_CASES = [  # (n, cin, cout, h, w): every K/32 (2, 4, 8, 16), both wavefront a
 
 @pytest.mark.parametrize("case", C3_CASES, ids=["%dx%d->%d@%dx%d" % c for c in C3_CASES])
 @pytest.mark.parametrize("mode", ["online_u8_bn_relu", "offline_s8_channel_w4", "online_s8_bias"])
-def test_conv3x3_i8_vs_oracle(dev, ops, case, mode):
+def test_conv3x3_i8_vs_oracle(dev, ops, case, mode, regime=None):
     n, cin, cout, h, w = case
     rng = np.random.default_rng(sum(case) + 7)
     x = (rng.standard_normal((n, cin, h, w)) * 2).astype(np.float32)
@@ -787,6 +823,7 @@ def test_conv3x3_i8_vs_oracle(dev, ops, case, mode):
     per_channel = "channel" in mode
     wt_width = 4 if "w4" in mode else 8
     rps = 1 if per_channel else cout
+    x, wt, rthr = R.apply(regime, x, "s8" in mode, wt, rps)
     codes, scales, rowsum = ops.weight_codes_3x3(T(wt, dev), rps, wt_width)
     ocodes, oscales = O.weight_codes(wt, rps, wt_width)
     _eq(N(scales), oscales, "weight scales")
@@ -803,6 +840,8 @@ def test_conv3x3_i8_vs_oracle(dev, ops, case, mode):
         thr = np.float32(2.3)
         kw.update(in_thr=T(np.float32([thr]), dev), width=8, flags=ops.act_flags(signed=True))
         okw.update(in_max=thr, signed=True, width=8)
+    _regime_threshold(regime, rthr, kw, okw, dev, x)
+    R.check(regime, x, okw["in_max"], okw["signed"], w=wt, rps=rps, wt_width=wt_width, taps=9)
     if "bn_relu" in mode:
         sc = rng.uniform(0.3, 1.5, cout).astype(np.float32)
         sh = rng.standard_normal(cout).astype(np.float32)
@@ -818,12 +857,14 @@ def test_conv3x3_i8_vs_oracle(dev, ops, case, mode):
     got = N(y)
     _eq(got, want, "dense 3x3 int8 convolution (exact integer sums)")
     _eq(N(stat_out), O.absmax_per_sample(got), "statistic")
-    if mode.startswith("online"):
+    if "in_stat" in kw:
         _eq(N(cur), np.float32([okw["in_max"]]), "current_input_max")
     # the host twin (full-size oracle of the net tests) agrees as well
     from oracle import host as H
     hy = H.conv3x3_i8(x, wt, rps, wt_width, **okw)
     _eq(hy, want, "host twin vs numpy oracle")
+    if regime is not None:
+        return                                               # (what follows is about Gaussian data under a threshold near its maximum)
     # the reference's formulation: fp32 convolution of the two dequantised tensors, equal up to fp32 summation noise
     wq = O.weight_fake_quant(wt, "channel" if per_channel else "layer", wt_width)[0]
     xq = O.ste_forward(x, O.act_scale(okw["in_max"], okw["signed"], okw["width"]), okw["in_max"],
@@ -841,7 +882,7 @@ C3S_CASES = [c for c in C3_CASES if c[2] % 32 == 0]
 
 @pytest.mark.parametrize("case", C3S_CASES, ids=["%dx%d->%d@%dx%d" % c for c in C3S_CASES])
 @pytest.mark.parametrize("mode", ["online_u8_bn_relu_wino", "offline_s8_bias"])
-def test_conv3x3_i8_sliced_vs_oracle(dev, ops, case, mode):
+def test_conv3x3_i8_sliced_vs_oracle(dev, ops, case, mode, regime=None):
     """fq_weight_slices + fq_conv3x3_i8_sliced (BASELINE config 5: filters under Winograd-domain quantisation are not on one
     integer grid per channel): the three int8 digit slices and their power-of-two scale against the oracle, the convolution
     bit for bit against the oracle's exact integer form, and within 2^-20 of the fp64 convolution of the very tensors the
@@ -859,6 +900,7 @@ def test_conv3x3_i8_sliced_vs_oracle(dev, ops, case, mode):
         wt[1] = 0.0                                      # an all-zero filter
         wt[2, 0, 0, 0] = np.float32(2.0) ** -3           # its maximum a power of two
         wt[2] = np.clip(wt[2], -0.125, 0.125)
+    x, wt, rthr = R.apply(regime, x, signed, wt, 1)
     codes, pscale, rowsum = ops.weight_slices_3x3(T(wt, dev))
     m, p = O.weight_slices(wt.transpose(0, 2, 3, 1).reshape(cout, -1))
     _eq(N(pscale), p, "per-channel power-of-two scale")
@@ -876,6 +918,8 @@ def test_conv3x3_i8_sliced_vs_oracle(dev, ops, case, mode):
         thr = np.float32(2.3)
         kw.update(in_thr=T(np.float32([thr]), dev), width=8, flags=ops.act_flags(signed=True))
         okw.update(in_max=thr, signed=True, width=8)
+    _regime_threshold(regime, rthr, kw, okw, dev, x)
+    R.check(regime, x, okw["in_max"], okw["signed"])
     if "bn_relu" in mode:
         sc = rng.uniform(0.3, 1.5, cout).astype(np.float32)
         sh = rng.standard_normal(cout).astype(np.float32)
@@ -891,7 +935,7 @@ def test_conv3x3_i8_sliced_vs_oracle(dev, ops, case, mode):
     got = N(y)
     _eq(got, want, "sliced dense 3x3 convolution (exact integer sums of three digit slices)")
     _eq(N(stat_out), O.absmax_per_sample(got), "statistic")
-    if "bn_relu" not in mode:
+    if "bn_relu" not in mode and regime is None:
         # against the real thing: fp64 convolution of the fake-quantised activations with the filter as given
         xq = O.ste_forward(x, O.act_scale(okw["in_max"], okw["signed"], 8), okw["in_max"],
                            -okw["in_max"] if okw["signed"] else 0.0)
@@ -1061,7 +1105,7 @@ DENSE_EVAL_CASES = [(128, 1024, 1000), (7, 64, 10), (70, 100, 37), (1, 512, 3), 
 
 @pytest.mark.parametrize("n,cin,units", DENSE_EVAL_CASES, ids=["%dx%d->%d" % c for c in DENSE_EVAL_CASES])
 @pytest.mark.parametrize("mode", ["online", "offline_channel_w4"])
-def test_dense_i8_eval_vs_oracle(dev, ops, n, cin, units, mode):
+def test_dense_i8_eval_vs_oracle(dev, ops, n, cin, units, mode, regime=None):
     """fq_dense_i8_eval = the classifier on the codes + the evaluation counters of its logits in ONE launch: logits equal the
     oracle's integer form, counters equal the oracle's counters of those logits, accumulated over three calls that reuse the
     library-side workspace (it must come back zeroed).  Ties (two identical weight rows: the first index wins, whichever
@@ -1078,6 +1122,8 @@ def test_dense_i8_eval_vs_oracle(dev, ops, n, cin, units, mode):
     b = rng.standard_normal(units).astype(np.float32)
     if units > 40:
         b[37] = b[6] = b[5] = np.float32(5)
+    if regime == "saturated" and units <= 40:
+        wt = R.saturate_rows(wt, 1 if per_channel else units)        # (above 40 units rows 5, 6, 37 tie for the maximum: kept)
     codes, scales, rowsum = ops.weight_codes(T(wt, dev), 1 if per_channel else units, wt_width)
     counters = torch.zeros(2 + 2 * units, device=dev)
     want_c = None
@@ -1093,6 +1139,7 @@ def test_dense_i8_eval_vs_oracle(dev, ops, n, cin, units, mode):
             x[2] = 0
             if units > 40:
                 labels[3] = 5                                         # units 5 / 6 / 37 tie for the maximum: 5 wins
+        x, _, rthr = R.apply(regime, x, False, thr=None if mode.startswith("online") else np.float32(3.1))
         kw, okw = {}, {}
         stat = O.absmax_per_sample(x)
         flags = ops.act_flags(signed=False, lo_neg_max=False)
@@ -1103,6 +1150,10 @@ def test_dense_i8_eval_vs_oracle(dev, ops, n, cin, units, mode):
             thr = np.float32(3.1)
             kw.update(in_thr=T(np.float32([thr]), dev), in_stat=T(stat, dev), width=8, flags=flags)
             okw.update(in_max=thr, signed=False, width=8)
+        if regime is not None and rthr is not None:                   # an offline regime: its threshold, the statistic on the side
+            kw.update(in_thr=T(np.float32([rthr]), dev), in_stat=T(stat, dev))
+            okw["in_max"] = np.float32(rthr)
+        R.check(regime, x, okw["in_max"], False)
         cur = torch.zeros(1, device=dev)
         y = ops.dense_i8_eval(T(x, dev), codes, scales, rowsum, torch.from_numpy(labels).to(dev), counters, bias=T(bias, dev),
                               cur_out=cur, **kw)

@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 import torch
 
+import regimes as R
+
 pytestmark = pytest.mark.gpu
 
 
@@ -53,7 +55,10 @@ MODES = ["online_u8_bn_relu", "online_u8_bn_relu6", "online_u8_bias_nobn", "onli
          "online_u8_w4_channel"]
 
 
-def _make(case, mode, dev, ops, seed=0):
+def _make(case, mode, dev, ops, seed=0, regime=None, allones=("in", "mid")):
+    """`regime`: a value regime of tests/regimes.py on the data as drawn.  One with a threshold of its own makes the pair an
+    offline one; `allones` names the thresholds - of the 1x1's input, of the tensor in the middle - that `allones_divisor`
+    replaces (the other keeps the driver's)."""
     n, cin, cout, h, w, stride = case
     rng = np.random.default_rng(seed + 17 * cin + h)
     signed = "s8" in mode
@@ -78,6 +83,20 @@ def _make(case, mode, dev, ops, seed=0):
     if "lo_neg" in mode:
         k["act1"] = None              # signed values reach the depthwise layer: its clip range is [-max, max]
     k["offline"] = "offline" in mode
+    k["thr1"], k["thr2"] = np.float32(4.25), np.float32(3.5)
+    x, w1, rthr = R.apply(regime, x, signed, w1, k["rps"], thr=k["thr1"] if k["offline"] else None)
+    if regime is not None and rthr is not None:
+        k["offline"] = True
+        if regime != "allones_divisor" or "in" in allones:
+            k["thr1"] = np.float32(rthr)
+        if regime == "allones_divisor" and "mid" in allones:
+            k["thr2"] = np.float32(rthr)
+    if regime == "allones_divisor":
+        assert allones and all(R.has_allones_significand(R.divisor(k[t], signed)) == (name in allones)
+                               for name, t in (("in", "thr1"), ("mid", "thr2")))
+    elif regime is not None:
+        R.check(regime, x, k["thr1"] if k["offline"] else R.stored_threshold(x), signed, w=w1, rps=k["rps"],
+                wt_width=k["wt_width"])
     k["x"], k["w1"], k["w2"] = x, w1, w2
     return k
 
@@ -101,8 +120,8 @@ def _run_pair(k, dev, ops, fused, codes_buf=None):
     cur2 = torch.zeros(1, device=dev)
     xstat = ops.absmax_per_sample(x)
     if k["offline"]:
-        thr1 = torch.full((1,), 4.25, device=dev)
-        thr2 = torch.full((1,), 3.5, device=dev)
+        thr1 = torch.full((1,), float(k["thr1"]), device=dev)
+        thr2 = torch.full((1,), float(k["thr2"]), device=dev)
         in1 = dict(in_thr=thr1, in_stat=xstat)
     else:
         thr2 = None
@@ -132,24 +151,24 @@ def _host_pair(k, ops, dev):
     bn1 = (None, None) if k["bn1"] is None else k["bn1"]
     bn2 = (None, None) if k["bn2"] is None else k["bn2"]
     off = k["offline"]
-    y, ystat = H.pwconv_i8(x, k["w1"], k["rps"], k["wt_width"], in_max=4.25 if off else None, in_stat=xstat, signed=k["signed"],
+    y, ystat = H.pwconv_i8(x, k["w1"], k["rps"], k["wt_width"], in_max=k["thr1"] if off else None, in_stat=xstat, signed=k["signed"],
                            bias=k["b1"], bn_scale=bn1[0], bn_shift=bn1[1], act=k["act1"], want_stat=True)
     w2 = N(ops.weight_fake_quant(_t(k["w2"], dev), cout, 8))
-    z, zstat = H.dwconv3x3(y, w2, k["b2"], stride, in_max=3.5 if off else None, in_stat=ystat, signed=k["signed"],
+    z, zstat = H.dwconv3x3(y, w2, k["b2"], stride, in_max=k["thr2"] if off else None, in_stat=ystat, signed=k["signed"],
                            bn_scale=bn2[0], bn_shift=bn2[1], act=k["act2"], want_stat=True)
     return dict(z=z, zstat=zstat, ystat=ystat)
 
 
 @pytest.mark.parametrize("case", CASES, ids=["%dx%d->%d@%dx%ds%d" % c for c in CASES])
 @pytest.mark.parametrize("mode", MODES)
-def test_pwdw_fused_equals_the_two_launches_and_the_host_twins(dev, ops, case, mode):
+def test_pwdw_fused_equals_the_two_launches_and_the_host_twins(dev, ops, case, mode, regime=None, allones=("in", "mid")):
     n, cin, cout, h, w, stride = case
     if not ops.pwdw_supported((n, cin, h, w), cout, stride):
         assert (h, w) == (8, 8), "an instantiated shape is refused: %s" % (case,)
         with pytest.raises(Exception):
             _run_pair(_make(case, mode, dev, ops), dev, ops, fused=True)
         return
-    k = _make(case, mode, dev, ops)
+    k = _make(case, mode, dev, ops, regime=regime, allones=allones)
     two = _run_pair(k, dev, ops, fused=False)
     one = _run_pair(k, dev, ops, fused=True)
     _eq(one["ystat"], two["ystat"], "statistic-only pass vs the storing pointwise kernel")
@@ -157,7 +176,7 @@ def test_pwdw_fused_equals_the_two_launches_and_the_host_twins(dev, ops, case, m
     _eq(one["cur2"], two["cur2"], "current_input_max of the depthwise block")
     _eq(one["z"], two["z"], "fused output vs the two launches")
     _eq(one["zstat"], two["zstat"], "fused per-sample statistic vs the two launches")
-    assert np.abs(one["z"]).max() > 0
+    assert regime is not None or np.abs(one["z"]).max() > 0
     host = _host_pair(k, ops, dev)
     _eq(one["ystat"], host["ystat"], "statistic-only pass vs host twin")
     _eq(one["z"], host["z"], "fused output vs host twins")

@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+import regimes as R
+
 pytestmark = pytest.mark.gpu
 
 
@@ -51,7 +53,8 @@ CASES = [
 MODES = ["online_u8_relu", "online_s8_none", "offline_u8_relu", "mixed_relu6_bias"]
 
 
-def _make(case, mode):
+def _make(case, mode, regime=None):
+    """`regime`: a value regime of tests/regimes.py, on both operands and both filter banks as drawn."""
     n, cin, cin2, cout, h, w = case
     rng = np.random.default_rng(cin + cin2 + h)
     signed = "s8" in mode
@@ -67,6 +70,14 @@ def _make(case, mode):
     k["bn2"] = ((0.5 + rng.random(cout)).astype(np.float32), (rng.standard_normal(cout) * 0.3).astype(np.float32))
     k["bias"] = (rng.standard_normal(cout) * 0.1).astype(np.float32) if "bias" in mode else None
     k["act"] = "relu6" if "relu6" in mode else ("relu" if "relu" in mode else None)
+    k["off1"], k["off2"] = "offline" in mode, "offline" in mode or "mixed" in mode
+    k["thr1"], k["thr2"] = np.float32(3.0), np.float32(4.5)
+    for a, wname, thr, off in (("x", "w", "thr1", "off1"), ("x2", "w2", "thr2", "off2")):
+        k[a], k[wname], rthr = R.apply(regime, k[a], signed, k[wname], 1, thr=k[thr] if k[off] else None)
+        if regime is not None and rthr is not None:
+            k[thr], k[off] = np.float32(rthr), True
+        if regime is not None:
+            R.check(regime, k[a], k[thr] if k[off] else R.O.batch_mean(R.O.absmax_per_sample(k[a])), signed, w=k[wname], rps=1)
     return k
 
 
@@ -78,10 +89,9 @@ def _run(k, dev, ops, fused):
     c2 = ops.weight_codes(_t(k["w2"], dev), 1, 8)
     st1, st2 = ops.absmax_per_sample(x), ops.absmax_per_sample(x2)
     cur1, cur2 = torch.zeros(1, device=dev), torch.zeros(1, device=dev)
-    offline1 = "offline" in k["mode"]
-    offline2 = "offline" in k["mode"] or "mixed" in k["mode"]
-    p1 = dict(in_thr=torch.full((1,), 3.0, device=dev), in_stat=st1) if offline1 else dict(in_stat=st1)
-    p2 = dict(in_thr=torch.full((1,), 4.5, device=dev), in_stat=st2) if offline2 else dict(in_stat=st2)
+    offline1, offline2 = k["off1"], k["off2"]
+    p1 = dict(in_thr=torch.full((1,), float(k["thr1"]), device=dev), in_stat=st1) if offline1 else dict(in_stat=st1)
+    p2 = dict(in_thr=torch.full((1,), float(k["thr2"]), device=dev), in_stat=st2) if offline2 else dict(in_stat=st2)
     bn, bn2 = (_t(k["bn"][0], dev), _t(k["bn"][1], dev)), (_t(k["bn2"][0], dev), _t(k["bn2"][1], dev))
     if not fused:
         s, _ = ops.pwconv_i8(x2, *c2, None, width=8, flags=flags, cur_out=cur2, bn_scale=bn2[0], bn_shift=bn2[1], act=None,
@@ -98,8 +108,8 @@ def _run(k, dev, ops, fused):
 
 @pytest.mark.parametrize("case", CASES, ids=["%dx%d+%d->%d@%dx%d" % c for c in CASES])
 @pytest.mark.parametrize("mode", MODES)
-def test_folded_shortcut_equals_the_two_launches_and_the_host_twin(dev, ops, case, mode):
-    k = _make(case, mode)
+def test_folded_shortcut_equals_the_two_launches_and_the_host_twin(dev, ops, case, mode, regime=None):
+    k = _make(case, mode, regime)
     got = _run(k, dev, ops, True)
     want = _run(k, dev, ops, False)
     for a, b, what in zip(got, want, ("output", "statistic", "current_input_max of the closing convolution",
@@ -107,11 +117,10 @@ def test_folded_shortcut_equals_the_two_launches_and_the_host_twin(dev, ops, cas
         _eq(a, b, what)
     from oracle import host as H
     n, cin, cin2, cout, h, w = case
-    off1 = "offline" in mode
-    off2 = "offline" in mode or "mixed" in mode
-    s = H.pwconv_i8(k["x2"], k["w2"].reshape(cout, cin2, 1, 1), 1, 8, in_max=4.5 if off2 else None,
+    off1, off2 = k["off1"], k["off2"]
+    s = H.pwconv_i8(k["x2"], k["w2"].reshape(cout, cin2, 1, 1), 1, 8, in_max=k["thr2"] if off2 else None,
                     in_stat=H.absmax_per_sample(k["x2"]), signed=k["signed"], bn_scale=k["bn2"][0], bn_shift=k["bn2"][1], act=None)
-    hy, hstat = H.pwconv_i8(k["x"], k["w"].reshape(cout, cin, 1, 1), 1, 8, in_max=3.0 if off1 else None,
+    hy, hstat = H.pwconv_i8(k["x"], k["w"].reshape(cout, cin, 1, 1), 1, 8, in_max=k["thr1"] if off1 else None,
                             in_stat=H.absmax_per_sample(k["x"]), signed=k["signed"], bias=k["bias"], bn_scale=k["bn"][0],
                             bn_shift=k["bn"][1], act=k["act"], want_stat=True, residual=s)
     _eq(got[0], hy, "host twins: output")
