@@ -54,8 +54,11 @@ FQ_FL_FN int front_byte(FrontLayout l, int c, int p) { return (((c >> 2) * l.pl 
 
 inline size_t front_band_bytes(int q, int rows, int cin) { return (size_t)((cin + 3) / 4) * front_layout(q, rows).pl * 4; }
 
-// phase 1: the channel of segment `seg` of wavefront `wave` in the turn that starts at channel c0 (4 * segs channels per turn)
+// phase 1: the channel of segment `seg` of wavefront `wave` in the turn that starts at channel c0 (waves * segs channels per
+// turn: a workgroup has kFrontWaves = 4 wavefronts, or kFrontWavesWide = 8 - front_waves_pick below)
 FQ_FL_FN int front_channel(int c0, int wave, int segs, int seg) { return c0 + wave * segs + seg; }
+
+constexpr int kFrontWaves = 4, kFrontWavesWide = 8;
 
 // the tile pixel of MFMA row i32 (row 8 g + 4 h + i holds pixel 16 h + 4 g + i: a lane's 16 registers are 16 consecutive pixels)
 FQ_FL_FN int mfma_row_pixel(int i32) { return 16 * ((i32 >> 2) & 1) + 4 * (i32 >> 3) + (i32 & 3); }
@@ -64,6 +67,12 @@ FQ_FL_FN int mfma_row_pixel(int i32) { return 16 * ((i32 >> 2) & 1) + 4 * (i32 >
 inline int stat_wg_per_cu(size_t lds, int cap) {
   const int by_lds = (int)((size_t)kStatLdsPerCU / (lds + 1024));
   return by_lds > cap ? cap : (by_lds < 1 ? 1 : by_lds);
+}
+
+// the cap on workgroups per CU for workgroups of `waves` wavefronts, from the cap for workgroups of four
+inline int stat_wg_cap(int cap4, int waves) {
+  const int cap = cap4 * kFrontWaves / waves;
+  return cap < 1 ? 1 : cap;
 }
 
 // Rows per band.  A band of R rows dequantises R + 2 input rows, and the n * ceil(h / R) bands go round by round over the
@@ -81,8 +90,25 @@ inline int stat_wg_per_cu(size_t lds, int cap) {
 // longer band is considered.
 // `lds_fixed`: what the launch needs beside the band buffer; `forced` > 0: that many rows (clamped), the tuning knob.
 // 0 when no band fits (the caller refuses the shape).
-inline int front_rows_pick(int64_t n, int64_t h, int64_t w, int cin, size_t lds_fixed, int num_cu, int wg_cap, int forced = 0) {
+// `waves`: wavefronts per workgroup.  What hides a latency is the wavefronts on a SIMD, workgroups * waves / 4, not the workgroups
+// on the CU: `wg_cap` counts workgroups of FOUR wavefronts (= wavefronts per SIMD the registers admit), a workgroup of eight
+// counts twice against it, and "room for two workgroups" above reads "two wavefronts per SIMD" - which ONE workgroup of eight is.
+// `lds_fixed` is the caller's figure for that many wavefronts (each has a max / min table).
+// Below four wavefronts per SIMD a row costs more: forced rows 1 .. 8 at both workgroup sizes (128 channels at 56 x 56, batch 128,
+// profiles/front_waves_sweep.txt) give 1.84-2.0 us per row of the rule at four wavefronts per SIMD and 2.2-2.4 us at two - eight
+// wavefronts on 5 rows (42 by the rule) take 84 us, on 7 rows (36, one workgroup per CU) 87 us.  Hence front_occupancy_cost: 1.2
+// at two wavefronts per SIMD and 1.0 at four are MEASURED; 1.1 at three is an interpolation that no sweep has covered.
+// Where the factor counts: among the bands of a workgroup of EIGHT, which holds two or four wavefronts per SIMD and nothing
+// else (the two measured points), and in front_waves_pick's comparison of the two workgroup sizes.  Among the bands of a
+// workgroup of four the rule is the plain one, so every pick of four wavefronts - 16 and 32 channels, odd shapes - is what it
+// was before there were workgroups of eight; the unmeasured 1.1 can tip the choice between four and eight wavefronts only.
+// `cost_out`: the cost of the choice with its factor, for front_waves_pick.
+inline double front_occupancy_cost(int waves_per_simd) { return waves_per_simd >= 4 ? 1.0 : (waves_per_simd == 3 ? 1.1 : 1.2); }
+
+inline int front_rows_pick(int64_t n, int64_t h, int64_t w, int cin, size_t lds_fixed, int num_cu, int wg_cap, int forced = 0,
+                           int waves = kFrontWaves, double* cost_out = nullptr) {
   const int q = (int)(w / 4);
+  wg_cap = stat_wg_cap(wg_cap, waves);
   int rmax = (int)(kFrontBandBytes / (32 * w));
   rmax = rmax > kFrontRows ? kFrontRows : rmax;
   rmax = rmax > h ? (int)h : rmax;
@@ -91,25 +117,83 @@ inline int front_rows_pick(int64_t n, int64_t h, int64_t w, int cin, size_t lds_
   if (forced > 0) return forced < rmax ? forced : rmax;
   {
     int r2 = rmax;
-    while (r2 >= 1 && stat_wg_per_cu(lds_fixed + front_band_bytes(q, r2, cin), wg_cap) < 2) --r2;
+    while (r2 >= 1 && stat_wg_per_cu(lds_fixed + front_band_bytes(q, r2, cin), wg_cap) * waves < 2 * 4) --r2;
     if (r2 >= 1) rmax = r2;
   }
-  double best = 1e30;
+  double best = 1e30, best_with_occ = 1e30;
   int best_r = rmax;
   bool best_whole = false;
   for (int r = rmax; r >= 1; --r) {
     const int64_t wgs = n * ((h + r - 1) / r);
-    const int64_t slots = (int64_t)num_cu * stat_wg_per_cu(lds_fixed + front_band_bytes(q, r, cin), wg_cap);
+    const int per_cu = stat_wg_per_cu(lds_fixed + front_band_bytes(q, r, cin), wg_cap);
+    const int64_t slots = (int64_t)num_cu * per_cu;
     const int64_t grid = wgs < slots ? wgs : slots, rounds = (wgs + grid - 1) / grid;
-    const double cost = (double)(rounds * ((grid + num_cu - 1) / num_cu) * (r + 2));
+    const double plain = (double)(rounds * ((grid + num_cu - 1) / num_cu) * (r + 2)), occ = front_occupancy_cost(per_cu * waves / 4);
+    const double cost = waves > kFrontWaves ? plain * occ : plain;
     const bool whole = (r * w) % 32 == 0;
     if (cost < best - 1e-9 || (cost < best + 1e-9 && whole && !best_whole)) {
       best = cost;
+      best_with_occ = plain * occ;
       best_r = r;
       best_whole = whole;
     }
   }
+  if (cost_out != nullptr) *cost_out = best_with_occ;
   return best_r;
+}
+
+// Wavefronts per workgroup.  The band buffer, the weights and the tables decide how many workgroups a CU holds, and with four
+// wavefronts each that is also the wavefronts per SIMD: two for 128 channels at 56 x 56 (5 rows), three or four for 64.  Eight
+// wavefronts on the same band fill the SIMDs without a shorter band's halo rows, and what a wavefront waits for - the loads of
+// phase 1, the fragment reads of phase 2, the barrier between them - is hidden by three others instead of one.  The choice is the
+// cheaper of the two by the rule above, each with its own rows: 128 channels - eight wavefronts on 5 rows (42 against 42 x 1.2),
+// 84 us where four took 96; 64 channels - eight on 7 rows (36 against 48 for four on 4 rows), 54.5 us against 60.5; 16 and 32
+// channels fit four workgroups of four anyway and have no instantiation of eight (profiles/front_waves_sweep.txt).
+// `lds_fixed4`, `lds_fixed8`: the fixed LDS of a launch with four and with eight wavefronts.
+inline int front_waves_pick(int64_t n, int64_t h, int64_t w, int cin, size_t lds_fixed4, size_t lds_fixed8, int num_cu, int wg_cap) {
+  double c4 = 0.0, c8 = 0.0;
+  const int r4 = front_rows_pick(n, h, w, cin, lds_fixed4, num_cu, wg_cap, 0, kFrontWaves, &c4);
+  const int r8 = front_rows_pick(n, h, w, cin, lds_fixed8, num_cu, wg_cap, 0, kFrontWavesWide, &c8);
+  return r8 >= 1 && (r4 < 1 || c8 < c4) ? kFrontWavesWide : kFrontWaves;
+}
+
+// LDS of the statistic pass beside a front layer's band: weight fragments, per-channel constants, one max / min table per
+// wavefront (kt, ct: 32-channel slabs of the input and of the output)
+inline size_t stat_fixed_lds(int kt, int ct, int waves = kFrontWaves) {
+  return (size_t)ct * kt * 1024 + 5 * (size_t)ct * 32 * 4 + (size_t)waves * ct * 128 * 4;
+}
+
+// ... and with a front layer: its weights, bias and BatchNorm constants, 12 floats per channel
+inline size_t front_fixed_lds(int64_t cin, int64_t cout, int waves) {
+  return stat_fixed_lds((int)((cin + 31) / 32), (int)((cout + 31) / 32), waves) + (size_t)cin * 12 * 4;
+}
+
+constexpr int kFrontWgCap = 4;          // (by registers: the front-layer instantiations fit four wavefronts per SIMD)
+
+// What a launch of the front-layer mode runs with: wavefronts per workgroup, rows per band (0: no band fits, the shape is
+// refused), its dynamic LDS.  Eight wavefronts are instantiated for 64 and 128 channels (16 and 32 leave a CU four workgroups of
+// four anyway); a shape whose band fits with four tables only stays with four, forced or not.
+// `forced_rows`, `forced_waves`: the tuning knobs (0: the rules above); `wg_cap`: kFrontWgCap unless a knob says otherwise.
+struct FrontPlan {
+  int waves, rows;
+  size_t lds;
+};
+inline FrontPlan front_plan(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w, int num_cu, int wg_cap = kFrontWgCap,
+                            int forced_rows = 0, int forced_waves = 0) {
+  FrontPlan p;
+  p.waves = kFrontWaves;
+  if (cin >= 64) {
+    if (forced_waves == kFrontWaves || forced_waves == kFrontWavesWide) p.waves = forced_waves;
+    else p.waves = front_waves_pick(n, h, w, (int)cin, front_fixed_lds(cin, cout, kFrontWaves),
+                                    front_fixed_lds(cin, cout, kFrontWavesWide), num_cu, wg_cap);
+  }
+  p.rows = front_rows_pick(n, h, w, (int)cin, front_fixed_lds(cin, cout, p.waves), num_cu, wg_cap, forced_rows, p.waves);
+  if (p.rows < 1 && p.waves != kFrontWaves) {
+    p.waves = kFrontWaves;
+    p.rows = front_rows_pick(n, h, w, (int)cin, front_fixed_lds(cin, cout, p.waves), num_cu, wg_cap, forced_rows, p.waves);
+  }
+  p.lds = p.rows >= 1 ? front_fixed_lds(cin, cout, p.waves) + front_band_bytes((int)(w / 4), p.rows, (int)cin) : 0;
+  return p;
 }
 
 }  // namespace fqi

@@ -585,8 +585,10 @@ struct PwFrontArgs {
   FrontLayout lay;                   // the band buffer's strides for (Q, R)
 };
 
-template <int KT, int FEPI = -1, bool FSIGNED = false>
-__global__ __launch_bounds__(kBlock, 3) void pw_stat_kernel(
+// NW: wavefronts of the workgroup - kBlock / 64 = 4, or (FRONT only) 8 on the same band where the band buffer leaves a CU too few
+// workgroups of four to fill its SIMDs (front_waves_pick).  Every wavefront has its own max / min table.
+template <int KT, int FEPI = -1, bool FSIGNED = false, int NW = kFrontWaves>
+__global__ __launch_bounds__(64 * NW, NW == kFrontWaves ? 3 : 2) void pw_stat_kernel(
     const float* __restrict__ x, const int8_t* __restrict__ wfrag, const float* __restrict__ wscale,
     const int* __restrict__ wsum, const float* __restrict__ bias, PwStatGeom g, const float* __restrict__ in_stat, int n,
     const float* __restrict__ in_thr, float levels, int lo_neg, float eps, float* __restrict__ cur_max_out,
@@ -594,17 +596,19 @@ __global__ __launch_bounds__(kBlock, 3) void pw_stat_kernel(
     int8_t* __restrict__ x_codes_out, PwFrontArgs fa) {
   constexpr bool FRONT = FEPI >= 0;
   static_assert(!FRONT || KT <= 4, "the front layer is built for up to four 32-channel slabs");
+  static_assert(NW * 64 == kBlock || (FRONT && NW == kFrontWavesWide), "four wavefronts; eight only with a front layer");
+  constexpr int kThreads = 64 * NW;
   extern __shared__ __attribute__((aligned(16))) unsigned char pst_smem[];
   v4i* ldsW = reinterpret_cast<v4i*>(pst_smem);                                           // [CT][KT][64]
   int* c_zs = reinterpret_cast<int*>(pst_smem + (size_t)g.CT * KT * 1024);                 // [CT * 32]
   float* c_k = reinterpret_cast<float*>(c_zs + g.CT * 32);                                 // [4][CT * 32]: w scale, bias, BN scale / shift
-  int* accs = reinterpret_cast<int*>(c_k + 4 * g.CT * 32);                                 // [4 waves][CT][2][64]
-  float* dwk = reinterpret_cast<float*>(accs + 4 * g.CT * 128);                             // FRONT: [Cin][12] taps, bias, BN scale / shift
+  int* accs = reinterpret_cast<int*>(c_k + 4 * g.CT * 32);                                 // [NW waves][CT][2][64]
+  float* dwk = reinterpret_cast<float*>(accs + NW * g.CT * 128);                            // FRONT: [Cin][12] taps, bias, BN scale / shift
   unsigned char* zbuf = reinterpret_cast<unsigned char*>(dwk + g.Cin * 12);                 // FRONT: [Cin / 4][lay.pl] dwords, band of codes
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int h = lane >> 5, i32 = lane & 31;
   const unsigned HW = (unsigned)g.HW, cols = (unsigned)g.cols;
-  const int64_t nwaves = (int64_t)gridDim.x * 4, wid = (int64_t)blockIdx.x * 4 + wave;
+  const int64_t nwaves = (int64_t)gridDim.x * NW, wid = (int64_t)blockIdx.x * NW + wave;
   // the wavefront's 32-pixel tiles - FRONT: the WORKGROUP's bands (band b of sample s is number s * bands + b)
   const int64_t n_bands = FRONT ? (int64_t)(g.cols / g.HW) * fa.bands : 0;
   const int64_t t_begin = FRONT ? n_bands * blockIdx.x / gridDim.x : g.tiles * wid / nwaves;
@@ -618,7 +622,7 @@ __global__ __launch_bounds__(kBlock, 3) void pw_stat_kernel(
   if constexpr (FRONT) {
     s_base = (unsigned)((t_begin < n_bands ? t_begin : n_bands - 1) / fa.bands);
   } else {
-    const int64_t t0 = g.tiles * ((int64_t)blockIdx.x * 4) / nwaves;
+    const int64_t t0 = g.tiles * ((int64_t)blockIdx.x * NW) / nwaves;
     const unsigned j0 = (unsigned)(t0 < g.tiles ? t0 : g.tiles - 1) * 32u;
     s_base = fast_div(j0 < cols ? j0 : cols - 1, g.hw);
   }
@@ -667,14 +671,14 @@ __global__ __launch_bounds__(kBlock, 3) void pw_stat_kernel(
   const unsigned nn_xor = fq_nonneg_xor(ubias);
   const bool wr_codes = x_codes_out != nullptr;
   const fq_rsrc rcodes = make_rsrc(x_codes_out, wr_codes ? (int64_t)(cols / HW) * 2 * KT * HW * 16 : 0);
-  for (int idx = threadIdx.x; idx < g.CT * KT * 64; idx += kBlock) {
+  for (int idx = threadIdx.x; idx < g.CT * KT * 64; idx += kThreads) {
     const int f = idx >> 6, ct = f / KT, kt = f - ct * KT;
     ldsW[idx] = *reinterpret_cast<const v4i*>(wfrag + (((int64_t)ct * g.KTS + kt) << 10) + ((idx & 63) << 4));
   }
   // (the epilogue's per-channel constants too: read from HBM inside flush() they cost every wavefront a memory latency per
   // channel tile and sample - a fixed 6-25 us that made the pass as slow at batch 32 as at batch 128)
   const int nchs = g.CT * 32;
-  for (int i = threadIdx.x; i < nchs; i += kBlock) {
+  for (int i = threadIdx.x; i < nchs; i += kThreads) {
     const bool okc = i < g.Cout;
     c_zs[i] = okc ? g.zoff * wsum[i] : 0;
     c_k[i] = okc ? wscale[i] : 0.0f;
@@ -683,7 +687,7 @@ __global__ __launch_bounds__(kBlock, 3) void pw_stat_kernel(
     c_k[3 * nchs + i] = (okc && bn_scale != nullptr) ? bn_shift[i] : 0.0f;
   }
   if constexpr (FRONT)
-    for (int i = threadIdx.x; i < g.Cin; i += kBlock) {
+    for (int i = threadIdx.x; i < g.Cin; i += kThreads) {
 #pragma unroll
       for (int t = 0; t < 9; ++t) dwk[i * 12 + t] = fa.w[i * 9 + t];
       dwk[i * 12 + 9] = fa.bias != nullptr ? fa.bias[i] : 0.0f;
@@ -865,7 +869,7 @@ __global__ __launch_bounds__(kBlock, 3) void pw_stat_kernel(
         cur = smp;
       }
       // ---- 1: the depthwise layer on rows r0 - 1 .. r0 + Rb of `segs` channels per wavefront and turn ----
-      for (int c0 = 0; c0 < g.Cin; c0 += 4 * fa.segs) {
+      for (int c0 = 0; c0 < g.Cin; c0 += NW * fa.segs) {
         const int c = front_channel(c0, wave, fa.segs, seg);
         const bool c_ok = seg < fa.segs && c < g.Cin;
         const int cc = c_ok ? c : 0;
@@ -929,7 +933,7 @@ __global__ __launch_bounds__(kBlock, 3) void pw_stat_kernel(
       __syncthreads();
       // ---- 2: the band's pixels as 32-pixel tiles (the last one may be short: its lanes past the band repeat the last pixel) ----
       const int npix = Rb * W, ntile = (npix + 31) >> 5;
-      for (int tl = wave; tl < ntile; tl += 4) {
+      for (int tl = wave; tl < ntile; tl += NW) {
         int pp = tl * 32 + pl;
         pp = pp < npix ? pp : npix - 1;
         // channels 32 kt + 16 h .. + 15 of pixel pp: byte 0 of planes 8 kt + 4 h .. + 3 (the half-slab past Cin has no planes)
@@ -1038,8 +1042,8 @@ PwDwPlan pwdw_plan(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w, i
 
 namespace fqi {
 
-// LDS of the statistic pass beside a front layer's: weight fragments, per-channel constants, the wavefronts' max / min
-static size_t pw_stat_lds(int kt, int ct) { return (size_t)ct * kt * 1024 + 5 * (size_t)ct * 32 * 4 + 4 * (size_t)ct * 128 * 4; }
+// LDS of the statistic pass beside a front layer's (fq_front_layout.h, where the host walk counts it too)
+static size_t pw_stat_lds(int kt, int ct, int waves = kFrontWaves) { return stat_fixed_lds(kt, ct, waves); }
 
 bool pw_stat_shape_ok(int64_t n, int64_t cin, int64_t cout, int64_t hw) {
   if (n <= 0 || cin <= 0 || cout <= 0 || hw < 32 || hw >= (1ll << 30) || n * hw >= (1ll << 31) - 512) return false;
@@ -1048,15 +1052,15 @@ bool pw_stat_shape_ok(int64_t n, int64_t cin, int64_t cout, int64_t hw) {
   return pw_stat_lds(kt, ct) <= (size_t)kStatLdsMax && n * cin * hw * 4 < (1ll << 32);
 }
 
-constexpr int kFrontWgCap = 4;          // (by registers: the front-layer instantiations fit four wavefronts per SIMD)
-
-// rows per band of the front-layer mode (front_rows_pick, fq_front_layout.h); FQ_PWSTAT_FRONT_ROWS forces them and is read at
-// every call, so that a test can vary it inside one process
-static int pw_front_rows(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w) {
+// wavefronts per workgroup, rows per band and LDS of the front-layer mode: front_plan of fq_front_layout.h.
+// FQ_PWSTAT_FRONT_ROWS and FQ_PWSTAT_FRONT_WAVES force the first two and are read at every call, so that a test can vary them
+// inside one process.
+static FrontPlan pw_front_plan(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w) {
   const char* e = getenv("FQ_PWSTAT_FRONT_ROWS");
+  const char* ew = getenv("FQ_PWSTAT_FRONT_WAVES");
   static const int wg_env = env_int("FQ_PWSTAT_WG_PER_CU", 0);
-  const size_t fixed = pw_stat_lds((int)((cin + 31) / 32), (int)((cout + 31) / 32)) + (size_t)cin * 12 * 4;
-  return front_rows_pick(n, h, w, (int)cin, fixed, num_cu(), wg_env > 0 ? wg_env : kFrontWgCap, e != nullptr ? atoi(e) : 0);
+  return front_plan(n, cin, cout, h, w, num_cu(), wg_env > 0 ? wg_env : kFrontWgCap, e != nullptr ? atoi(e) : 0,
+                    ew != nullptr ? atoi(ew) : 0);
 }
 
 bool pw_stat_front_shape_ok(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w) {
@@ -1064,38 +1068,41 @@ bool pw_stat_front_shape_ok(int64_t n, int64_t cin, int64_t cout, int64_t h, int
       !pw_stat_shape_ok(n, cin, cout, h * w))
     return false;
   // (the depthwise statistic pass in front must take the plane too: fq_dwconv3x3 without y)
-  return pw_front_rows(n, cin, cout, h, w) >= 1 && n * cin * ((w / 4 + 61) / 62) < (1ll << 31) - 1024;
+  return pw_front_plan(n, cin, cout, h, w).rows >= 1 && n * cin * ((w / 4 + 61) / 62) < (1ll << 31) - 1024;
 }
 
 int pw_stat_launch(const PwCall& c) {
   const int kt = (int)((c.cin + 31) / 32), ct = (int)((c.cout + 31) / 32);
   size_t lds = pw_stat_lds(kt, ct);
   PwFrontArgs fa = {};
+  int waves = kFrontWaves;
   if (c.front != nullptr) {
     const PwFront& f = *c.front;
     fa.codes = static_cast<const int8_t*>(f.codes);
     fa.w = f.w; fa.bias = f.bias; fa.bn_scale = f.bn_scale; fa.bn_shift = f.bn_shift;
     fa.in_stat = f.in_stat; fa.in_thr = f.in_thr; fa.levels = f.levels; fa.act = f.act;
     fa.H = (int)f.h; fa.W = (int)f.wdt; fa.Q = fa.W / 4; fa.segs = 64 / fa.Q;
-    fa.R = pw_front_rows(c.n, c.cin, c.cout, f.h, f.wdt);
+    const FrontPlan plan = pw_front_plan(c.n, c.cin, c.cout, f.h, f.wdt);
+    waves = plan.waves;
+    fa.R = plan.rows;
     FQ_REQUIRE(fa.R >= 1, "fq_pwconv_i8_stat: no band of the front layer fits the LDS");
     fa.bands = (fa.H + fa.R - 1) / fa.R;
     fa.lay = front_layout(fa.Q, fa.R);
-    lds += (size_t)c.cin * 12 * 4 + front_band_bytes(fa.Q, fa.R, (int)c.cin);
+    lds = plan.lds;
   }
   PwStatGeom g;
   g.Cin = (int)c.cin; g.KTS = (int)(c.cin_pad / 32); g.Cout = (int)c.cout; g.CT = ct; g.HW = (int)c.hw;
   g.cols = c.n * c.hw; g.tiles = (g.cols + 31) / 32; g.zoff = c.zoff;
   g.hw = fast_div_for((unsigned)c.hw);
   if (int rc = pw_zero_stat(c)) return rc;
-  int per_cu = stat_wg_per_cu(lds, c.front != nullptr ? kFrontWgCap : 3);
+  int per_cu = stat_wg_per_cu(lds, c.front != nullptr ? stat_wg_cap(kFrontWgCap, waves) : 3);
   static const int wg_env = env_int("FQ_PWSTAT_WG_PER_CU", 0);
   if (wg_env > 0) per_cu = wg_env;
   int64_t grid = (int64_t)num_cu() * per_cu;
   const int64_t need = c.front != nullptr ? c.n * fa.bands : (g.tiles + 3) / 4;
   if (grid > need) grid = need;
   static const int table_env = env_int("FQ_PWSTAT_TABLE", -1);
-  g.table = table_env >= 0 ? table_env : (g.tiles < grid * 4 * 10 ? 1 : 0);
+  g.table = table_env >= 0 ? table_env : (g.tiles < grid * waves * 10 ? 1 : 0);
 #define FQ_PST_GO(KT_)                                                                                                     \
   case KT_: {                                                                                                              \
     static const bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&pw_stat_kernel<KT_>),                   \
@@ -1106,14 +1113,23 @@ int pw_stat_launch(const PwCall& c) {
                        c.out_current_max, c.bn_scale, c.bn_shift, c.act, c.stat_out, (int8_t*)c.x_codes_out, fa);          \
   } break;
   // front layer: the depthwise epilogue at compile time where fq_dwconv3x3 has it so, the signedness of its input codes
-#define FQ_PST_FRONT(KT_, EPI_, SG_)                                                                                       \
+#define FQ_PST_FRONT_W(KT_, EPI_, SG_, NW_)                                                                                \
   {                                                                                                                        \
-    static const bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&pw_stat_kernel<KT_, EPI_, SG_>),        \
+    static const bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&pw_stat_kernel<KT_, EPI_, SG_, NW_>),   \
                                                     hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024) == hipSuccess; \
     FQ_REQUIRE(attr_ok, "fq_pwconv_i8_stat: cannot raise the dynamic LDS limit");                                          \
-    hipLaunchKernelGGL((pw_stat_kernel<KT_, EPI_, SG_>), dim3((unsigned)grid), dim3(kBlock), lds, c.st, c.x, c.wcodes,     \
-                       c.wscale, (const int*)c.wsum, c.bias, g, c.in_stat, (int)c.n, c.in_thr, c.levels, c.lo_neg, kEps,   \
-                       c.out_current_max, c.bn_scale, c.bn_shift, c.act, c.stat_out, (int8_t*)c.x_codes_out, fa);          \
+    hipLaunchKernelGGL((pw_stat_kernel<KT_, EPI_, SG_, NW_>), dim3((unsigned)grid), dim3(64 * NW_), lds, c.st, c.x,        \
+                       c.wcodes, c.wscale, (const int*)c.wsum, c.bias, g, c.in_stat, (int)c.n, c.in_thr, c.levels,         \
+                       c.lo_neg, kEps, c.out_current_max, c.bn_scale, c.bn_shift, c.act, c.stat_out,                       \
+                       (int8_t*)c.x_codes_out, fa);                                                                        \
+  }
+  // (eight wavefronts: instantiated where pw_front_plan can choose them, two and four slabs)
+#define FQ_PST_FRONT(KT_, EPI_, SG_)                                                                                       \
+  {                                                                                                                        \
+    if constexpr (KT_ >= 2) {                                                                                              \
+      if (waves == kFrontWavesWide) FQ_PST_FRONT_W(KT_, EPI_, SG_, kFrontWavesWide)                                        \
+      else FQ_PST_FRONT_W(KT_, EPI_, SG_, kFrontWaves)                                                                     \
+    } else FQ_PST_FRONT_W(KT_, EPI_, SG_, kFrontWaves)                                                                     \
   }
 #define FQ_PST_FRONT_S(KT_, EPI_)                                                                                          \
   {                                                                                                                        \
@@ -1137,6 +1153,7 @@ int pw_stat_launch(const PwCall& c) {
 #undef FQ_PST_FRONT_E
 #undef FQ_PST_FRONT_S
 #undef FQ_PST_FRONT
+#undef FQ_PST_FRONT_W
 #undef FQ_PST_GO
   FQ_LAUNCH_CHECK();
   return FQ_OK;

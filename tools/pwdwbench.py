@@ -1,7 +1,7 @@
 """The recompute pair alone on the GPU (round 6): fq_pwconv_i8 + fq_dwconv3x3 (two launches, the tensor between them written and
 read) against fq_pwconv_i8_stat + fq_pwdw_fused, on MobileNet1.0's pointwise -> depthwise pairs at batch 128.
 
-    python tools/pwdwbench.py [--batch 128] [--reps 30] [--pairs 1,2,3,4,5] [--codes 0] [--front 1] [--chain 1]
+    python tools/pwdwbench.py [--batch 128] [--reps 30] [--pairs 1,2,3,4,5] [--codes 0] [--front 1] [--chain 1] [--sweep 1]
 
 --codes 1 (default): the statistic pass keeps the int8 codes of x and the fused launch loads them; 0: both read the fp32 x.
 --front 1: ONLY the table of the depthwise layer in front of the first pair - fq_dwconv3x3 (storing) + fq_pwconv_i8_stat against
@@ -11,6 +11,10 @@ MobileNet1.0's and MobileNet0.5's dw1 -> pw1 at the batch size.
 fq_pwdw_fused in statistic mode (mid_codes_out: the codes of its depthwise input kept, no z) + fq_pwconv_i8_stat with the depthwise
 layer recomputed in front - on MobileNet1.0's and MobileNet0.5's shapes, the four launches alternating repetition by repetition.
 Under a library without the statistic mode (FQ_LIB_PATH = the parent's) the stored pair alone is timed.
+--sweep 1: with --front 1 or --chain 1, ONLY the statistic pass with the front layer, under FQ_PWSTAT_FRONT_ROWS = 1 .. 8 and
+FQ_PWSTAT_FRONT_WAVES = 4 and 8 (the library reads both at every call) and under the launch's own choice, all configurations
+alternating repetition by repetition in this one process; median +- standard deviation, every configuration's values compared
+with the first one's (the forced-rows blocks of profiles/front_waves_sweep.txt).
 
 Per pair: time of each launch (HIP events on the launch stream, median over reps, all launches back to back), bytes each form
 moves, and the resulting TB/s.  Values are checked bit-equal before timing."""
@@ -43,12 +47,53 @@ def timed(fn, reps):
     return float(np.median(ts))
 
 
+def sweep_front_stat(label, cin, run, result, reps):
+    """`run()`: the statistic pass with the front layer; `result()`: its outputs, to be compared.  One block of the table."""
+    waves = (4, 8) if cin >= 64 else (4,)
+    cfgs = [(w, r) for w in waves for r in range(1, 9)] + [(0, 0)]
+    ts, same, first = {c: [] for c in cfgs}, True, None
+
+    def under(c):
+        for name, v in (("FQ_PWSTAT_FRONT_WAVES", c[0]), ("FQ_PWSTAT_FRONT_ROWS", c[1])):
+            if v:
+                os.environ[name] = str(v)
+            else:
+                os.environ.pop(name, None)
+    for c in cfgs:                                         # warm-up, and the values of every configuration
+        under(c)
+        run()
+        run()
+        torch.cuda.synchronize()
+        got = [t.clone() for t in result()]
+        first = first or got
+        same = same and all(torch.equal(a, b) for a, b in zip(got, first))
+    for _ in range(reps):
+        for c in cfgs:
+            under(c)
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            run()
+            b.record()
+            b.synchronize()
+            ts[c].append(a.elapsed_time(b) * 1e3)
+    under((0, 0))
+    cell = lambda c: "%6.1f±%-4.1f" % (float(np.median(ts[c])), float(np.std(ts[c])))      # noqa: E731
+    print("== %s, %d alternating repetitions, values %s" % (label, reps, "bit-equal" if same else "DIFFER"))
+    print("   rows:     " + " ".join("%11d" % r for r in range(1, 9)))
+    for w in waves:
+        print("   %d waves:   " % w + " ".join(cell((w, r)) for r in range(1, 9)))
+    print("   the launch's own choice: " + cell((0, 0)))
+
+
 FRONTS = {"mobilenet1.0": (32, 64, 112), "mobilenet0.5": (16, 32, 112)}
 
 
-def front_table(n, reps, dev):
-    print("front          shape              stored: dw + stat = total (us)        recomputed: dw-stat + stat = total (us)   "
-          "MB moved stored / recomputed   speed-up")
+def front_table(n, reps, dev, sweep=False):
+    if sweep:
+        print("statistic pass with the front layer, forced rows per band and wavefronts per workgroup (us)")
+    else:
+        print("front          shape              stored: dw + stat = total (us)        recomputed: dw-stat + stat = total (us)   "
+              "MB moved stored / recomputed   speed-up")
     for name, (cin, cout, hw) in FRONTS.items():
         y0 = torch.relu(torch.randn(n, cin, hw, hw, device=dev)) * 1.7
         dww = ops.weight_fake_quant(torch.randn(cin, 1, 3, 3, device=dev) * 0.3, cin, 8)
@@ -81,6 +126,10 @@ def front_table(n, reps, dev):
         dw(); sa(); ds(); sf()
         torch.cuda.synchronize()
         ok = torch.equal(st["zs"], st["zs1"]) and torch.equal(st["ps"], st["ps1"]) and torch.equal(zc[0], zc[1])
+        if sweep:
+            sweep_front_stat("%s %d->%d @%d, batch %d%s" % (name, cin, cout, hw, n, "" if ok else ", VALUES DIFFER from the stored pair"),
+                             cin, sf, lambda: (st["ps1"], zc[1]), reps)
+            continue
         ts, sds = [], []
         for fn in (dw, sa, ds, sf):
             ts.append(timed(fn, reps))
@@ -100,7 +149,7 @@ def front_table(n, reps, dev):
 CHAINS = {"mobilenet1.0": (64, 128, 128, 56), "mobilenet0.5": (32, 64, 64, 56)}
 
 
-def chain_table(n, reps, dev):
+def chain_table(n, reps, dev, sweep=False):
     has_new = ops.pwdw_chain_supported((n, 64, 56, 56), 128)
     print("chain          shape                   stored: fused + stat = total (us)        chained: fused-stat + stat = total (us)   "
           "MB moved stored / chained   speed-up")
@@ -141,6 +190,10 @@ def chain_table(n, reps, dev):
             f()
         torch.cuda.synchronize()
         ok = not has_new or (torch.equal(st["zs"], st["zs1"]) and torch.equal(st["ps"], st["ps1"]) and torch.equal(zc[0], zc[1]))
+        if sweep and has_new:
+            sweep_front_stat("%s %d->%d @%d, batch %d%s" % (name, cmid, cout, hw, n, "" if ok else ", VALUES DIFFER from the stored pair"),
+                             cmid, sf, lambda: (st["ps1"], zc[1]), reps)
+            continue
         for _ in range(3):
             for f in fns:
                 f()
@@ -180,15 +233,16 @@ def main():
     ap.add_argument("--codes", type=int, default=1)
     ap.add_argument("--front", type=int, default=0)
     ap.add_argument("--chain", type=int, default=0)
+    ap.add_argument("--sweep", type=int, default=0)
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
     n = a.batch
     if a.front:
-        front_table(n, a.reps, dev)
+        front_table(n, a.reps, dev, bool(a.sweep))
         return
     if a.chain:
-        chain_table(n, a.reps, dev)
+        chain_table(n, a.reps, dev, bool(a.sweep))
         return
     print("pair  shape                          two launches: pw + dw = total (us)   recompute: stat + fused = total (us)   "
           "MB moved two / fused   speed-up")
