@@ -30,8 +30,9 @@ FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=
 
 
 # per-unit extras.  fq_pwdw: the SLP vectoriser packs the depthwise chains into v_pk_fma_f32 and pays two v_mov per pair for it
-# (a packed fp32 instruction costs about 1.7 plain ones on gfx950, profiles/r5_pk_probe.txt): 72 instead of 48 instructions
-UNIT_FLAGS = {"fq_pwdw": ["-fno-slp-vectorize"]}
+# (a packed fp32 instruction costs about 1.7 plain ones on gfx950, profiles/r5_pk_probe.txt): 72 instead of 48 instructions.
+# fq_pw_stat: its front mode's tap chains were compiled with the flag while the kernel lived in fq_pwdw, and keep it
+UNIT_FLAGS = {"fq_pwdw": ["-fno-slp-vectorize"], "fq_pw_stat": ["-fno-slp-vectorize"]}
 
 
 def hipcc():

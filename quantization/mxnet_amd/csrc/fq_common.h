@@ -9,18 +9,32 @@
 //                      K11 global average pool + statistic, K12 evaluation counters
 //   fq_dwconv.hip      K2c/K2d/K2e depthwise 3x3 with quantise-on-load (LDS tiles / 1 column per lane / 4 columns per lane),
 //                      K2o whole small planes in registers, K2p 14x14 / 7x7 planes as flat 16-byte ranges through an LDS transpose
+//   fq_dwconv16.hip    K2s depthwise 3x3 between two C16 code tensors
 //   fq_stem.hip        K2q / K2r first convolution 3x3 / 7x7 s2 on the fp32 matrix cores (K2r: input rows staged in LDS)
-//   fq_conv3x3.hip     K2n dense 3x3 on int8 codes (implicit GEMM over tap and channel)
+//   fq_stem_pool.hip   K2u first convolution 7x7 s2 + BatchNorm + activation + MaxPool 3x3 s2 in one kernel
+//   fq_conv3x3.hip     K2n dense 3x3 on int8 codes (implicit GEMM over tap and channel); fq_conv3x3_16.hip: its instantiations
+//                      with C16 code tensors on either side (the kernel: fq_conv3x3_kernel.h)
 //   fq_pw_stream.hip   K2h pointwise on int8 codes, weights resident in LDS (largest planes)
 //   fq_pw_sample.hip   K2r pointwise, one block of 96..128 pixels x 256 / 512 channels per workgroup, output-stationary
-//   fq_pw_split.hip    K2m pointwise, one (pixel tile, channel group) per workgroup: every other layer from 28x28 planes down
+//   fq_pw_split.hip    K2m pointwise, one (pixel tile, channel group) per workgroup: every other layer from 28x28 planes down;
+//                      fq_pw_split16.hip (C16 code tensors) and fq_pw_split_sub.hip (subsampled output): more instantiations of
+//                      the same kernel (fq_pw_split_kernel.h)
+//   fq_pw_short.hip    K2s the closing 1x1 of a residual unit with the unit's shortcut convolution in the same launch
+//   fq_pw_rows.hip     K2t pointwise on planes of one pixel: the classifier, optionally with its evaluation counters
 //   fq_pw_generic.hip  K2f pointwise for every other shape (quantise + transpose, then an integer GEMM)
 //   fq_mma.h           (header) what the kernels on v_mfma_i32_32x32x32_i8 share: statistic table, output quantiser
 //                      of a code output, epilogue choice, XCD work order, output windows (split, stream, 3x3, shortcut, generic)
+//   fq_pwdw.hip        K2y pointwise + the depthwise 3x3 behind it in one launch (fq_pwdw_fused: the recompute pair)
+//   fq_pw_stat.hip     K2z the statistic-only pass of a pointwise (fq_pwconv_i8_stat), optionally recomputing a depthwise 3x3
+//                      in front of it (the band buffer and the rows of a band: fq_front_layout.h)
+//   fq_pair.h          (header) what those two kernels share: the A fragment of sixteen fp32 values, the launchers' run-time
+//                      value -> integral_constant dispatch
 //   fq_pwconv.hip      fq_pwconv_i8: shape-based choice between the pointwise forms; the weight-code kernel (fq_weight_codes)
 //   fq_weights.hip     K3 weight fake-quant (layer / group / channel), generic STE, K4 Winograd-domain weights
 //   fq_calib.hip       K5 EMA, K6 global max, K7 histogram, K8 KL threshold search
 //   fq_codes.hip       K9 int-code quantise / dequantise, K10 exact int8 GEMM (nn.Conv2D(quantized=True))
+//   fq_qconv.hip       the stand-alone quantised convolution, nn.Conv2D(quantized=True), one entry point per forward
+//   fq_comm.hip        the collectives of multi-GPU calibration over RCCL
 //
 // Design rules applied throughout:
 //   * 64-wide wavefronts, 256-thread workgroups, 16 B per lane per access where the layout allows; streaming kernels keep
@@ -565,6 +579,13 @@ __device__ __forceinline__ bool fq_nonneg(const QParams& q) { return q.lo == 0.0
 __device__ __forceinline__ unsigned fq_nonneg_xor(int ubias) { return ubias == 0 ? 0x80808080u : 0u; }
 __device__ __forceinline__ int fq_code_nonneg(float x, const QParams& q) {
   const float Q = ieee_div_by(fq_clip(x, q), q.rden);
+  int r;
+  asm("v_cvt_rpi_i32_f32 %0, %1" : "=v"(r) : "v"(Q));
+  return r;
+}
+// ... with the fp32 quotient (fast_quot, where make_fast_quot() took the divisor): what the recompute pairs quantise with
+__device__ __forceinline__ int fq_code_nonneg(float x, const QParams& q, const FastQuot& f) {
+  const float Q = fast_quot(fq_clip(x, q), f);
   int r;
   asm("v_cvt_rpi_i32_f32 %0, %1" : "=v"(r) : "v"(Q));
   return r;

@@ -1,4 +1,4 @@
-// libfakequant - the band buffer of the front-layer statistic pass (fq_pwdw.hip: pw_stat_kernel with FEPI >= 0) and the rows
+// libfakequant - the band buffer of the front-layer statistic pass (fq_pw_stat.hip: pw_stat_kernel with FEPI >= 0) and the rows
 // a band gets.  Plain C++ as well as HIP: tests/front_layout_main.cpp compiles this file alone and walks every admitted shape.
 //
 // The buffer holds the codes of one band - R rows of W = 4 Q pixels, Cin channels - between the two phases of the kernel:

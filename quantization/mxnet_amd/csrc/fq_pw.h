@@ -66,7 +66,7 @@ struct PwCall {
   const PwFront* front = nullptr;   // fq_pwconv_i8_stat: x is not read but recomputed from this layer's input codes
 };
 
-// K2z  fq_pwdw.hip: the statistic-only pass (fq_pwconv_i8_stat): stat_out and out_current_max only, c.y is not touched
+// K2z  fq_pw_stat.hip: the statistic-only pass (fq_pwconv_i8_stat): stat_out and out_current_max only, c.y is not touched
 bool pw_stat_shape_ok(int64_t n, int64_t cin, int64_t cout, int64_t hw);
 bool pw_stat_front_shape_ok(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w);      // ... with a front layer
 int pw_stat_launch(const PwCall& c);

@@ -237,7 +237,7 @@ int fq_pwconv_i8(const float* x, const int8_t* wcodes, const float* wscale, cons
 }
 
 // The statistic-only pass in front of fq_pwdw_fused (round 6): the per-sample maxima fq_pwconv_i8 would leave in stat_out
-// (and its out_current_max) without computing, let alone storing, more of the output than its extreme sums (fq_pwdw.hip, K2z).
+// (and its out_current_max) without computing, let alone storing, more of the output than its extreme sums (fq_pw_stat.hip, K2z).
 int fq_pwconv_i8_stat_supported(int64_t n, int64_t cin, int64_t cout, int64_t hw, int64_t front_h, int64_t front_wdt) {
   if (front_h != 0 || front_wdt != 0)
     return (front_h > 0 && front_wdt > 0 && front_h * front_wdt == hw && pw_stat_front_shape_ok(n, cin, cout, front_h, front_wdt)) ? 1 : 0;

@@ -1,5 +1,5 @@
 // libfakequant — K2y: a pointwise (1x1) convolution on int8 codes AND the depthwise 3x3 behind it in one launch
-// (see fq_common.h for the list of translation units and the design rules)
+// (see fq_common.h for the list of translation units and the design rules; what it shares with fq_pw_stat.hip: fq_pair.h)
 //
 // Why (round 6): under ONLINE thresholds every fused producer writes its output in fp32 only for the next launch to read it
 // back - the batch statistic that scales the consumer's quantiser (convert_conv2d.py:56-58: mean over the batch of the
@@ -23,11 +23,7 @@
 // three products in the order of the row-major 3x3 chain (fq_dwconv3x3's arithmetic: fmaf by fmaf from +0).
 // A workgroup = all strips of a band x the channel groups; finished output rows go through an LDS row buffer (two rows) and
 // leave as whole rows, 16 bytes per lane.
-#include "fq_pw.h"
-
-#include "fq_front_layout.h"
-
-#include <climits>
+#include "fq_pair.h"
 
 namespace {
 
@@ -40,6 +36,16 @@ struct PwDwGeom {
 };
 
 constexpr int kRowSlack = 8;          // floats in front of each row buffer (a strip's invalid first column lands there)
+
+// The launch's dynamic LDS in bytes: [ct][kt][64] weight fragments; two row buffers of slack + cout * pitch floats with one more
+// slack in front (none of it in the statistic mode, which stores no rows); at stride 1 the depthwise layer's constants, 13
+// floats per channel.  The plan and the launcher size the launch with it; the kernel's pointers (ldsW, rowbuf, ldsK at its
+// top) are this order written out - taking the offsets from here keeps every count but changes 64 instruction sequences
+// (profiles/pair_units_one_of_each.txt).
+inline size_t pwdw_lds(int ct, int kt, int cout, int pitch, int stride, bool stat_mode) {
+  const size_t rows = stat_mode ? 0 : (size_t)(kRowSlack + 2 * (cout * pitch + kRowSlack)) * 4;
+  return (size_t)ct * kt * 1024 + rows + (stride == 1 ? (size_t)cout * 13 * 4 : 0);
+}
 
 // slabs in flight per lane: a ring of NB buffers of 16 values, the loads of slab q + NB - 1 issued before slab q is quantised
 // (stride 1 keeps 32 more partial sums per channel tile: two buffers there)
@@ -58,7 +64,7 @@ template <int KT, int S> struct PwDwRing {
 // taken from the finished sums and nothing of it is stored (no LDS row buffer, no barrier per row); instead the codes of the
 // pointwise output, which the launch has just made for the stencil, leave as planar int8 (`y` is that buffer: [n][Cout][H * W]
 // bytes, 0 .. 255 or two's complement, what fq_dwconv3x3's statistic pass keeps of ITS input) for the front layer of the next
-// pair's statistic pass (pw_stat_kernel below), which recomputes the depthwise values from them.
+// pair's statistic pass (pw_stat_kernel of fq_pw_stat.hip), which recomputes the depthwise values from them.
 template <int KT, int CW, int S, int LZ, int FAST, int CODES, int NS = 0>
 __global__ __launch_bounds__(512) void pwdw_kernel(
     const float* __restrict__ x, const int8_t* __restrict__ xc, const int8_t* __restrict__ wfrag, const float* __restrict__ wscale,
@@ -97,8 +103,7 @@ __global__ __launch_bounds__(512) void pwdw_kernel(
   int c0;
   if (S == 1) c0 = (s == g.strips - 1) ? g.W - 30 : 30 * s;      // (W < 30: one strip, c0 = -LZ)
   else c0 = 30 * s;
-  // A-operand pixel of this lane (MFMA row i32): p = 16 * ((i32 >> 2) & 1) + 4 * (i32 >> 3) + (i32 & 3)
-  const int pl = 16 * ((i32 >> 2) & 1) + 4 * (i32 >> 3) + (i32 & 3);
+  const int pl = mfma_row_pixel(i32);                             // A-operand pixel of this lane (MFMA row i32)
   int col_ld = c0 + pl - 1;
   col_ld = col_ld < 0 ? 0 : (col_ld >= g.W ? g.W - 1 : col_ld);
   const fq_rsrc rs = CODES ? make_rsrc(xc + (int64_t)smp * 2 * KT * HW * 16, (int64_t)2 * KT * HW * 16)
@@ -220,23 +225,6 @@ __global__ __launch_bounds__(512) void pwdw_kernel(
   // NN: both clip ranges start at 0 AND both divisors take the fp32 quotient (fq_common.h: fast_quot); else the general forms
   auto body = [&](auto nn_c) __attribute__((always_inline)) {
     constexpr bool NN = decltype(nn_c)::value;
-    auto pack_x = [&](float a, float b, float c, float d) __attribute__((always_inline)) {
-      if constexpr (NN) {
-        auto code = [&](float v) __attribute__((always_inline)) {
-          int r;
-          const float Q = fast_quot(fq_clip(v, q1), fq1);
-          asm("v_cvt_rpi_i32_f32 %0, %1" : "=v"(r) : "v"(Q));
-          return (unsigned)r;
-        };
-        unsigned u = code(a);
-        u |= code(b) << 8;
-        u |= code(c) << 16;
-        u |= code(d) << 24;
-        return (int)(u ^ nn_xor1);
-      } else {
-        return fq_pack4<false>(a, b, c, d, q1, ubias1, nn_xor1);
-      }
-    };
     // open partial sums: stride 1 - A (output row t-1: has its first two tap rows) and B (output row t: its first);
     // stride 2 - A only (8 outputs per lane)
     constexpr int NO = S == 1 ? 16 : 8;
@@ -267,13 +255,7 @@ __global__ __launch_bounds__(512) void pwdw_kernel(
           const int qn = kt + NB - 1;                                  // the slab NB - 1 ahead goes into the buffer freed last
           issue(t + qn / KT, qn % KT, raw[(PH * KT + kt + NB - 1) % NB]);
           FQ_PIN();
-          float (&mine)[16] = raw[(PH * KT + kt) % NB];
-          v4i f;
-#pragma unroll
-          for (int d = 0; d < 4; ++d)
-            f[d] = pack_x(mine[4 * d + 0], mine[4 * d + 1], mine[4 * d + 2], mine[4 * d + 3]);
-          asm volatile("" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]));
-          afrag[kt] = f;
+          afrag[kt] = pair_frag16<NN>(raw[(PH * KT + kt) % NB], q1, fq1, ubias1, nn_xor1);
           FQ_PIN();
         }
       }
@@ -533,440 +515,6 @@ __global__ __launch_bounds__(512) void pwdw_kernel(
   }
 }
 
-// K2z: the statistic-only pass of a pointwise convolution (fq_pwconv_i8_stat): stat_out[n] <- max |act(BN(conv))| over the
-// sample, nothing else leaves the chip.  Same operand roles as above (lane = output channel, registers = 16 pixels of a
-// 32-pixel tile), and ONE more observation: every step of the epilogue - int32 -> fp32, * sx*sw, + bias, * bn_scale, + bn_shift,
-// the activation - is a monotone function of the integer sum (rounding is monotone, a negative factor only turns the order
-// round), so the maximum of |act(BN(.))| over a set of pixels is attained at the largest or the smallest INTEGER sum of the
-// channel.  The kernel therefore keeps, per channel and sample, max and min of the int32 sums (v_max3 / v_min3: one
-// instruction per output value instead of the storing kernel's six) and runs the fp32 epilogue on those two only, once per
-// sample: bit for bit the statistic of fq_pwconv_i8.  That turns the pass from instruction-bound (3.5 TB/s as the storing
-// kernel without its stores) into a read of x.
-// x_codes_out (optional): the codes of x do exist once this pass has quantised them - lane (i32, h) holds, per slab kt, the 16
-// codes of ITS pixel's channels 32 kt + 16 h .. + 15 as the bytes of an MFMA A fragment, which is a C16 vector (fakequant.h).  The
-// lane stores it at [smp][2 kt + h][p][16]: fq_pwdw_fused's lane of the same pixel and slab loads it back with one instruction
-// instead of sixteen loads and sixteen quantisations.  The 32 lanes of a half write 512 contiguous bytes per instruction; the
-// lanes of a partial last tile, clamped to the last pixel, rewrite that pixel's own bytes.
-__device__ __forceinline__ void buf_st_v4i(fq_rsrc r, unsigned voff, v4i v) {
-  typedef unsigned v4u __attribute__((ext_vector_type(4)));
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, v), r, (int)voff, 0, 0);
-  asm volatile("s_nop 1" : : "v"(v));
-}
-
-struct PwStatGeom {
-  int Cin, KTS, Cout, CT, HW;
-  int64_t cols, tiles;
-  int zoff;
-  int table;                 // 1: per-sample maxima through the workgroup's LDS table (few tiles per wavefront)
-  FastDiv hw;
-};
-
-// FRONT (FEPI >= 0; fq_pwconv_i8_stat with a front layer): x is the output of a stride-1 depthwise 3x3 that was never stored.
-// Its INPUT arrives as planar int8 codes (fq_dwconv3x3's statistic pass kept them), and a workgroup recomputes x band by band:
-//   1  stencil, lane = (channel, four columns) as in fq_dwconv3x3's four-columns form (that is how the planar codes lie: one
-//      dword per lane and row, the horizontal neighbours by DPP from the adjacent lanes - a row of the plane is W / 4 <= 64
-//      lanes, so the plane's edge is the segment's edge and takes 0): dequantise (code * scale, once per element and band),
-//      the row-major fmaf chain, the layer's epilogue (kEpi* as there) - bit for bit what that kernel stores - then THIS
-//      launch's quantiser (the threshold is known: the depthwise pass left its statistic), and the code byte goes to an LDS
-//      band buffer of four-channel planes (fq_front_layout.h: the order in which no store and no read meets a bank conflict).
-//      The transposition planar -> C16 happens here, on LDS bytes;
-//   2  the band buffer is read back as MFMA A fragments (four dword LDS reads per lane, slab and 32-pixel tile: the 16 channels
-//      32 kt + 16 h .. + 15 of the lane's pixel are planes 8 kt + 4 h .. + 3) and everything from there on is the kernel's own:
-//      the fragment leaves as x_codes_out (block 2 kt + h), max / min of the int32 sums, flush per sample.
-// A band is R <= kFrontRows output rows of one sample (all channels, whole rows): R + 2 input rows are dequantised for it
-// (front_rows_pick chooses R).  FSIGNED: the input codes are two's complement bytes (FQ_ACT_SIGNED), else 0 .. 255.
-struct PwFrontArgs {
-  const int8_t* codes;               // [n][Cin][H * W]
-  const float *w, *bias, *bn_scale, *bn_shift;
-  const float *in_stat, *in_thr;     // the depthwise layer's input quantiser
-  float levels;
-  int act;
-  int H, W, Q, segs, R, bands;       // Q = W / 4 lanes per row, `segs` rows (channels) per wavefront, R output rows per band
-  FrontLayout lay;                   // the band buffer's strides for (Q, R)
-};
-
-// NW: wavefronts of the workgroup - kBlock / 64 = 4, or (FRONT only) 8 on the same band where the band buffer leaves a CU too few
-// workgroups of four to fill its SIMDs (front_waves_pick).  Every wavefront has its own max / min table.
-template <int KT, int FEPI = -1, bool FSIGNED = false, int NW = kFrontWaves>
-__global__ __launch_bounds__(64 * NW, NW == kFrontWaves ? 3 : 2) void pw_stat_kernel(
-    const float* __restrict__ x, const int8_t* __restrict__ wfrag, const float* __restrict__ wscale,
-    const int* __restrict__ wsum, const float* __restrict__ bias, PwStatGeom g, const float* __restrict__ in_stat, int n,
-    const float* __restrict__ in_thr, float levels, int lo_neg, float eps, float* __restrict__ cur_max_out,
-    const float* __restrict__ bn_scale, const float* __restrict__ bn_shift, int act, float* __restrict__ stat_out,
-    int8_t* __restrict__ x_codes_out, PwFrontArgs fa) {
-  constexpr bool FRONT = FEPI >= 0;
-  static_assert(!FRONT || KT <= 4, "the front layer is built for up to four 32-channel slabs");
-  static_assert(NW * 64 == kBlock || (FRONT && NW == kFrontWavesWide), "four wavefronts; eight only with a front layer");
-  constexpr int kThreads = 64 * NW;
-  extern __shared__ __attribute__((aligned(16))) unsigned char pst_smem[];
-  v4i* ldsW = reinterpret_cast<v4i*>(pst_smem);                                           // [CT][KT][64]
-  int* c_zs = reinterpret_cast<int*>(pst_smem + (size_t)g.CT * KT * 1024);                 // [CT * 32]
-  float* c_k = reinterpret_cast<float*>(c_zs + g.CT * 32);                                 // [4][CT * 32]: w scale, bias, BN scale / shift
-  int* accs = reinterpret_cast<int*>(c_k + 4 * g.CT * 32);                                 // [NW waves][CT][2][64]
-  float* dwk = reinterpret_cast<float*>(accs + NW * g.CT * 128);                            // FRONT: [Cin][12] taps, bias, BN scale / shift
-  unsigned char* zbuf = reinterpret_cast<unsigned char*>(dwk + g.Cin * 12);                 // FRONT: [Cin / 4][lay.pl] dwords, band of codes
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int h = lane >> 5, i32 = lane & 31;
-  const unsigned HW = (unsigned)g.HW, cols = (unsigned)g.cols;
-  const int64_t nwaves = (int64_t)gridDim.x * NW, wid = (int64_t)blockIdx.x * NW + wave;
-  // the wavefront's 32-pixel tiles - FRONT: the WORKGROUP's bands (band b of sample s is number s * bands + b)
-  const int64_t n_bands = FRONT ? (int64_t)(g.cols / g.HW) * fa.bands : 0;
-  const int64_t t_begin = FRONT ? n_bands * blockIdx.x / gridDim.x : g.tiles * wid / nwaves;
-  const int64_t t_end = FRONT ? n_bands * (blockIdx.x + 1) / gridDim.x : g.tiles * (wid + 1) / nwaves;
-  const int pl = mfma_row_pixel(i32);                                     // tile pixel of this lane's MFMA row
-  int* my = accs + (size_t)wave * g.CT * 128;
-  constexpr int kSlots = 8;
-  __shared__ unsigned k_stat[kSlots];
-  if (threadIdx.x < kSlots) k_stat[threadIdx.x] = 0u;
-  unsigned s_base;                               // first sample of the workgroup's tile range
-  if constexpr (FRONT) {
-    s_base = (unsigned)((t_begin < n_bands ? t_begin : n_bands - 1) / fa.bands);
-  } else {
-    const int64_t t0 = g.tiles * ((int64_t)blockIdx.x * NW) / nwaves;
-    const unsigned j0 = (unsigned)(t0 < g.tiles ? t0 : g.tiles - 1) * 32u;
-    s_base = fast_div(j0 < cols ? j0 : cols - 1, g.hw);
-  }
-
-  struct Pix { unsigned smp, p; };
-  auto pix_of = [&](int64_t t) __attribute__((always_inline)) {
-    unsigned j = (unsigned)t * 32u + (unsigned)pl;
-    j = j < cols ? j : cols - 1;                                          // (a copy of the last pixel: changes no maximum)
-    Pix r;
-    r.smp = fast_div(j, g.hw);
-    r.p = j - r.smp * HW;
-    return r;
-  };
-  // slab q of the wave's range = (tile t_begin + q / KT, 32-channel slab q % KT), kept in buffer q % NB; the loads of slab
-  // q + NB - 1 leave before slab q is quantised: NB - 1 slabs (4 KB each) in flight per wavefront, three wavefronts per SIMD.  One tile ahead - the first
-  // version - left every wavefront waiting a memory latency per tile (3.9 TB/s on the 205 MB tensor of the first pair).
-  constexpr int NB = 3;
-  const fq_rsrc rs = make_rsrc(x, (int64_t)(cols / HW) * g.Cin * HW * 4);
-  auto issue = [&](int64_t t, int kt, float (&v)[16]) __attribute__((always_inline)) {
-    if (t >= t_end) return;
-    const Pix px = pix_of(t);
-    // (a ragged half-slab: channels past Cin are out of the buffer's range only for the LAST sample - clamp and zero instead)
-    // (a half-slab past Cin: an offset out of the buffer's range - the loads return 0, whose code meets zero weight codes)
-    const bool ok = kt * 32 + 16 * h < g.Cin;
-    const unsigned vo = ok ? (unsigned)(((px.smp * (unsigned)g.Cin + 16u * h) * HW + px.p) * 4u) : 0x80000000u;
-    const unsigned so = (unsigned)kt * 32u * HW * 4u;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) v[i] = buf_ld_f32(rs, vo, so + (unsigned)i * HW * 4u);
-  };
-  float raw[NB][16];
-#pragma unroll
-  for (int b2 = 0; b2 < NB; ++b2)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) raw[b2][i] = 0.0f;
-  if constexpr (!FRONT) {
-#pragma unroll
-    for (int qq = 0; qq < NB - 1; ++qq) issue(t_begin + qq / KT, qq % KT, raw[qq]);
-  }
-  FQ_PIN();
-  // FRONT: the multiply-back scale of the depthwise layer's input quantiser (make_qparams: max_ / levels)
-  float fscale = 0.0f;
-  if constexpr (FRONT) fscale = input_threshold(fa.in_stat, n, fa.in_thr, nullptr, false) / fa.levels;
-  const float max_ = input_threshold(in_stat, n, in_thr, cur_max_out, blockIdx.x == 0);
-  const QParams q = make_qparams(max_, levels, lo_neg != 0, eps);
-  const int ubias = 128 - g.zoff;
-  const unsigned nn_xor = fq_nonneg_xor(ubias);
-  const bool wr_codes = x_codes_out != nullptr;
-  const fq_rsrc rcodes = make_rsrc(x_codes_out, wr_codes ? (int64_t)(cols / HW) * 2 * KT * HW * 16 : 0);
-  for (int idx = threadIdx.x; idx < g.CT * KT * 64; idx += kThreads) {
-    const int f = idx >> 6, ct = f / KT, kt = f - ct * KT;
-    ldsW[idx] = *reinterpret_cast<const v4i*>(wfrag + (((int64_t)ct * g.KTS + kt) << 10) + ((idx & 63) << 4));
-  }
-  // (the epilogue's per-channel constants too: read from HBM inside flush() they cost every wavefront a memory latency per
-  // channel tile and sample - a fixed 6-25 us that made the pass as slow at batch 32 as at batch 128)
-  const int nchs = g.CT * 32;
-  for (int i = threadIdx.x; i < nchs; i += kThreads) {
-    const bool okc = i < g.Cout;
-    c_zs[i] = okc ? g.zoff * wsum[i] : 0;
-    c_k[i] = okc ? wscale[i] : 0.0f;
-    c_k[nchs + i] = (okc && bias != nullptr) ? bias[i] : 0.0f;
-    c_k[2 * nchs + i] = (okc && bn_scale != nullptr) ? bn_scale[i] : 1.0f;
-    c_k[3 * nchs + i] = (okc && bn_scale != nullptr) ? bn_shift[i] : 0.0f;
-  }
-  if constexpr (FRONT)
-    for (int i = threadIdx.x; i < g.Cin; i += kThreads) {
-#pragma unroll
-      for (int t = 0; t < 9; ++t) dwk[i * 12 + t] = fa.w[i * 9 + t];
-      dwk[i * 12 + 9] = fa.bias != nullptr ? fa.bias[i] : 0.0f;
-      dwk[i * 12 + 10] = fa.bn_scale != nullptr ? fa.bn_scale[i] : 1.0f;
-      dwk[i * 12 + 11] = fa.bn_scale != nullptr ? fa.bn_shift[i] : 0.0f;
-    }
-  auto reset = [&]() __attribute__((always_inline)) {
-    for (int ct = 0; ct < g.CT; ++ct) {
-      my[ct * 128 + lane] = INT_MIN;
-      my[ct * 128 + 64 + lane] = INT_MAX;
-    }
-  };
-  reset();
-  __syncthreads();
-  const bool has_bn = bn_scale != nullptr;
-  // the fp32 epilogue of fq_pwconv_i8 on the two extreme sums of every channel, then the maximum over the wave's channels
-  auto flush = [&](unsigned smp) __attribute__((always_inline)) {
-    float m = 0.0f;
-    for (int ct = 0; ct < g.CT; ++ct) {
-      const int c = ct * 32 + i32;
-      int hi = my[ct * 128 + lane], lo = my[ct * 128 + 64 + lane];
-      // (both halves hold the same channel: pixels 0..15 and 16..31)
-      const int ohi = __shfl_xor(hi, 32, 64), olo = __shfl_xor(lo, 32, 64);
-      hi = hi > ohi ? hi : ohi;
-      lo = lo < olo ? lo : olo;
-      if (c < g.Cout && hi >= lo) {
-        hi += c_zs[c];
-        lo += c_zs[c];
-        const float sxw = q.scale * c_k[c];
-        const float bch = c_k[nchs + c];
-        const float bsc = c_k[2 * nchs + c], bsh = c_k[3 * nchs + c];
-        auto f = [&](int a) {
-          float v = (float)a * sxw;
-          if (bias != nullptr) v = v + bch;
-          if (has_bn) {
-            v = v * bsc;
-            v = v + bsh;
-          }
-          return fabsf(act_rt(v, act));
-        };
-        m = fmaxf(m, fmaxf(f(hi), f(lo)));
-      }
-    }
-    m = wave_max_nonneg(m);
-    // into the workgroup's table; ONE global atomic per (workgroup, sample) at the end.  (A first version issued one per
-    // wavefront: 3072 atomics on the n floats of stat_out - a single cache line at batch 32 - serialise in L2 at ~10 ns each,
-    // a fixed 30 us that made the pass as slow at batch 32 as at batch 128: profiles/r6_pwstat_atomics.txt)
-    // Where the maximum goes.  Few tiles per wavefront (small batches): into the workgroup's LDS table, ONE global atomic per
-    // (workgroup, sample) at the end - one atomic per wavefront means thousands of same-cache-line atomics (stat_out is n
-    // floats: one line at batch 32) that serialise in L2 at ~10 ns each, a fixed 30 us.  Many tiles per wavefront: straight to
-    // memory - the atomics of a long kernel are spread over its run time and overlap with the other wavefronts' work, while
-    // the table's flush would put them all at the end (40 against 47 us on the first pair at batch 128).
-    // profiles/r6_pwstat_atomics.txt
-    if (lane == 0 && __float_as_uint(m) != 0u) {
-      const unsigned slot = smp - s_base;
-      if (g.table && slot < (unsigned)kSlots) atomicMax(&k_stat[slot], __float_as_uint(m));
-      else FQ_STAT_FLUSH_MAX(reinterpret_cast<unsigned*>(stat_out) + smp, __float_as_uint(m));
-    }
-    reset();
-  };
-  v4i afrag[KT];
-  const FastQuot fqx = make_fast_quot(q.denom);
-  auto quant = [&](int kt, const float (&v)[16], auto nn_c) __attribute__((always_inline)) {
-    v4i f;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-      if constexpr (decltype(nn_c)::value) {     // clip range from 0 and a divisor that takes the fp32 quotient (fq_common.h)
-        unsigned u = 0u;
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-          int r;
-          const float Q = fast_quot(fq_clip(v[4 * d + b], q), fqx);
-          asm("v_cvt_rpi_i32_f32 %0, %1" : "=v"(r) : "v"(Q));
-          u |= (unsigned)r << (8 * b);
-        }
-        f[d] = (int)(u ^ nn_xor);
-      } else {
-        f[d] = fq_pack4<false>(v[4 * d + 0], v[4 * d + 1], v[4 * d + 2], v[4 * d + 3], q, ubias, nn_xor);
-      }
-    }
-    asm volatile("" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]));
-    afrag[kt] = f;
-  };
-  // pixels [plo, phi) of the tile (in tile order: this lane's registers are pixels 16 h + r) join the open sample
-  auto reduce_tile = [&](int plo, int phi) __attribute__((always_inline)) {
-    const bool whole = plo <= 0 && phi >= 32;
-#pragma unroll 1
-    for (int ct = 0; ct < g.CT; ++ct) {
-      v16i acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};      // (zoff * rowsum joins at the flush: max / min commute with it)
-#pragma unroll
-      for (int kt = 0; kt < KT; ++kt)
-        acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(afrag[kt], ldsW[((ct * KT + kt) << 6) + lane], acc, 0, 0, 0);
-      int hi = INT_MIN, lo = INT_MAX;
-      if (whole) {
-#pragma unroll
-        for (int k = 0; k < 16; k += 2) {
-          hi = max(max(acc[k], acc[k + 1]), hi);
-          lo = min(min(acc[k], acc[k + 1]), lo);
-        }
-      } else {
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-          const int p = 16 * h + k;
-          const bool in = p >= plo && p < phi;
-          hi = in && acc[k] > hi ? acc[k] : hi;
-          lo = in && acc[k] < lo ? acc[k] : lo;
-        }
-      }
-      atomicMax(&my[ct * 128 + lane], hi);
-      atomicMin(&my[ct * 128 + 64 + lane], lo);
-    }
-  };
-  unsigned cur = FRONT ? s_base : fast_div((unsigned)((t_begin < g.tiles ? t_begin : g.tiles - 1) * 32), g.hw);
-  auto run_tile = [&](int64_t t, auto ph_c, auto nn_c) __attribute__((always_inline)) {
-    constexpr int PH = decltype(ph_c)::value;                 // the tile's first slab sits in buffer (PH * KT) % NB
-    const Pix px = pix_of(t);
-    const unsigned cvo = ((px.smp * (unsigned)(2 * KT) + (unsigned)h) * HW + px.p) * 16u;
-#pragma unroll
-    for (int kt = 0; kt < KT; ++kt) {
-      const int qn = kt + NB - 1;
-      issue(t + qn / KT, qn % KT, raw[(PH * KT + kt + NB - 1) % NB]);
-      FQ_PIN();
-      quant(kt, raw[(PH * KT + kt) % NB], nn_c);
-      // (the whole offset in the lane register: with a constant scalar offset the compiler itself keeps the data registers of a
-      // 16-byte store untouched for as long as the store reads them - fq_common.h at buf_st_v4f)
-      if (wr_codes) buf_st_v4i(rcodes, cvo + (unsigned)(2 * kt) * HW * 16u, afrag[kt]);
-      FQ_PIN();
-    }
-    const unsigned j0 = (unsigned)t * 32u, j1 = j0 + 31u < cols ? j0 + 31u : cols - 1;
-    const unsigned s0 = fast_div(j0, g.hw), s1 = fast_div(j1, g.hw);
-    if (s0 != cur) {
-      flush(cur);
-      cur = s0;
-    }
-    if (s0 == s1) {
-      reduce_tile(0, 32);
-    } else {                                   // a tile across two samples (planes of at least 32 pixels: never three)
-      const int pb = (int)(s1 * HW - j0);
-      reduce_tile(0, pb);
-      flush(cur);
-      cur = s1;
-      reduce_tile(pb, 32);
-    }
-    FQ_PIN();
-  };
-  auto run_all = [&](auto nn_c) __attribute__((always_inline)) {
-    constexpr int U = (KT % NB == 0) ? 1 : NB;                  // tiles per turn: U * KT is a multiple of NB (NB prime)
-    using std::integral_constant;
-    for (int64_t t = t_begin; t < t_end; t += U) {
-      run_tile(t, integral_constant<int, 0>{}, nn_c);
-      if (U > 1 && t + 1 < t_end) run_tile(t + 1, integral_constant<int, 1 % U>{}, nn_c);
-      if (U > 2 && t + 2 < t_end) run_tile(t + 2, integral_constant<int, 2 % U>{}, nn_c);
-      if (U > 3 && t + 3 < t_end) run_tile(t + 3, integral_constant<int, 3 % U>{}, nn_c);
-    }
-  };
-  // FRONT: band by band - recompute the depthwise values into the band buffer as codes, then the tiles of the band
-  auto run_front = [&](auto nn_c) __attribute__((always_inline)) {
-    constexpr bool NN = decltype(nn_c)::value;
-    constexpr int FE = FRONT ? FEPI : kEpiRuntime;
-    const int Q = fa.Q, W = fa.W, H = fa.H;
-    const int seg = lane / Q, pos = lane - seg * Q;
-    const bool first = pos == 0, last = pos == Q - 1;
-    const bool has_fb = fa.bias != nullptr, has_fbn = fa.bn_scale != nullptr;
-    QParams qc = q;                               // compile-time epilogue, clip range from 0: ReLU / ReLU6 and the clip are one median
-    if (NN && FE != kEpiRuntime) qc.hi = FE == kEpiBnRelu6 ? fminf(q.hi, 6.0f) : q.hi;
-    const unsigned* xc32 = reinterpret_cast<const unsigned*>(fa.codes);
-    const int z4 = stored_zero4(ubias);
-    const v4i zero_frag = (v4i){z4, z4, z4, z4};
-    auto deq = [&](unsigned wd, int b) __attribute__((always_inline)) {
-      const int code = FSIGNED ? (int)(int8_t)(wd >> (8 * b)) : (int)((wd >> (8 * b)) & 255u);
-      return (float)code * fscale;
-    };
-    for (int64_t bt = t_begin; bt < t_end; ++bt) {
-      const unsigned smp = (unsigned)(bt / fa.bands);
-      const int r0 = (int)(bt - (int64_t)smp * fa.bands) * fa.R;
-      const int Rb = H - r0 < fa.R ? H - r0 : fa.R;
-      if (smp != cur) {
-        flush(cur);
-        cur = smp;
-      }
-      // ---- 1: the depthwise layer on rows r0 - 1 .. r0 + Rb of `segs` channels per wavefront and turn ----
-      for (int c0 = 0; c0 < g.Cin; c0 += NW * fa.segs) {
-        const int c = front_channel(c0, wave, fa.segs, seg);
-        const bool c_ok = seg < fa.segs && c < g.Cin;
-        const int cc = c_ok ? c : 0;
-        const float* kc = dwk + cc * 12;
-        const float w00 = kc[0], w01 = kc[1], w02 = kc[2], w10 = kc[3], w11 = kc[4], w12 = kc[5], w20 = kc[6], w21 = kc[7],
-                    w22 = kc[8], bch = kc[9], bsc = kc[10], bsh = kc[11];
-        const unsigned* src = xc32 + ((int64_t)(smp * (unsigned)g.Cin + (unsigned)cc) * H) * Q + pos;
-        unsigned raw_c[kFrontRows + 2];           // (unconditional loads from clamped rows, masked: a row outside the plane is zero codes)
-#pragma unroll
-        for (int k = 0; k < kFrontRows + 2; ++k) {
-          const int t = r0 - 1 + k, tc = t < 0 ? 0 : (t > H - 1 ? H - 1 : t);
-          raw_c[k] = src[tc * Q] & ((t >= 0 && t < H) ? 0xFFFFFFFFu : 0u);
-        }
-        // this launch's code of one depthwise sum (the stored byte of the C16 layout)
-        auto zcode = [&](float acc) __attribute__((always_inline)) {
-          if constexpr (NN) {
-            const float v = FE == kEpiRuntime ? dw_finish<kEpiRuntime>(acc, has_fb, bch, has_fbn, bsc, bsh, fa.act)
-                                              : dw_finish<FE, false>(acc, false, 0.0f, true, bsc, bsh, 0);
-            int r;
-            const float Qv = fast_quot(fq_clip(v, qc), fqx);
-            asm("v_cvt_rpi_i32_f32 %0, %1" : "=v"(r) : "v"(Qv));
-            return (unsigned)r ^ (nn_xor & 255u);
-          } else {
-            const float v = dw_finish<FE>(acc, has_fb, bch, has_fbn, bsc, bsh, fa.act);
-            return (unsigned)(fq_code_int(v, q) + ubias) ^ 0x80u;
-          }
-        };
-        float a[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, b[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        // the lane's byte of band pixel (row 0, column 4 pos); a column / a row further on are front_byte's own strides (the map
-        // is linear in the row and in the column of a four-column group) - one running address instead of 32
-        unsigned dst = (unsigned)front_byte(fa.lay, cc, 4 * pos);
-        const unsigned jstep = (unsigned)(front_byte(fa.lay, 0, 1) - front_byte(fa.lay, 0, 0));
-        const unsigned rstep = (unsigned)(front_byte(fa.lay, 0, 4 * Q) - front_byte(fa.lay, 0, 0));
-#pragma unroll
-        for (int k = 0; k < kFrontRows + 2; ++k) {
-          if (k <= Rb + 1) {                      // (the same for the whole workgroup)
-            float cv[6];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) cv[j + 1] = deq(raw_c[k], j);
-            const float lp = lane_prev(cv[4]), ln = lane_next(cv[1]);      // (taken by every lane, masked afterwards)
-            cv[0] = first ? 0.0f : lp;
-            cv[5] = last ? 0.0f : ln;
-            if (k >= 2) {                         // input row r0 + k - 1 closes output row r0 + k - 2
-#pragma unroll
-              for (int j = 0; j < 4; ++j) {
-                const unsigned code = zcode(dw_taps(w00, w01, w02, w10, w11, w12, w20, w21, w22, a[j], a[j + 1], a[j + 2], b[j],
-                                                    b[j + 1], b[j + 2], cv[j], cv[j + 1], cv[j + 2]));
-                if (c_ok) zbuf[dst + j * jstep] = (unsigned char)code;
-              }
-              dst += rstep;
-              asm volatile("" : "+v"(dst));
-            }
-#pragma unroll
-            for (int j = 0; j < 6; ++j) {
-              a[j] = b[j];
-              b[j] = cv[j];
-            }
-          }
-        }
-      }
-      __syncthreads();
-      // ---- 2: the band's pixels as 32-pixel tiles (the last one may be short: its lanes past the band repeat the last pixel) ----
-      const int npix = Rb * W, ntile = (npix + 31) >> 5;
-      for (int tl = wave; tl < ntile; tl += NW) {
-        int pp = tl * 32 + pl;
-        pp = pp < npix ? pp : npix - 1;
-        // channels 32 kt + 16 h .. + 15 of pixel pp: byte 0 of planes 8 kt + 4 h .. + 3 (the half-slab past Cin has no planes)
-        const unsigned* zp = reinterpret_cast<const unsigned*>(zbuf + front_byte(fa.lay, g.Cin <= 16 ? 0 : 16 * h, pp));
-#pragma unroll
-        for (int kt = 0; kt < KT; ++kt) {
-          v4i f;
-#pragma unroll
-          for (int u = 0; u < 4; ++u) f[u] = (int)zp[(8 * kt + u) * fa.lay.pl];
-          if (KT == 1 && g.Cin <= 16 && h == 1) f = zero_frag;     // (the half-slab past Cin: the code of 0)
-          if (wr_codes)
-            buf_st_v4i(rcodes, ((smp * (unsigned)(2 * KT) + (unsigned)(2 * kt + h)) * HW + (unsigned)(r0 * W + pp)) * 16u, f);
-          afrag[kt] = f;
-        }
-        const int valid = npix - tl * 32;
-        reduce_tile(0, valid < 32 ? valid : 32);
-      }
-      __syncthreads();                            // (the next band overwrites the buffer)
-    }
-  };
-  if constexpr (FRONT) {
-    if (fq_nonneg(q) && fqx.ok) run_front(std::true_type{});
-    else run_front(std::false_type{});
-  } else {
-    if (fq_nonneg(q) && fqx.ok) run_all(std::true_type{});
-    else run_all(std::false_type{});
-  }
-  if (t_begin < t_end) flush(cur);
-  __syncthreads();
-  if (threadIdx.x < kSlots && k_stat[threadIdx.x] != 0u && s_base + threadIdx.x < cols / HW)
-    FQ_STAT_FLUSH_MAX(reinterpret_cast<unsigned*>(stat_out) + s_base + threadIdx.x, k_stat[threadIdx.x]);
-}
-
 // test hook (fq_debug_fast_quotient): the quotient the recompute kernels divide with, element by element
 __global__ void fast_quotient_kernel(const float* __restrict__ c, int64_t n, const float* __restrict__ d, float* __restrict__ out,
                                      int* __restrict__ ok_out) {
@@ -1003,7 +551,7 @@ PwDwPlan pwdw_plan(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w, i
   const int reach = stride == 1 ? (int)w + 2 + p.lz : 15 * p.strips + 1;
   p.pitch = (reach > wo ? reach : wo) + p.lz;
   p.pitch |= 1;
-  p.lds = (size_t)ct * kt * 1024 + 2 * ((size_t)cout * p.pitch + kRowSlack) * 4 + kRowSlack * 4 + (stride == 1 ? (size_t)cout * 13 * 4 : 0);
+  p.lds = pwdw_lds(ct, kt, (int)cout, p.pitch, stride, false);     // (the storing launch's: it admits the shape and sizes the bands)
   if (p.lds + 10 * 1024 > (size_t)max_lds_bytes()) return p;
   // rows per band: the bands of all samples should fill the chip's workgroup slots (two wavefronts per SIMD by registers, the
   // row buffers by LDS) in as few rounds as possible, a band re-computing the one or two pointwise rows above / below it.
@@ -1040,127 +588,6 @@ PwDwPlan pwdw_plan(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w, i
 
 }  // namespace
 
-namespace fqi {
-
-// LDS of the statistic pass beside a front layer's (fq_front_layout.h, where the host walk counts it too)
-static size_t pw_stat_lds(int kt, int ct, int waves = kFrontWaves) { return stat_fixed_lds(kt, ct, waves); }
-
-bool pw_stat_shape_ok(int64_t n, int64_t cin, int64_t cout, int64_t hw) {
-  if (n <= 0 || cin <= 0 || cout <= 0 || hw < 32 || hw >= (1ll << 30) || n * hw >= (1ll << 31) - 512) return false;
-  const int kt = (int)((cin + 31) / 32), ct = (int)((cout + 31) / 32);
-  if (!(kt == 1 || kt == 2 || kt == 4 || kt == 8) || cin % 16 != 0) return false;
-  return pw_stat_lds(kt, ct) <= (size_t)kStatLdsMax && n * cin * hw * 4 < (1ll << 32);
-}
-
-// wavefronts per workgroup, rows per band and LDS of the front-layer mode: front_plan of fq_front_layout.h.
-// FQ_PWSTAT_FRONT_ROWS and FQ_PWSTAT_FRONT_WAVES force the first two and are read at every call, so that a test can vary them
-// inside one process.
-static FrontPlan pw_front_plan(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w) {
-  const char* e = getenv("FQ_PWSTAT_FRONT_ROWS");
-  const char* ew = getenv("FQ_PWSTAT_FRONT_WAVES");
-  static const int wg_env = env_int("FQ_PWSTAT_WG_PER_CU", 0);
-  return front_plan(n, cin, cout, h, w, num_cu(), wg_env > 0 ? wg_env : kFrontWgCap, e != nullptr ? atoi(e) : 0,
-                    ew != nullptr ? atoi(ew) : 0);
-}
-
-bool pw_stat_front_shape_ok(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w) {
-  if (h < 1 || w < 4 || w % 4 != 0 || w / 4 > 64 || !(cin == 16 || cin == 32 || cin == 64 || cin == 128) ||
-      !pw_stat_shape_ok(n, cin, cout, h * w))
-    return false;
-  // (the depthwise statistic pass in front must take the plane too: fq_dwconv3x3 without y)
-  return pw_front_plan(n, cin, cout, h, w).rows >= 1 && n * cin * ((w / 4 + 61) / 62) < (1ll << 31) - 1024;
-}
-
-int pw_stat_launch(const PwCall& c) {
-  const int kt = (int)((c.cin + 31) / 32), ct = (int)((c.cout + 31) / 32);
-  size_t lds = pw_stat_lds(kt, ct);
-  PwFrontArgs fa = {};
-  int waves = kFrontWaves;
-  if (c.front != nullptr) {
-    const PwFront& f = *c.front;
-    fa.codes = static_cast<const int8_t*>(f.codes);
-    fa.w = f.w; fa.bias = f.bias; fa.bn_scale = f.bn_scale; fa.bn_shift = f.bn_shift;
-    fa.in_stat = f.in_stat; fa.in_thr = f.in_thr; fa.levels = f.levels; fa.act = f.act;
-    fa.H = (int)f.h; fa.W = (int)f.wdt; fa.Q = fa.W / 4; fa.segs = 64 / fa.Q;
-    const FrontPlan plan = pw_front_plan(c.n, c.cin, c.cout, f.h, f.wdt);
-    waves = plan.waves;
-    fa.R = plan.rows;
-    FQ_REQUIRE(fa.R >= 1, "fq_pwconv_i8_stat: no band of the front layer fits the LDS");
-    fa.bands = (fa.H + fa.R - 1) / fa.R;
-    fa.lay = front_layout(fa.Q, fa.R);
-    lds = plan.lds;
-  }
-  PwStatGeom g;
-  g.Cin = (int)c.cin; g.KTS = (int)(c.cin_pad / 32); g.Cout = (int)c.cout; g.CT = ct; g.HW = (int)c.hw;
-  g.cols = c.n * c.hw; g.tiles = (g.cols + 31) / 32; g.zoff = c.zoff;
-  g.hw = fast_div_for((unsigned)c.hw);
-  if (int rc = pw_zero_stat(c)) return rc;
-  int per_cu = stat_wg_per_cu(lds, c.front != nullptr ? stat_wg_cap(kFrontWgCap, waves) : 3);
-  static const int wg_env = env_int("FQ_PWSTAT_WG_PER_CU", 0);
-  if (wg_env > 0) per_cu = wg_env;
-  int64_t grid = (int64_t)num_cu() * per_cu;
-  const int64_t need = c.front != nullptr ? c.n * fa.bands : (g.tiles + 3) / 4;
-  if (grid > need) grid = need;
-  static const int table_env = env_int("FQ_PWSTAT_TABLE", -1);
-  g.table = table_env >= 0 ? table_env : (g.tiles < grid * waves * 10 ? 1 : 0);
-#define FQ_PST_GO(KT_)                                                                                                     \
-  case KT_: {                                                                                                              \
-    static const bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&pw_stat_kernel<KT_>),                   \
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024) == hipSuccess; \
-    FQ_REQUIRE(attr_ok, "fq_pwconv_i8_stat: cannot raise the dynamic LDS limit");                                          \
-    hipLaunchKernelGGL((pw_stat_kernel<KT_>), dim3((unsigned)grid), dim3(kBlock), lds, c.st, c.x, c.wcodes, c.wscale,       \
-                       (const int*)c.wsum, c.bias, g, c.in_stat, (int)c.n, c.in_thr, c.levels, c.lo_neg, kEps,              \
-                       c.out_current_max, c.bn_scale, c.bn_shift, c.act, c.stat_out, (int8_t*)c.x_codes_out, fa);          \
-  } break;
-  // front layer: the depthwise epilogue at compile time where fq_dwconv3x3 has it so, the signedness of its input codes
-#define FQ_PST_FRONT_W(KT_, EPI_, SG_, NW_)                                                                                \
-  {                                                                                                                        \
-    static const bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&pw_stat_kernel<KT_, EPI_, SG_, NW_>),   \
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024) == hipSuccess; \
-    FQ_REQUIRE(attr_ok, "fq_pwconv_i8_stat: cannot raise the dynamic LDS limit");                                          \
-    hipLaunchKernelGGL((pw_stat_kernel<KT_, EPI_, SG_, NW_>), dim3((unsigned)grid), dim3(64 * NW_), lds, c.st, c.x,        \
-                       c.wcodes, c.wscale, (const int*)c.wsum, c.bias, g, c.in_stat, (int)c.n, c.in_thr, c.levels,         \
-                       c.lo_neg, kEps, c.out_current_max, c.bn_scale, c.bn_shift, c.act, c.stat_out,                       \
-                       (int8_t*)c.x_codes_out, fa);                                                                        \
-  }
-  // (eight wavefronts: instantiated where pw_front_plan can choose them, two and four slabs)
-#define FQ_PST_FRONT(KT_, EPI_, SG_)                                                                                       \
-  {                                                                                                                        \
-    if constexpr (KT_ >= 2) {                                                                                              \
-      if (waves == kFrontWavesWide) FQ_PST_FRONT_W(KT_, EPI_, SG_, kFrontWavesWide)                                        \
-      else FQ_PST_FRONT_W(KT_, EPI_, SG_, kFrontWaves)                                                                     \
-    } else FQ_PST_FRONT_W(KT_, EPI_, SG_, kFrontWaves)                                                                     \
-  }
-#define FQ_PST_FRONT_S(KT_, EPI_)                                                                                          \
-  {                                                                                                                        \
-    if (c.front->is_signed) FQ_PST_FRONT(KT_, EPI_, true) else FQ_PST_FRONT(KT_, EPI_, false)                              \
-  }
-#define FQ_PST_FRONT_E(KT_)                                                                                                \
-  {                                                                                                                        \
-    if (c.front->epi == kEpiBnRelu) FQ_PST_FRONT_S(KT_, kEpiBnRelu)                                                        \
-    else if (c.front->epi == kEpiBnRelu6) FQ_PST_FRONT_S(KT_, kEpiBnRelu6)                                                 \
-    else FQ_PST_FRONT_S(KT_, kEpiRuntime)                                                                                  \
-  }
-  if (c.front != nullptr) {
-    FQ_REQUIRE(kt == 1 || kt == 2 || kt == 4, "fq_pwconv_i8_stat: a front layer needs cin <= 128");
-    if (kt == 1) FQ_PST_FRONT_E(1) else if (kt == 2) FQ_PST_FRONT_E(2) else FQ_PST_FRONT_E(4)
-  } else {
-    switch (kt) {
-      FQ_PST_GO(1) FQ_PST_GO(2) FQ_PST_GO(4) FQ_PST_GO(8)
-      default: return fail(FQ_ERR_INVALID, "fq_pwconv_i8_stat: K / 32 = %d is not instantiated", kt);
-    }
-  }
-#undef FQ_PST_FRONT_E
-#undef FQ_PST_FRONT_S
-#undef FQ_PST_FRONT
-#undef FQ_PST_FRONT_W
-#undef FQ_PST_GO
-  FQ_LAUNCH_CHECK();
-  return FQ_OK;
-}
-
-}  // namespace fqi
-
 using namespace fqi;
 
 extern "C" {
@@ -1180,14 +607,24 @@ int fq_pwdw_fused_supported(int64_t n, int64_t cin, int64_t cout, int64_t h, int
 
 }  // extern "C"
 
+// one instantiation's launch: it owns the raised dynamic LDS limit; `args` are pwdw_kernel's, written out by the one caller
+template <int KT, int CW, int S, int LZ, int FAST, int CODES, int NS, class... Args>
+static int pwdw_go(unsigned grid, int threads, size_t lds, hipStream_t st, Args... args) {
+  static const bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&pwdw_kernel<KT, CW, S, LZ, FAST, CODES, NS>),
+                                                  hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) == hipSuccess;
+  FQ_REQUIRE(attr_ok, "fq_pwdw_fused: cannot raise the dynamic LDS limit");
+  hipLaunchKernelGGL((pwdw_kernel<KT, CW, S, LZ, FAST, CODES, NS>), dim3(grid), dim3((unsigned)threads), lds, st, args...);
+  return FQ_OK;
+}
+
 // fq_pwdw_fused: y, or mid_codes_out instead of y - the statistic mode, NS of pwdw_kernel
-static int pwdw_fused_impl(const float* x, const int8_t* wcodes, const float* wscale, const int32_t* wsum, const float* pw_bias,
-                           int64_t n, int64_t cin, int64_t cin_pad, int64_t cout_pad, int64_t cout, int64_t h, int64_t w,
-                           const float* in_stat, const float* in_thr, int in_width, unsigned in_flags, const float* pw_bn_scale,
-                           const float* pw_bn_shift, int pw_act, const float* mid_stat, const float* mid_thr, int mid_width,
-                           unsigned mid_flags, float* mid_current_max, const float* dw_w, const float* dw_bias, int dw_stride,
-                           const float* dw_bn_scale, const float* dw_bn_shift, int dw_act, float* y, void* mid_codes_out,
-                           float* stat_out, const void* x_codes, fqStream_t stream) {
+extern "C" int fq_pwdw_fused(const float* x, const int8_t* wcodes, const float* wscale, const int32_t* wsum, const float* pw_bias,
+                             int64_t n, int64_t cin, int64_t cin_pad, int64_t cout_pad, int64_t cout, int64_t h, int64_t w,
+                             const float* in_stat, const float* in_thr, int in_width, unsigned in_flags, const float* pw_bn_scale,
+                             const float* pw_bn_shift, int pw_act, const float* mid_stat, const float* mid_thr, int mid_width,
+                             unsigned mid_flags, float* mid_current_max, const float* dw_w, const float* dw_bias, int dw_stride,
+                             const float* dw_bn_scale, const float* dw_bn_shift, int dw_act, float* y, float* stat_out,
+                             const void* x_codes, fqStream_t stream, void* mid_codes_out) {
   const bool ns = mid_codes_out != nullptr;
   FQ_REQUIRE((x || x_codes) && wcodes && wscale && wsum && dw_w && (y || ns), "fq_pwdw_fused: null pointer");
   if (ns) {
@@ -1249,68 +686,34 @@ static int pwdw_fused_impl(const float* x, const int8_t* wcodes, const float* ws
   const int8_t* xc = static_cast<const int8_t*>(x_codes);
   const unsigned grid = (unsigned)(n * p.bands);
   // (the statistic mode has no row buffers: weight fragments and the depthwise layer's constants only)
-  const size_t lds = ns ? (size_t)(cout / 32) * p.kt * 1024 + (size_t)cout * 13 * 4 : p.lds;
+  const size_t lds = ns ? pwdw_lds((int)(cout / 32), p.kt, (int)cout, p.pitch, dw_stride, true) : p.lds;
   float* const y_arg = ns ? static_cast<float*>(mid_codes_out) : y;
-#define FQ_PWDW_GO(KT_, CW_, S_, LZ_, F_, C_, NS_)                                                                          \
-  {                                                                                                                        \
-    static const bool attr_ok =                                                                                            \
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&pwdw_kernel<KT_, CW_, S_, LZ_, F_, C_, NS_>),                    \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) == hipSuccess;                         \
-    FQ_REQUIRE(attr_ok, "fq_pwdw_fused: cannot raise the dynamic LDS limit");                                              \
-    hipLaunchKernelGGL((pwdw_kernel<KT_, CW_, S_, LZ_, F_, C_, NS_>), dim3(grid), dim3((unsigned)p.threads), lds, st, x,    \
-                       xc, wfrag, wscale, (const int*)wsum, pw_bias, g, in_stat, (int)n, in_thr, levels1, lo1, kEps,        \
-                       pw_bn_scale, pw_bn_shift, pw_act, mid_stat, mid_thr, levels2, lo2, mid_current_max, dw_w, dw_bias,   \
-                       dw_bn_scale, dw_bn_shift, dw_act, y_arg, stat_out);                                                 \
-  }
-#define FQ_PWDW_C(KT_, CW_, S_, LZ_, F_)                                                                                    \
-  {                                                                                                                        \
-    if (xc != nullptr) FQ_PWDW_GO(KT_, CW_, S_, LZ_, F_, 1, 0) else FQ_PWDW_GO(KT_, CW_, S_, LZ_, F_, 0, 0)                 \
-  }
-#define FQ_PWDW_F(KT_, CW_, S_, LZ_)                                                                                        \
-  {                                                                                                                        \
-    if (fast == 1) FQ_PWDW_C(KT_, CW_, S_, LZ_, 1) else FQ_PWDW_C(KT_, CW_, S_, LZ_, 0)                                     \
-  }
-#define FQ_PWDW_N(KT_, CW_, LZ_)                                                                                            \
-  {                                                                                                                        \
-    if (fast == 1) FQ_PWDW_GO(KT_, CW_, 1, LZ_, 1, 1, 1) else FQ_PWDW_GO(KT_, CW_, 1, LZ_, 0, 1, 1)                         \
-  }
-#define FQ_PWDW_S(KT_, CW_)                                                                                                 \
-  {                                                                                                                        \
-    if (dw_stride == 2) FQ_PWDW_F(KT_, CW_, 2, 0)                                                                          \
-    else if (ns) {                                                                                                         \
-      if (p.lz == 0) FQ_PWDW_N(KT_, CW_, 0) else FQ_PWDW_N(KT_, CW_, 2)                                                    \
-    } else if (p.lz == 0) FQ_PWDW_F(KT_, CW_, 1, 0) else FQ_PWDW_F(KT_, CW_, 1, 2)                                          \
-  }
-#define FQ_PWDW_K(KT_)                                                                                                      \
-  case KT_:                                                                                                                \
-    if (p.cw == 2) FQ_PWDW_S(KT_, 2) else FQ_PWDW_S(KT_, 1)                                                                \
-    break;
-  switch (p.kt) {
-    FQ_PWDW_K(1) FQ_PWDW_K(2) FQ_PWDW_K(4) FQ_PWDW_K(8)
-    default: break;
-  }
-#undef FQ_PWDW_K
-#undef FQ_PWDW_S
-#undef FQ_PWDW_N
-#undef FQ_PWDW_F
-#undef FQ_PWDW_C
-#undef FQ_PWDW_GO
+  // the instantiations: every (KT, CW) x (stride 1 with LZ 0 / 2, stride 2) x epilogue x input kind, and the statistic mode
+  // for stride 1 on code input (what the checks above and pwdw_plan admit)
+  int rc = FQ_OK;
+  pair_pick<1, 2, 4, 8>(p.kt, [&](auto kt_c) {
+    pair_pick<1, 2>(p.cw, [&](auto cw_c) {
+      pair_pick<1, 2>(dw_stride, [&](auto s_c) {
+        pair_pick<0, 2>(p.lz, [&](auto lz_c) {
+          pair_pick<0, 1>(fast, [&](auto fast_c) {
+            pair_pick<0, 1>(xc != nullptr ? 1 : 0, [&](auto codes_c) {
+              pair_pick<0, 1>(ns ? 1 : 0, [&](auto ns_c) {
+                constexpr int KT = decltype(kt_c)::value, CW = decltype(cw_c)::value, S = decltype(s_c)::value,
+                              LZ = decltype(lz_c)::value, FAST = decltype(fast_c)::value, CODES = decltype(codes_c)::value,
+                              NS = decltype(ns_c)::value;
+                if constexpr ((S == 1 || LZ == 0) && (NS == 0 || (S == 1 && CODES == 1)))
+                  rc = pwdw_go<KT, CW, S, LZ, FAST, CODES, NS>(
+                      grid, p.threads, lds, st, x, xc, wfrag, wscale, (const int*)wsum, pw_bias, g, in_stat, (int)n, in_thr,
+                      levels1, lo1, kEps, pw_bn_scale, pw_bn_shift, pw_act, mid_stat, mid_thr, levels2, lo2, mid_current_max,
+                      dw_w, dw_bias, dw_bn_scale, dw_bn_shift, dw_act, y_arg, stat_out);
+              });
+            });
+          });
+        });
+      });
+    });
+  });
+  if (rc != FQ_OK) return rc;
   FQ_LAUNCH_CHECK();
   return FQ_OK;
 }
-
-extern "C" {
-
-int fq_pwdw_fused(const float* x, const int8_t* wcodes, const float* wscale, const int32_t* wsum, const float* pw_bias,
-                  int64_t n, int64_t cin, int64_t cin_pad, int64_t cout_pad, int64_t cout, int64_t h, int64_t w,
-                  const float* in_stat, const float* in_thr, int in_width, unsigned in_flags, const float* pw_bn_scale,
-                  const float* pw_bn_shift, int pw_act, const float* mid_stat, const float* mid_thr, int mid_width,
-                  unsigned mid_flags, float* mid_current_max, const float* dw_w, const float* dw_bias, int dw_stride,
-                  const float* dw_bn_scale, const float* dw_bn_shift, int dw_act, float* y, float* stat_out,
-                  const void* x_codes, fqStream_t stream, void* mid_codes_out) {
-  return pwdw_fused_impl(x, wcodes, wscale, wsum, pw_bias, n, cin, cin_pad, cout_pad, cout, h, w, in_stat, in_thr, in_width,
-                         in_flags, pw_bn_scale, pw_bn_shift, pw_act, mid_stat, mid_thr, mid_width, mid_flags, mid_current_max,
-                         dw_w, dw_bias, dw_stride, dw_bn_scale, dw_bn_shift, dw_act, y, mid_codes_out, stat_out, x_codes, stream);
-}
-
-}  // extern "C"

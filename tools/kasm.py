@@ -16,7 +16,8 @@ from quantization.mxnet_amd.csrc import build  # noqa: E402
 def main():
     src, want = sys.argv[1], sys.argv[2]
     defs = [a for a in sys.argv[3:] if a.startswith("-D")]
-    flags = [f for f in build.FLAGS if f not in ("-fPIC", "-shared")]
+    unit = os.path.splitext(os.path.basename(src))[0]          # (the unit's own flags too: what the library is built with)
+    flags = [f for f in build.FLAGS if f not in ("-fPIC", "-shared")] + build.UNIT_FLAGS.get(unit, [])
     subprocess.run([build.hipcc()] + flags + defs + ["-S", "--cuda-device-only", src, "-o", "/tmp/kasm.s"], check=True,
                    capture_output=True)
     text = open("/tmp/kasm.s").read()

@@ -16,7 +16,9 @@ def main():
     src = sys.argv[1]
     defs = [a for a in sys.argv[2:] if a.startswith("-D")]
     flt = sys.argv[sys.argv.index("--filter") + 1] if "--filter" in sys.argv else ""
-    cmd = [build.hipcc()] + build.FLAGS + defs + ["-c", src, "-o", "/tmp/kres.o", "-Rpass-analysis=kernel-resource-usage"]
+    unit = os.path.splitext(os.path.basename(src))[0]          # (the unit's own flags too: what the library is built with)
+    cmd = [build.hipcc()] + build.FLAGS + build.UNIT_FLAGS.get(unit, []) + defs
+    cmd += ["-c", src, "-o", "/tmp/kres.o", "-Rpass-analysis=kernel-resource-usage"]
     out = subprocess.run(cmd, capture_output=True, text=True).stderr
     cur = None
     rows = []
