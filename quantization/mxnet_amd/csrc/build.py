@@ -6,7 +6,7 @@ Every `fq_*.hip` translation unit is compiled to an object under `csrc/build/` (
 changed) and the objects are linked into one shared library.  `--amalgamate` compiles all units as ONE translation unit
 instead (used by the trace build `-DFQ_PW_TRACE`, whose `__device__` debug symbols must exist once).  `--only fq_pw_sample`
 (tuning variants): the defines apply to the named units only, every other object is the default build's - a variant then
-costs one compilation instead of thirteen.
+costs one compilation, not one per unit.
 
 Flags that matter for parity: `-ffp-contract=off` (HIP defaults to fast contraction; a fused multiply-add would change
 Winograd/EMA/interpolation results against the oracle) and NO fast-math (IEEE fp32 division and roundf decide the
@@ -120,6 +120,14 @@ def _run(cmd, verbose):
     subprocess.check_call(cmd)
 
 
+def write_amalgamated(unit):
+    """Write the one translation unit of `--amalgamate` to `unit`: every source included, in the order they are compiled."""
+    with open(unit, "w") as f:
+        for s in sources():
+            f.write('#include "%s"\n' % os.path.basename(s))
+    return unit
+
+
 def build_library(force=False, verbose=True, defines=(), out=OUT, amalgamate=False, jobs=None, only=()):
     """Returns the path of the library.  `defines` (e.g. ["-DFQ_PW_TRACE"]) select a separate object directory; with
     `only` (unit names without extension) they apply to those units and the rest is taken from the default objects."""
@@ -139,10 +147,7 @@ def build_library(force=False, verbose=True, defines=(), out=OUT, amalgamate=Fal
     bid = source_id(defines)
     idflag = '-DFQ_BUILD_ID="%s"' % bid
     if amalgamate:
-        unit = os.path.join(objdir, "fq_all.hip")
-        with open(unit, "w") as f:
-            for s in sources():
-                f.write('#include "%s"\n' % os.path.basename(s))
+        unit = write_amalgamated(os.path.join(objdir, "fq_all.hip"))
         _run([cc] + FLAGS + defines + [idflag, "-shared", unit, "-o", out], verbose)
         return out
     todo, objs = [], []

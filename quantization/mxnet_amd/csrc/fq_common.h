@@ -7,9 +7,13 @@
 //   fq_core.hip        errors, event timing (fq_profile_*), device info, streaming policy
 //   fq_stream.hip      K1 per-sample statistic, K1b batch means, K2 fake-quant apply, K2b BatchNorm+activation+statistic,
 //                      K11 global average pool + statistic, K12 evaluation counters
-//   fq_dwconv.hip      K2c/K2d/K2e depthwise 3x3 with quantise-on-load (LDS tiles / 1 column per lane / 4 columns per lane),
-//                      K2o whole small planes in registers, K2p 14x14 / 7x7 planes as flat 16-byte ranges through an LDS transpose
-//   fq_dwconv16.hip    K2s depthwise 3x3 between two C16 code tensors
+//   fq_dwconv.hip      fq_dwconv3x3, the depthwise 3x3 with quantise-on-load: argument checks and the choice between its forms,
+//                      one unit each: fq_dw_tiles.hip K2c LDS tiles (every shape), fq_dw_cols.hip K2d / K2e the sliding window in
+//                      registers, 1 / 4 columns per lane (K2e: also the statistic pass), fq_dw_planes.hip K2o whole small planes
+//                      in registers, fq_dw_flat.hip K2p 28x28 / 14x14 / 7x7 planes as flat 16-byte ranges through an LDS transpose
+//   fq_dw.h            (header) the family's interface and what the forms share: tap chains, epilogue (kEpi*, also taken by the
+//                      units that recompute a depthwise layer), block range, statistic table, the launch and the grid rules
+//   fq_dwconv16.hip   K2s depthwise 3x3 between two C16 code tensors
 //   fq_stem.hip        K2q / K2r first convolution 3x3 / 7x7 s2 on the fp32 matrix cores (K2r: input rows staged in LDS)
 //   fq_stem_pool.hip   K2u first convolution 7x7 s2 + BatchNorm + activation + MaxPool 3x3 s2 in one kernel
 //   fq_conv3x3.hip     K2n dense 3x3 on int8 codes (implicit GEMM over tap and channel); fq_conv3x3_16.hip: its instantiations
@@ -762,51 +766,6 @@ __device__ __forceinline__ float lane_prev(float v) {
 }
 __device__ __forceinline__ float lane_next(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x130, 0xF, 0xF, false));
-}
-
-// The 3x3 sum of one output: rows a, b, c (above, centre, below), each as left / centre / right.  The order of these nine
-// operations is the numerical contract of the unit (the oracle emulates exactly this chain).
-__device__ __forceinline__ float dw_taps(float w00, float w01, float w02, float w10, float w11, float w12, float w20,
-                                         float w21, float w22, float a0, float a1, float a2, float b0, float b1, float b2,
-                                         float c0, float c1, float c2) {
-  float acc = 0.0f;
-  acc = fmaf(w00, a0, acc);
-  acc = fmaf(w01, a1, acc);
-  acc = fmaf(w02, a2, acc);
-  acc = fmaf(w10, b0, acc);
-  acc = fmaf(w11, b1, acc);
-  acc = fmaf(w12, b2, acc);
-  acc = fmaf(w20, c0, acc);
-  acc = fmaf(w21, c1, acc);
-  acc = fmaf(w22, c2, acc);
-  return acc;
-}
-
-// Epilogue of the depthwise kernels.  EPI 0: bias / BN / activation decided at run time (hipcc turns the wave-uniform
-// branches into four selects per output); EPI 1 / 2: the fused-inference case - BN, no bias, ReLU / ReLU6 - in 3 / 4
-// instructions.  Same operations in the same order either way.
-constexpr int kEpiRuntime = 0, kEpiBnRelu = 1, kEpiBnRelu6 = 2;
-// bit of the kernels' `act` argument (set by the library's own callers, run-time epilogue only): the per-channel `bias` vector
-// MULTIPLIES the sum instead of being added - the dequantisation factor in_scale * w_scale of nn.Conv2D(quantized=True)'s
-// depthwise layer, applied to the exact integer sum before a folded BatchNorm (its own multiply and add stay separate)
-constexpr int kActBiasMul = 0x10;
-// (ACT = false: a compile-time epilogue WITHOUT its activation - for a code output, where ReLU / ReLU6 and the consumer's clip
-// are one median: clip(relu6(v), lo <= 0, hi) == med3(v, 0, min(6, hi)))
-template <int EPI, bool ACT = true>
-__device__ __forceinline__ float dw_finish(float acc, bool has_bias, float bch, bool has_bn, float bsc, float bsh, int act) {
-  if (EPI == kEpiRuntime) {
-    if (has_bias) acc = (act & kActBiasMul) ? acc * bch : acc + bch;
-    if (has_bn) {
-      acc = acc * bsc;
-      acc = acc + bsh;
-    }
-    return act_rt(acc, act & 15);
-  }
-  acc = acc * bsc;
-  acc = acc + bsh;
-  if (!ACT) return acc;
-  acc = fmaxf(acc, 0.0f);
-  return EPI == kEpiBnRelu6 ? fminf(acc, 6.0f) : acc;
 }
 
 #ifdef FQ_PW_TRACE

@@ -2,7 +2,7 @@
 // MobileNetV2 unit under OFFLINE input quantisation, whose input the expansion convolution wrote as integer codes and whose
 // output the projection convolution reads as integer codes (see fq_common.h for the list of translation units and the design
 // rules; the C16 layout: include/fakequant.h at fq_pwconv_i8_c16)
-#include "fq_common.h"
+#include "fq_dw.h"
 
 namespace {
 
@@ -37,7 +37,7 @@ struct Dw16Geom {
 // v_pk_fma_f32: each component an IEEE operation of its own, so the results are those of the scalar form bit for bit).  The
 // 36 multiply-adds of a lane's four channels are 18 packed ones, BatchNorm one packed multiply and one packed add per pair
 // (~135 -> ~95 instructions per output row and lane).
-typedef float f2 __attribute__((ext_vector_type(2)));
+// (f2: fq_dw.h)
 __device__ __forceinline__ f2 fma2(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
 
 // What bounds this kernel (round 5; rocprofv3 counters, ablation builds and probes on 144 channels x 56 x 56, batch 128 -

@@ -11,7 +11,7 @@ namespace fqi {
 struct PwFront {
   const void* codes;             // [n][cin][h * wdt] int8: the codes of the depthwise layer's input
   const float *w, *bias, *bn_scale, *bn_shift;
-  int act, epi;                  // epi: kEpi* (fq_common.h), the epilogue fq_dwconv3x3 would have chosen
+  int act, epi;                  // epi: kEpi* (fq_dw.h), the epilogue fq_dwconv3x3 would have chosen
   const float *in_stat, *in_thr;
   float levels;
   bool is_signed;

@@ -15,6 +15,7 @@
 // lane stores it at [smp][2 kt + h][p][16]: fq_pwdw_fused's lane of the same pixel and slab loads it back with one instruction
 // instead of sixteen loads and sixteen quantisations.  The 32 lanes of a half write 512 contiguous bytes per instruction; the
 // lanes of a partial last tile, clamped to the last pixel, rewrite that pixel's own bytes.
+#include "fq_dw.h"
 #include "fq_pair.h"
 
 namespace {

@@ -1,5 +1,6 @@
 // libfakequant — fq_pwconv_i8: argument checks and the shape-based choice between the pointwise forms; fq_weight_codes
 // (see fq_common.h for the list of translation units and the design rules)
+#include "fq_dw.h"
 #include "fq_pw.h"
 
 namespace {

@@ -23,6 +23,7 @@
 // three products in the order of the row-major 3x3 chain (fq_dwconv3x3's arithmetic: fmaf by fmaf from +0).
 // A workgroup = all strips of a band x the channel groups; finished output rows go through an LDS row buffer (two rows) and
 // leave as whole rows, 16 bytes per lane.
+#include "fq_dw.h"
 #include "fq_pair.h"
 
 namespace {

@@ -3,16 +3,16 @@
 // record, int32 bias codes, per-layer constants (one small launch) -> the convolution with the quantiser on its loads:
 //   1x1 (stride 1)            the pointwise forms on the int8 matrix cores (fq_pw_sample / _split / _stream, range mode)
 //   dense 3x3 (s1, p1)        the implicit-GEMM kernel of fq_conv3x3 (Cin 64 ... 512)
-//   depthwise 3x3 (s1|2, p1)  the depthwise forms of fq_dwconv with integer CODES in the fp32 fmaf chain (exact: 9 taps)
+//   depthwise 3x3 (s1|2, p1)  the depthwise forms of fq_dwconv3x3 (fq_dw.h) with integer CODES in the fp32 fmaf chain (exact: 9 taps)
 //   every other geometry      qconv_direct_kernel below: one output per thread, exact, slow
 // - no im2col tensor, no int32 code tensor, no casts - followed by the SAME direct kernel as a conditional fix-up that
 // returns at once unless the range record says the fast kernel's 8-bit / fp32-exact representation did not hold (codes
 // spanning 257 values through a double rounding tie, a clip range that excludes the padding zero, |code| > 14 000).
 // (see fq_common.h for the list of translation units and the design rules)
-#include "fq_common.h"
+#include "fq_dw.h"
 
 namespace fqi {
-// fq_pwconv.hip / fq_conv3x3.hip / fq_dwconv.hip
+// fq_pwconv.hip / fq_conv3x3.hip (the depthwise layer's dw_range_call: fq_dw.h)
 int pw_range_call(const float* x, const int8_t* wcodes, const float* wscale, const int32_t* wsum, const int32_t* ibias,
                   float* y, int64_t n, int64_t cin, int64_t cin_pad, int64_t cout, int64_t h, int64_t w, int stride,
                   const float* rec, const float* bn_scale, const float* bn_shift, int act, float* stat_out, hipStream_t st,
@@ -21,9 +21,6 @@ bool conv3x3_range_shape_ok(int64_t cin, int64_t cout);
 int conv3x3_range_call(const float* x, const int8_t* wcodes, const float* wscale, const int32_t* wsum, const int32_t* ibias,
                        float* y, int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w, const float* rec,
                        const float* bn_scale, const float* bn_shift, int act, float* stat_out, hipStream_t st);
-int dw_range_call(const float* x, const float* wcodes_f32, float* y, int64_t n, int64_t c, int64_t h, int64_t wdt, int stride,
-                  const float* rec, const float* svec, const float* bn_scale, const float* bn_shift, int act,
-                  float* stat_out, hipStream_t st);
 }  // namespace fqi
 
 namespace {

@@ -1,6 +1,6 @@
 // libfakequant — K2q / K2r first convolution 3x3 / 7x7 stride 2 (3 -> 32 / 64) on the fp32 matrix cores
 // (see fq_common.h for the list of translation units and the design rules)
-#include "fq_common.h"
+#include "fq_dw.h"
 
 namespace {
 

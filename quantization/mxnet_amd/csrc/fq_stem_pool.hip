@@ -1,6 +1,6 @@
 // libfakequant — K2u first convolution 7x7 stride 2 (3 -> 64) + BatchNorm + activation + MaxPool 3x3 stride 2 in ONE kernel
 // (see fq_common.h for the list of translation units and the design rules)
-#include "fq_common.h"
+#include "fq_dw.h"
 
 namespace {
 

@@ -88,3 +88,19 @@ def test_library_carries_the_id_of_the_sources_it_sits_beside(tmp_path):
     stale.write_bytes(b"\x7fELF....FQ_BUILD_ID=" + b"0" * 40 + b"....")
     assert B.built_id(str(stale)) == "0" * 40 and not B.up_to_date(str(stale))
     assert B.built_id(str(tmp_path / "absent.so")) is None
+
+
+def test_all_units_compile_as_one_translation_unit(tmp_path):
+    """`build.py --amalgamate -DFQ_PW_TRACE=1` is the only way to the trace build (tools/pw_trace.py, dw_trace.py, c3_trace.py,
+    stem_trace.py): no two headers or units may define one name at namespace scope.  The device half of that unit, syntax only."""
+    import subprocess
+    from quantization.mxnet_amd.csrc import build as B
+    try:
+        cc = B.hipcc()
+        subprocess.run([cc, "--version"], check=True, capture_output=True)
+    except (RuntimeError, OSError, subprocess.CalledProcessError):
+        pytest.skip("no hipcc")
+    unit = B.write_amalgamated(str(tmp_path / "fq_all.hip"))
+    r = subprocess.run([cc] + B.FLAGS + ["-DFQ_PW_TRACE=1", "--cuda-device-only", "-fsyntax-only", unit],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-4000:]

@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""Per-workgroup phase stamps of the column-walking depthwise kernel (debug build -DFQ_PW_TRACE, see pw_trace.py)."""
+"""Per-workgroup phase stamps (PW_STAMP) of the depthwise 3x3 forms that carry them - one column per lane (csrc/fq_dw_cols.hip),
+whole planes (fq_dw_planes.hip), flat (fq_dw_flat.hip) - in the debug build: csrc/build.py --amalgamate -DFQ_PW_TRACE=1, see
+pw_trace.py."""
 import ctypes
 import os
 import sys

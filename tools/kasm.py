@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Instruction mix of one kernel of a translation unit (device assembly via hipcc -S).
 
-    python tools/kasm.py quantization/mxnet_amd/csrc/fq_dwconv.hip "planes_kernel<1, true, true, 14>" [-DNAME=V ...] [--dump]"""
+    python tools/kasm.py quantization/mxnet_amd/csrc/fq_dw_planes.hip "planes_kernel<1, true, true, 14>" [-DNAME=V ...] [--dump]"""
 import collections
 import os
 import re
