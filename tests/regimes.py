@@ -7,6 +7,11 @@ weights and its thresholds into values that take the other side; `apply` does th
 `check` asserts FROM THE ORACLE'S CODES that the regime did what its name says - before the driver compares anything, so that
 a regime that no longer reaches its branch fails instead of passing vacuously.
 
+`boundaries` is about rounding, not about a branch: Gaussian data essentially never lands within a few ulp of a quotient
+k + 0.5, so the tie behaviour of the quantisers copied into the kernels (`v_cvt_rpi`, `copysign(0.49999997f)`, the fast
+quotient) goes unseen.  The regime fills x with the fp32 neighbours of every (k + 0.5) * d under a stored threshold of its own
+and plants that threshold as every sample's maximum, so an online launch divides by the same d.
+
 A plain helper: numpy and the numpy oracle only, no device memory, no fixtures."""
 import numpy as np
 
@@ -14,13 +19,16 @@ from oracle import fq_oracle as O
 
 F32 = np.float32
 
-INPUT = ("zero", "zero_sample", "eps_scale", "tiny", "subnormal", "huge", "saturated", "allones_divisor")
+INPUT = ("zero", "zero_sample", "eps_scale", "tiny", "subnormal", "huge", "saturated", "allones_divisor", "boundaries")
 OUTPUT = ("out_saturated", "out_zero_codes", "out_allones_divisor")
 STANDALONE = ("zero_sample", "eps_scale", "tiny", "subnormal", "huge")      # kernels without weights or a stored threshold
 ALL = INPUT + OUTPUT
 
 SATURATED_VALUE = F32(8.0)
 SATURATED_THRESHOLD = F32(0.25)
+BOUNDARY_THRESHOLD = F32(2.75)
+BOUNDARY_NEIGHBOURS = 3                              # fp32 neighbours on either side of fp32((k + 0.5) * d)
+_HALF_PRED = np.nextafter(F32(0.5), F32(0))          # the one quotient at which trunc(Q + 0.5f) and roundf(Q) differ
 _SCALE = {"tiny": F32(2.0) ** -100, "subnormal": F32(1e-41), "huge": F32(2.0) ** 100}
 _MIN_NORMAL = np.finfo(np.float32).tiny
 
@@ -110,7 +118,57 @@ def saturated_input(x, signed, block=1):
     return y
 
 
-def apply(regime, x, signed, w=None, rps=None, thr=None, width=8):
+def boundary_count(signed, width=8, lo_neg_max=None):
+    """Rounding boundaries k + 0.5 between two codes of the clip range: L from 0 up, 2 L where the range starts at -max."""
+    lo_neg = signed if lo_neg_max is None else lo_neg_max
+    return (2 if lo_neg else 1) * levels(signed, width)
+
+
+def boundary_table(signed, width=8, lo_neg_max=None):
+    """(boundaries, 7) fp32: row k holds fp32((k + 0.5) * d), d the divisor of BOUNDARY_THRESHOLD, between its three fp32
+    neighbours below and above, ascending - inputs whose quotient by d lies within a few ulp of the tie k + 0.5.  k runs over
+    0 .. L-1, over -L .. L-1 where the clip range starts at -max."""
+    L = levels(signed, width)
+    lo_neg = signed if lo_neg_max is None else lo_neg_max
+    d = np.float64(divisor(BOUNDARY_THRESHOLD, signed, width))
+    mid = ((np.arange(-L if lo_neg else 0, L, dtype=np.float64) + 0.5) * d).astype(F32)
+    cols = [mid]
+    for _ in range(BOUNDARY_NEIGHBOURS):
+        cols = [np.nextafter(cols[0], F32(-np.inf))] + cols + [np.nextafter(cols[-1], F32(np.inf))]
+    table = np.stack(cols, axis=1).astype(F32)
+    assert np.abs(table).max() < BOUNDARY_THRESHOLD
+    return table
+
+
+def reaches_half_pred(x, in_max, signed, width=8):
+    """Whether an element of x has the fp32 quotient +-pred(0.5) exactly.  Every other fp32 |Q| < 2^23 has
+    trunc(Q + 0.5f) == roundf(Q) (csrc/fq_common.h at round_half_away), so a quantiser that rounds that way is wrong on this
+    quotient alone.  0.5 * d is exact in fp32 and its neighbours below step through the quotients in strides of
+    2 / (significand of d) ulp: pred(0.5) is the first of them where that significand exceeds 4 / 3.  Under 2.75 it does
+    for every level count 2^b - 1, b = 1 .. 8; under 2.5 it does for 3, 7 and 15 levels and not for 31, 63, 127 or 255."""
+    q = (np.asarray(x, F32) / divisor(in_max, signed, width)).astype(F32)
+    return bool((np.abs(q) == _HALF_PRED).any())
+
+
+def _planted(x):
+    """One element per sample - its last - carries the threshold of `boundaries`."""
+    mask = np.zeros(x.shape, bool)
+    mask.reshape(x.shape[0], -1)[:, -1] = True
+    return mask
+
+
+def boundary_input(x, signed, width=8, lo_neg_max=None):
+    """x filled flat, boundary-major, by cycling through `boundary_table`; the last element of every sample is BOUNDARY_THRESHOLD
+    instead (the fill passes over it), so that the per-sample maxima and their batch mean are that threshold exactly: an
+    online launch divides by the very d a stored one does."""
+    x = np.asarray(x, F32)
+    mask = _planted(x)
+    y = np.full(x.shape, BOUNDARY_THRESHOLD, F32)
+    y[~mask] = np.resize(boundary_table(signed, width, lo_neg_max).reshape(-1), x.size - x.shape[0])
+    return y
+
+
+def apply(regime, x, signed, w=None, rps=None, thr=None, width=8, lo_neg_max=None):
     """-> (x, w, thr): the regime's input, weights and INPUT threshold.  `thr` None: the launch quantises online, and stays
     so unless the regime has a threshold of its own.  `thr` given: the launch works under a STORED threshold; a regime without
     one of its own then stores the batch mean of the per-sample maxima of its input - what a calibration run over such data
@@ -120,7 +178,7 @@ def apply(regime, x, signed, w=None, rps=None, thr=None, width=8):
     assert regime in INPUT, regime
     x = np.asarray(x, F32)
     if thr is not None:
-        thr = None if regime in ("saturated", "allones_divisor") else "batch mean"
+        thr = None if regime in ("saturated", "allones_divisor", "boundaries") else "batch mean"
     if regime == "eps_scale":
         x = (x * eps_factor(signed, width)).astype(F32)
     elif regime == "zero":
@@ -138,6 +196,9 @@ def apply(regime, x, signed, w=None, rps=None, thr=None, width=8):
             w = saturate_rows(w, rps)
     elif regime == "allones_divisor":
         thr = allones_threshold(signed, width)
+    elif regime == "boundaries":
+        x = boundary_input(x, signed, width, lo_neg_max)
+        thr = BOUNDARY_THRESHOLD
     if isinstance(thr, str):
         thr = stored_threshold(x)
     return x, w, thr
@@ -147,10 +208,10 @@ def stored_threshold(x):
     return O.batch_mean(O.absmax_per_sample(x))
 
 
-def stored(regime, x, signed, w=None, rps=None, thr=None, width=8):
+def stored(regime, x, signed, w=None, rps=None, thr=None, width=8, lo_neg_max=None):
     """`apply` for a launch whose input threshold is always a stored one (code tensors)."""
     assert thr is not None
-    return apply(regime, x, signed, w, rps, thr, width)
+    return apply(regime, x, signed, w, rps, thr, width, lo_neg_max)
 
 
 def output_threshold(regime, y, signed, thr=None, width=8):
@@ -225,6 +286,23 @@ def check(regime, x, in_max, signed, width=8, lo_neg_max=None, w=None, rps=None,
                 assert m > 2 ** 24, "saturated: max|isum| = %d does not pass 2^24" % m
     elif regime == "allones_divisor":
         assert has_allones_significand(divisor(in_max, signed, width)), "allones_divisor: divisor of %r" % (in_max,)
+    elif regime == "boundaries":
+        assert in_max == BOUNDARY_THRESHOLD and O.batch_mean(O.absmax_per_sample(x)) == BOUNDARY_THRESHOLD
+        mask = x == BOUNDARY_THRESHOLD                 # (the table's largest value lies below the threshold)
+        n = int(mask.sum())
+        assert n == x.shape[0] and mask.reshape(n, -1).any(axis=1).all(), "boundaries: one planted element per sample"
+        nb = boundary_count(signed, width, lo_neg_max)
+        groups = (x.size - n) // 7
+        c = codes[~mask][:7 * groups].reshape(groups, 7)
+        k = (np.arange(groups) % nb + (-L if lo_neg else 0)).reshape(groups, 1)
+        straddles = ((c == k) | (c == k + 1)).all(axis=1) & (c == k).any(axis=1) & (c == k + 1).any(axis=1)
+        assert straddles.all(), "boundaries: group %d (k = %d) has the codes %s" % (
+            np.argmin(straddles), k[np.argmin(straddles), 0], sorted(set(c[np.argmin(straddles)].tolist())))
+        seen = len(set(k[straddles, 0].tolist()))
+        assert seen >= min(nb, groups), "boundaries: %d of %d boundaries straddled" % (seen, nb)
+        assert seen == nb or x.size < 2 * 7 * nb + n
+        # ... and where the whole table is there, the one quotient that tells roundf from trunc(Q + 0.5f)
+        assert groups < nb or reaches_half_pred(x[~mask], in_max, signed, width), "boundaries: no quotient is pred(0.5)"
 
 
 def check_output(regime, y, thr, signed, width=8):

@@ -40,7 +40,7 @@ PW_CASES = [(12, 16, 96, 112, 112, 1), (11, 32, 16, 112, 112, 1), (43, 96, 24, 5
 
 @pytest.mark.parametrize("case", PW_CASES, ids=["%dx%d->%d@%dx%d/s%d" % c for c in PW_CASES])
 @pytest.mark.parametrize("mode", ["u8-out", "s8-out", "s8-out-relu", "u8-out-relu6-thr9"])
-def test_pointwise_producer_writes_the_consumers_codes(dev, ops, case, mode, regime=None):
+def test_pointwise_producer_writes_the_consumers_codes(dev, ops, case, mode, regime=None, width=8, out_width=8):
     """(the last two modes: a ReLU in front of a SIGNED consumer range, and a ReLU6 whose 6 lies below the consumer's threshold -
     the epilogue folds the activation into the clip, med3(v, 0, min(6, hi)), and takes the statistic from the raw values)"""
     signed_out = mode.startswith("s8")
@@ -50,30 +50,31 @@ def test_pointwise_producer_writes_the_consumers_codes(dev, ops, case, mode, reg
     wt = (rng.standard_normal((cout, cin, 1, 1)) * 0.2).astype(np.float32)
     sc = rng.uniform(0.3, 1.5, cout).astype(np.float32)
     sh = rng.standard_normal(cout).astype(np.float32)
-    x, wt, thr_in = R.stored(regime, x, False, wt, 1, np.float32(2.7))
-    R.check(regime, x, thr_in, False, w=wt, rps=1)
+    x, wt, thr_in = R.stored(regime, x, False, wt, 1, np.float32(2.7), width=width)
+    R.check(regime, x, thr_in, False, w=wt, rps=1, width=width)
     codes, scales, rowsum = ops.weight_codes(T(wt, dev), 1, 8)
     thr_in = T(np.float32([thr_in]), dev)
     act = {"u8-out": "relu6", "s8-out": None, "s8-out-relu": "relu", "u8-out-relu6-thr9": "relu6"}[mode]
     if mode == "u8-out-relu6-thr9":
         sc = sc * np.float32(4)                                          # (values beyond 6, so that the 6 is what clips)
-    kw = dict(in_thr=thr_in, width=8, flags=0, bn_scale=T(sc, dev), bn_shift=T(sh, dev), act=act, stride=stride)
+    kw = dict(in_thr=thr_in, width=width, flags=0, bn_scale=T(sc, dev), bn_shift=T(sh, dev), act=act, stride=stride)
     y, stat = ops.pwconv_i8(T(x, dev), codes, scales, rowsum, form="split", **kw)
     yf = y.cpu().numpy()
-    thr_out = R.output_threshold(regime, yf, signed_out, np.float32(9.0 if mode == "u8-out-relu6-thr9" else 1.9))
-    R.check_output(regime, yf, thr_out, signed_out)
+    thr_out = R.output_threshold(regime, yf, signed_out, np.float32(9.0 if mode == "u8-out-relu6-thr9" else 1.9),
+                                 width=out_width)
+    R.check_output(regime, yf, thr_out, signed_out, width=out_width)
     oflags = ops.act_flags(signed=signed_out)
-    yc, stat_c = ops.pwconv_i8(T(x, dev), codes, scales, rowsum, out_codes=dict(thr=T(np.float32([thr_out]), dev), width=8,
+    yc, stat_c = ops.pwconv_i8(T(x, dev), codes, scales, rowsum, out_codes=dict(thr=T(np.float32([thr_out]), dev), width=out_width,
                                                                                 flags=oflags), **kw)
     assert isinstance(yc, ops.Codes16) and yc.shape == tuple(y.shape)
-    want = O.ste_codes(yf, O.act_scale(thr_out, signed_out, 8), thr_out, np.float32(-thr_out) if signed_out else np.float32(0))
+    want = O.ste_codes(yf, O.act_scale(thr_out, signed_out, out_width), thr_out, np.float32(-thr_out) if signed_out else np.float32(0))
     assert np.array_equal(yc.t.cpu().numpy(), O.to_c16(want.astype(np.int64), 0 if signed_out else 128)), "C16 codes"
     assert torch.equal(stat, stat_c), "the statistic is that of the fp32 values"
 
 
 @pytest.mark.parametrize("case", PW_CASES, ids=["%dx%d->%d@%dx%d/s%d" % c for c in PW_CASES])
 @pytest.mark.parametrize("mode", ["u8_bn_relu", "s8_res"])
-def test_pointwise_consumer_of_codes_equals_consumer_of_fp32(dev, ops, case, mode, regime=None):
+def test_pointwise_consumer_of_codes_equals_consumer_of_fp32(dev, ops, case, mode, regime=None, width=8):
     n, cin, cout, h, w, stride = case
     rng = np.random.default_rng(sum(case) + 5)
     signed = "s8" in mode
@@ -83,26 +84,26 @@ def test_pointwise_consumer_of_codes_equals_consumer_of_fp32(dev, ops, case, mod
     wt = (rng.standard_normal((cout, cin, 1, 1)) * 0.2).astype(np.float32)
     sc = rng.uniform(0.3, 1.5, cout).astype(np.float32)
     sh = rng.standard_normal(cout).astype(np.float32)
-    x, wt, thr = R.stored(regime, x, signed, wt, cout, np.float32(2.3))
-    R.check(regime, x, thr, signed, w=wt, rps=cout)
+    x, wt, thr = R.stored(regime, x, signed, wt, cout, np.float32(2.3), width=width)
+    R.check(regime, x, thr, signed, w=wt, rps=cout, width=width)
     codes, scales, rowsum = ops.weight_codes(T(wt, dev), cout, 8)
     thr_t = T(np.float32([thr]), dev)
     flags = ops.act_flags(signed=signed)
     ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
-    kw = dict(in_thr=thr_t, width=8, flags=flags, bn_scale=T(sc, dev), bn_shift=T(sh, dev), stride=stride,
+    kw = dict(in_thr=thr_t, width=width, flags=flags, bn_scale=T(sc, dev), bn_shift=T(sh, dev), stride=stride,
               act="relu" if "relu" in mode else None)
     if "res" in mode:
         kw["residual"] = T((rng.standard_normal((n, cout, ho, wo)) * 3).astype(np.float32), dev)
     stat_in = T(O.absmax_per_sample(x), dev)
     cur_a, cur_b = torch.zeros(1, device=dev), torch.zeros(1, device=dev)
     want, want_stat = ops.pwconv_i8(T(x, dev), codes, scales, rowsum, form="split", in_stat=stat_in, cur_out=cur_a, **kw)
-    cx = O.ste_codes(x, O.act_scale(thr, signed, 8), thr, np.float32(-thr) if signed else np.float32(0))
-    xc = ops.Codes16(T(O.to_c16(cx.astype(np.int64), 0 if signed else 128), dev), x.shape, thr_t, 8, flags)
+    cx = O.ste_codes(x, O.act_scale(thr, signed, width), thr, np.float32(-thr) if signed else np.float32(0))
+    xc = ops.Codes16(T(O.to_c16(cx.astype(np.int64), 0 if signed else 128), dev), x.shape, thr_t, width, flags)
     got, got_stat = ops.pwconv_i8(xc, codes, scales, rowsum, in_stat=stat_in, cur_out=cur_b, **kw)
     assert torch.equal(got, want), "output of the consumer fed with codes"
     assert torch.equal(got_stat, want_stat) and torch.equal(cur_a, cur_b)
     with pytest.raises(ValueError, match="another threshold"):
-        ops.pwconv_i8(xc, codes, scales, rowsum, in_thr=T(np.float32([thr]), dev), width=8, flags=flags)
+        ops.pwconv_i8(xc, codes, scales, rowsum, in_thr=T(np.float32([thr]), dev), width=width, flags=flags)
 
 
 BOTH_CASES = [(3, 256, 64, 56, 56, 1), (2, 512, 128, 28, 28, 1), (5, 1024, 256, 14, 14, 1), (7, 2048, 512, 7, 7, 1), (2, 256, 64, 9, 11, 1),
@@ -113,7 +114,7 @@ BOTH_CASES = [(3, 256, 64, 56, 56, 1), (2, 512, 128, 28, 28, 1), (5, 1024, 256, 
 
 
 @pytest.mark.parametrize("case", BOTH_CASES, ids=["%dx%d->%d@%dx%d/s%d" % c for c in BOTH_CASES])
-def test_pointwise_between_two_code_tensors(dev, ops, case, regime=None):
+def test_pointwise_between_two_code_tensors(dev, ops, case, regime=None, width=8, out_width=8):
     """Codes in AND codes out (round 4: the first 1x1 of a ResNet unit fed by the trunk's code copy, handing codes to the
     unit's 3x3): == the codes of what the fp32-in / fp32-out call computes, statistic and batch mean unchanged."""
     n, cin, cout, h, w, stride = case
@@ -122,21 +123,22 @@ def test_pointwise_between_two_code_tensors(dev, ops, case, regime=None):
     wt = (rng.standard_normal((cout, cin, 1, 1)) * 0.05).astype(np.float32)
     sc = rng.uniform(0.3, 1.5, cout).astype(np.float32)
     sh = rng.standard_normal(cout).astype(np.float32)
-    x, wt, thr = R.stored(regime, x, False, wt, 1, np.float32(2.3))
-    R.check(regime, x, thr, False, w=wt, rps=1)
+    x, wt, thr = R.stored(regime, x, False, wt, 1, np.float32(2.3), width=width)
+    R.check(regime, x, thr, False, w=wt, rps=1, width=width)
     codes, scales, rowsum = ops.weight_codes(T(wt, dev), 1, 8)
     thr_t = T(np.float32([thr]), dev)
     stat_in = T(O.absmax_per_sample(x), dev)
     cur_a, cur_b = torch.zeros(1, device=dev), torch.zeros(1, device=dev)
-    kw = dict(in_thr=thr_t, width=8, flags=0, bn_scale=T(sc, dev), bn_shift=T(sh, dev), act="relu", stride=stride, in_stat=stat_in)
+    kw = dict(in_thr=thr_t, width=width, flags=0, bn_scale=T(sc, dev), bn_shift=T(sh, dev), act="relu", stride=stride, in_stat=stat_in)
     want, want_stat = ops.pwconv_i8(T(x, dev), codes, scales, rowsum, form="split", cur_out=cur_a, **kw)
-    thr2 = R.output_threshold(regime, want.cpu().numpy(), False, np.float32(1.7))
-    R.check_output(regime, want.cpu().numpy(), thr2, False)
-    cx = O.ste_codes(x, O.act_scale(thr, False, 8), thr, np.float32(0))
-    xc = ops.Codes16(T(O.to_c16(cx.astype(np.int64), 128), dev), x.shape, thr_t, 8, 0)
-    yc, st = ops.pwconv_i8(xc, codes, scales, rowsum, cur_out=cur_b, out_codes=dict(thr=T(np.float32([thr2]), dev), width=8, flags=0),
+    thr2 = R.output_threshold(regime, want.cpu().numpy(), False, np.float32(1.7), width=out_width)
+    R.check_output(regime, want.cpu().numpy(), thr2, False, width=out_width)
+    cx = O.ste_codes(x, O.act_scale(thr, False, width), thr, np.float32(0))
+    xc = ops.Codes16(T(O.to_c16(cx.astype(np.int64), 128), dev), x.shape, thr_t, width, 0)
+    yc, st = ops.pwconv_i8(xc, codes, scales, rowsum, cur_out=cur_b, out_codes=dict(thr=T(np.float32([thr2]), dev), width=out_width,
+                                                                              flags=0),
                            **kw)
-    wantc = O.to_c16(O.ste_codes(want.cpu().numpy(), O.act_scale(thr2, False, 8), thr2, np.float32(0)).astype(np.int64), 128)
+    wantc = O.to_c16(O.ste_codes(want.cpu().numpy(), O.act_scale(thr2, False, out_width), thr2, np.float32(0)).astype(np.int64), 128)
     assert isinstance(yc, ops.Codes16) and yc.shape == tuple(want.shape)
     assert np.array_equal(yc.t.cpu().numpy(), wantc), "codes of the output"
     assert torch.equal(st, want_stat) and torch.equal(cur_a, cur_b)
@@ -147,7 +149,7 @@ DUAL_CASES = [(43, 64, 256, 56, 56), (3, 64, 256, 9, 11), (5, 128, 512, 28, 28),
 
 
 @pytest.mark.parametrize("case", DUAL_CASES, ids=["%dx%d->%d@%dx%d" % c for c in DUAL_CASES])
-def test_closing_pointwise_stores_the_trunk_twice(dev, ops, case, regime=None):
+def test_closing_pointwise_stores_the_trunk_twice(dev, ops, case, regime=None, width=8, out_width=8):
     """fq_pwconv_i8_c16_dual (round 4): codes in, residual added, fp32 out - and the codes of that output under the NEXT
     consumer's threshold beside it.  y, statistic and batch mean are those of the one-output call; the side tensor holds the
     oracle's codes of y.  (The first case runs the streaming form - more than 4096 pixel tiles -, the others the split form.)"""
@@ -158,31 +160,31 @@ def test_closing_pointwise_stores_the_trunk_twice(dev, ops, case, regime=None):
     sc = rng.uniform(0.3, 1.5, cout).astype(np.float32)
     sh = rng.standard_normal(cout).astype(np.float32)
     res = (rng.standard_normal((n, cout, h, w)) * 2).astype(np.float32)
-    x, wt, thr = R.stored(regime, x, False, wt, 1, np.float32(2.3))
-    R.check(regime, x, thr, False, w=wt, rps=1)
+    x, wt, thr = R.stored(regime, x, False, wt, 1, np.float32(2.3), width=width)
+    R.check(regime, x, thr, False, w=wt, rps=1, width=width)
     codes, scales, rowsum = ops.weight_codes(T(wt, dev), 1, 8)
     thr_t = T(np.float32([thr]), dev)
     stat_in = T(O.absmax_per_sample(x), dev)
-    cx = O.ste_codes(x, O.act_scale(thr, False, 8), thr, np.float32(0))
-    xc = ops.Codes16(T(O.to_c16(cx.astype(np.int64), 128), dev), x.shape, thr_t, 8, 0)
+    cx = O.ste_codes(x, O.act_scale(thr, False, width), thr, np.float32(0))
+    xc = ops.Codes16(T(O.to_c16(cx.astype(np.int64), 128), dev), x.shape, thr_t, width, 0)
     cur_a, cur_b = torch.zeros(1, device=dev), torch.zeros(1, device=dev)
-    kw = dict(in_thr=thr_t, width=8, flags=0, bn_scale=T(sc, dev), bn_shift=T(sh, dev), act="relu", in_stat=stat_in,
+    kw = dict(in_thr=thr_t, width=width, flags=0, bn_scale=T(sc, dev), bn_shift=T(sh, dev), act="relu", in_stat=stat_in,
               residual=T(res, dev))
     want, want_stat = ops.pwconv_i8(xc, codes, scales, rowsum, cur_out=cur_a, **kw)
-    thr2 = R.output_threshold(regime, want.cpu().numpy(), False, np.float32(3.1))
-    R.check_output(regime, want.cpu().numpy(), thr2, False)
+    thr2 = R.output_threshold(regime, want.cpu().numpy(), False, np.float32(3.1), width=out_width)
+    R.check_output(regime, want.cpu().numpy(), thr2, False, width=out_width)
     got, got_stat, side = ops.pwconv_i8(xc, codes, scales, rowsum, cur_out=cur_b,
-                                        side_codes=dict(thr=T(np.float32([thr2]), dev), width=8, flags=0), **kw)
+                                        side_codes=dict(thr=T(np.float32([thr2]), dev), width=out_width, flags=0), **kw)
     assert torch.equal(got, want) and torch.equal(got_stat, want_stat) and torch.equal(cur_a, cur_b)
-    wantc = O.to_c16(O.ste_codes(want.cpu().numpy(), O.act_scale(thr2, False, 8), thr2, np.float32(0)).astype(np.int64), 128)
+    wantc = O.to_c16(O.ste_codes(want.cpu().numpy(), O.act_scale(thr2, False, out_width), thr2, np.float32(0)).astype(np.int64), 128)
     assert isinstance(side, ops.Codes16) and side.shape == tuple(want.shape)
     assert np.array_equal(side.t.cpu().numpy(), wantc), "the side tensor's codes"
     # ... and a consumer fed with the side tensor computes what it computes from the fp32 trunk
     w2 = (rng.standard_normal((cout // 4, cout, 1, 1)) * 0.05).astype(np.float32)
     c2, s2, r2 = ops.weight_codes(T(w2, dev), 1, 8)
     thr2_t = side.thr
-    a, _ = ops.pwconv_i8(want, c2, s2, r2, in_thr=thr2_t, width=8, flags=0, act="relu", form="split")
-    b, _ = ops.pwconv_i8(side, c2, s2, r2, in_thr=thr2_t, width=8, flags=0, act="relu")
+    a, _ = ops.pwconv_i8(want, c2, s2, r2, in_thr=thr2_t, width=out_width, flags=0, act="relu", form="split")
+    b, _ = ops.pwconv_i8(side, c2, s2, r2, in_thr=thr2_t, width=out_width, flags=0, act="relu")
     assert torch.equal(a, b)
 
 
@@ -228,7 +230,7 @@ DW_CASES = [(2, 96, 112, 112, 2), (2, 144, 56, 56, 1), (3, 24, 9, 11, 1), (2, 19
 
 @pytest.mark.parametrize("case", DW_CASES, ids=["%dx%d@%dx%d/s%d" % c for c in DW_CASES])
 @pytest.mark.parametrize("signed", [False, True], ids=["u8", "s8"])
-def test_depthwise_between_two_code_tensors(dev, ops, case, signed, regime=None):
+def test_depthwise_between_two_code_tensors(dev, ops, case, signed, regime=None, width=8, out_width=8):
     """fq_dwconv3x3_c16: codes in (the threshold of this layer), codes out (the threshold of the next) == the oracle's codes of
     what fq_dwconv3x3 computes from the fp32 tensor under the same stored threshold; the statistic is that of the fp32
     values."""
@@ -240,22 +242,22 @@ def test_depthwise_between_two_code_tensors(dev, ops, case, signed, regime=None)
     wt = (rng.standard_normal((c, 1, 3, 3)) * 0.4).astype(np.float32)
     sc = rng.uniform(0.3, 1.5, c).astype(np.float32)
     sh = rng.standard_normal(c).astype(np.float32)
-    x, _, thr = R.stored(regime, x, signed, thr=np.float32(2.3))
-    R.check(regime, x, thr, signed)
+    x, _, thr = R.stored(regime, x, signed, thr=np.float32(2.3), width=width)
+    R.check(regime, x, thr, signed, width=width)
     thr_t = T(np.float32([thr]), dev)
     flags = ops.act_flags(signed=signed)
     stat_in = T(O.absmax_per_sample(x), dev)
     cur_a, cur_b = torch.zeros(1, device=dev), torch.zeros(1, device=dev)
-    kw = dict(stride=stride, in_stat=stat_in, in_thr=thr_t, width=8, flags=flags, bn_scale=T(sc, dev), bn_shift=T(sh, dev),
+    kw = dict(stride=stride, in_stat=stat_in, in_thr=thr_t, width=width, flags=flags, bn_scale=T(sc, dev), bn_shift=T(sh, dev),
               act="relu6")
     want, want_stat = ops.dwconv3x3(T(x, dev), T(wt, dev), cur_out=cur_a, **kw)
-    thr2 = R.output_threshold(regime, want.cpu().numpy(), False, np.float32(1.7))
-    R.check_output(regime, want.cpu().numpy(), thr2, False)
-    cx = O.ste_codes(x, O.act_scale(thr, signed, 8), thr, np.float32(-thr) if signed else np.float32(0))
-    xc = ops.Codes16(T(O.to_c16(cx.astype(np.int64), 0 if signed else 128), dev), x.shape, thr_t, 8, flags)
-    yc, st = ops.dwconv3x3_c16(xc, T(wt, dev), cur_out=cur_b, out_codes=dict(thr=T(np.float32([thr2]), dev), width=8, flags=0),
+    thr2 = R.output_threshold(regime, want.cpu().numpy(), False, np.float32(1.7), width=out_width)
+    R.check_output(regime, want.cpu().numpy(), thr2, False, width=out_width)
+    cx = O.ste_codes(x, O.act_scale(thr, signed, width), thr, np.float32(-thr) if signed else np.float32(0))
+    xc = ops.Codes16(T(O.to_c16(cx.astype(np.int64), 0 if signed else 128), dev), x.shape, thr_t, width, flags)
+    yc, st = ops.dwconv3x3_c16(xc, T(wt, dev), cur_out=cur_b, out_codes=dict(thr=T(np.float32([thr2]), dev), width=out_width, flags=0),
                                **kw)
-    wantc = O.to_c16(O.ste_codes(want.cpu().numpy(), O.act_scale(thr2, False, 8), thr2, np.float32(0)).astype(np.int64), 128)
+    wantc = O.to_c16(O.ste_codes(want.cpu().numpy(), O.act_scale(thr2, False, out_width), thr2, np.float32(0)).astype(np.int64), 128)
     assert yc.shape == tuple(want.shape)
     assert np.array_equal(yc.t.cpu().numpy(), wantc), "codes of the depthwise output"
     assert torch.equal(st, want_stat) and torch.equal(cur_a, cur_b)
@@ -310,7 +312,7 @@ C3_CASES = [(2, 64, 64, 9, 11), (3, 128, 128, 7, 7), (2, 256, 256, 5, 6), (1, 51
 
 @pytest.mark.parametrize("case", C3_CASES, ids=["%dx%d->%d@%dx%d" % c for c in C3_CASES])
 @pytest.mark.parametrize("signed", [False, True], ids=["u8", "s8"])
-def test_dense3x3_with_codes_on_both_sides(dev, ops, case, signed, regime=None):
+def test_dense3x3_with_codes_on_both_sides(dev, ops, case, signed, regime=None, width=8, out_width=8):
     """The 3x3 convolution in the middle of a bottleneck: C16 in == fp32 in, C16 out == oracle codes of the fp32 output, and
     both at once == the codes of the all-fp32 call."""
     n, cin, cout, h, w = case
@@ -321,21 +323,21 @@ def test_dense3x3_with_codes_on_both_sides(dev, ops, case, signed, regime=None):
     wt = (rng.standard_normal((cout, cin, 3, 3)) * 0.1).astype(np.float32)
     sc = rng.uniform(0.3, 1.5, cout).astype(np.float32)
     sh = rng.standard_normal(cout).astype(np.float32)
-    x, wt, thr = R.stored(regime, x, signed, wt, 1, np.float32(2.3))
-    R.check(regime, x, thr, signed, w=wt, rps=1, taps=9)
+    x, wt, thr = R.stored(regime, x, signed, wt, 1, np.float32(2.3), width=width)
+    R.check(regime, x, thr, signed, w=wt, rps=1, taps=9, width=width)
     codes, scales, rowsum = ops.weight_codes_3x3(T(wt, dev), 1, 8)
     thr_t = T(np.float32([thr]), dev)
     flags = ops.act_flags(signed=signed)
-    kw = dict(in_thr=thr_t, width=8, flags=flags, bn_scale=T(sc, dev), bn_shift=T(sh, dev), act="relu")
+    kw = dict(in_thr=thr_t, width=width, flags=flags, bn_scale=T(sc, dev), bn_shift=T(sh, dev), act="relu")
     want, want_stat = ops.conv3x3_i8(T(x, dev), codes, scales, rowsum, **kw)
-    cx = O.ste_codes(x, O.act_scale(thr, signed, 8), thr, np.float32(-thr) if signed else np.float32(0))
-    xc = ops.Codes16(T(O.to_c16(cx.astype(np.int64), 0 if signed else 128), dev), x.shape, thr_t, 8, flags)
+    cx = O.ste_codes(x, O.act_scale(thr, signed, width), thr, np.float32(-thr) if signed else np.float32(0))
+    xc = ops.Codes16(T(O.to_c16(cx.astype(np.int64), 0 if signed else 128), dev), x.shape, thr_t, width, flags)
     got, got_stat = ops.conv3x3_i8(xc, codes, scales, rowsum, **kw)
     assert torch.equal(got, want) and torch.equal(got_stat, want_stat), "codes in"
-    thr2 = R.output_threshold(regime, want.cpu().numpy(), False, np.float32(1.1))
-    R.check_output(regime, want.cpu().numpy(), thr2, False)
-    oc = dict(thr=T(np.float32([thr2]), dev), width=8, flags=0)
-    wantc = O.to_c16(O.ste_codes(want.cpu().numpy(), O.act_scale(thr2, False, 8), thr2, np.float32(0)).astype(np.int64), 128)
+    thr2 = R.output_threshold(regime, want.cpu().numpy(), False, np.float32(1.1), width=out_width)
+    R.check_output(regime, want.cpu().numpy(), thr2, False, width=out_width)
+    oc = dict(thr=T(np.float32([thr2]), dev), width=out_width, flags=0)
+    wantc = O.to_c16(O.ste_codes(want.cpu().numpy(), O.act_scale(thr2, False, out_width), thr2, np.float32(0)).astype(np.int64), 128)
     for src, what in ((T(x, dev), "codes out"), (xc, "codes in and out")):
         yc, st = ops.conv3x3_i8(src, codes, scales, rowsum, out_codes=oc, **kw)
         assert np.array_equal(yc.t.cpu().numpy(), wantc), what

@@ -56,7 +56,7 @@ MODES = ["online_u8_bn_relu", "online_s8_bn_none", "offline_u8_bias_relu6"]
 
 @pytest.mark.parametrize("case", CASES, ids=["%dx%d->%d@%dx%d%s" % (c[:5] + ("+res" if c[5] else "",)) for c in CASES])
 @pytest.mark.parametrize("mode", MODES)
-def test_gap_producer_equals_the_two_launches_and_the_host_twin(dev, ops, case, mode, regime=None):
+def test_gap_producer_equals_the_two_launches_and_the_host_twin(dev, ops, case, mode, regime=None, width=8):
     n, cin, cout, h, w, with_res = case
     rng = np.random.default_rng(cin + cout + n)
     signed = "s8" in mode
@@ -66,11 +66,12 @@ def test_gap_producer_equals_the_two_launches_and_the_host_twin(dev, ops, case, 
     wt = (rng.standard_normal((cout, cin)) * 0.05).astype(np.float32)
     res = (rng.standard_normal((n, cout, h, w)) * 2).astype(np.float32) if with_res else None
     offline, thr = "offline" in mode, np.float32(2.5)
-    x, wt, rthr = R.apply(regime, x, signed, wt, 1, thr=thr if offline else None)
+    x, wt, rthr = R.apply(regime, x, signed, wt, 1, thr=thr if offline else None, width=width)
     if regime is not None and rthr is not None:
         offline, thr = True, np.float32(rthr)
     if regime is not None:
-        R.check(regime, x, thr if offline else R.O.batch_mean(R.O.absmax_per_sample(x)), signed, w=wt, rps=1)
+        R.check(regime, x, thr if offline else R.O.batch_mean(R.O.absmax_per_sample(x)), signed, w=wt, rps=1,
+                width=width)
     if "bias" in mode:
         bn, bias = (None, None), (rng.standard_normal(cout) * 0.1).astype(np.float32)
     else:
@@ -82,7 +83,7 @@ def test_gap_producer_equals_the_two_launches_and_the_host_twin(dev, ops, case, 
     codes, scales, rowsum = ops.weight_codes(_t(wt, dev), 1, 8)
     xstat = ops.absmax_per_sample(xt)
     plan = dict(in_thr=torch.full((1,), float(thr), device=dev), in_stat=xstat) if offline else dict(in_stat=xstat)
-    kw = dict(width=8, flags=flags, bn_scale=_t(bn[0], dev), bn_shift=_t(bn[1], dev), act=act, residual=_t(res, dev))
+    kw = dict(width=width, flags=flags, bn_scale=_t(bn[0], dev), bn_shift=_t(bn[1], dev), act=act, residual=_t(res, dev))
     cur_a, cur_b = torch.zeros(1, device=dev), torch.zeros(1, device=dev)
     y, _ = ops.pwconv_i8(xt, codes, scales, rowsum, _t(bias, dev), cur_out=cur_a, **kw, **plan)
     want, want_stat = ops.global_avg_pool_stat(y, want_stat=True)
@@ -95,7 +96,7 @@ def test_gap_producer_equals_the_two_launches_and_the_host_twin(dev, ops, case, 
         from oracle import host as H
         hy, _ = H.pwconv_i8(x, wt.reshape(cout, cin, 1, 1), 1, 8, in_max=thr if offline else None,
                             in_stat=H.absmax_per_sample(x), signed=signed, bias=bias, bn_scale=bn[0], bn_shift=bn[1], act=act,
-                            want_stat=True, residual=res)
+                            want_stat=True, residual=res, width=width)
         hg, hs = H.global_avg_pool(hy, want_stat=True)
         _eq(N(got).reshape(n, cout), np.asarray(hg).reshape(n, cout), "host twin: means")
         _eq(N(got_stat), hs, "host twin: statistic")

@@ -49,9 +49,10 @@ def _id(c):
     return "%dx%d->%d->%d@%dx%d" % c
 
 
-def _make(case, signed, regime=None):
+def _make(case, signed, regime=None, width=8, mid_width=8):
     """`regime`: a value regime of tests/regimes.py on the input as drawn (every quantiser of the chain works online: the
-    regimes with a threshold of their own have none to be stored in)."""
+    regimes with a threshold of their own have none to be stored in).  `width`: the activation width of both 1x1 inputs;
+    `mid_width`: that of the depthwise layer's input, the tensor in the middle of the first pair."""
     n, cin, cmid, cout, h, w = case
     rng = np.random.default_rng(1000 * cin + 37 * h + w + cout + (7 if signed else 0))
     x = rng.standard_normal((n, cin, h, w)).astype(np.float32) * np.float32(1.7)
@@ -59,7 +60,7 @@ def _make(case, signed, regime=None):
         x = np.maximum(x, 0)
     x = x * (np.float32(0.55) + np.float32(0.4) * np.arange(n, dtype=np.float32)).reshape(n, 1, 1, 1)
     x[0, 0, 0, 0] = np.float32(5.5)
-    k = dict(case=case, signed=signed, x=x.astype(np.float32))
+    k = dict(case=case, signed=signed, x=x.astype(np.float32), width=width, mid_width=mid_width)
     k["w1"] = (rng.standard_normal((cmid, cin)) * 0.2).astype(np.float32)
     k["dww"] = (rng.standard_normal((cmid, 1, 3, 3)) * 0.3).astype(np.float32)
     k["w2"] = (rng.standard_normal((cout, cmid)) * 0.2).astype(np.float32)
@@ -72,8 +73,8 @@ def _make(case, signed, regime=None):
     k["act3"] = "relu"
     if regime is not None:
         assert regime not in ("saturated", "allones_divisor")
-        k["x"], k["w1"], _ = R.apply(regime, k["x"], signed, k["w1"], cmid)
-        R.check(regime, k["x"], R.stored_threshold(k["x"]), signed)
+        k["x"], k["w1"], _ = R.apply(regime, k["x"], signed, k["w1"], cmid, width=width)
+        R.check(regime, k["x"], R.stored_threshold(k["x"]), signed, width=width)
     return k
 
 
@@ -94,14 +95,14 @@ def _first_half(k, o, dev, ops, empty):
     cur1 = torch.zeros(1, device=dev)
     xstat = ops.absmax_per_sample(o["x"])
     xcodes = empty(ops.pair_codes_shape(o["x"].shape), torch.int8)
-    ystat = ops.pwconv_i8_stat(o["x"], *o["w1"], None, in_stat=xstat, width=8, flags=o["flags"], cur_out=cur1,
+    ystat = ops.pwconv_i8_stat(o["x"], *o["w1"], None, in_stat=xstat, width=k["width"], flags=o["flags"], cur_out=cur1,
                                bn_scale=o["bn1"][0], bn_shift=o["bn1"][1], act=k["act1"], x_codes_out=xcodes)
     return xstat, xcodes, ystat
 
 
 def _fused(k, o, dev, ops, xstat, xcodes, ystat, cur2, x=None, **more):
-    return ops.pwdw_fused(o["x"] if x is None else x, *o["w1"], o["dww"], in_stat=xstat, width=8, flags=o["flags"],
-                          pw_bn_scale=o["bn1"][0], pw_bn_shift=o["bn1"][1], pw_act=k["act1"], mid_stat=ystat, mid_width=8,
+    return ops.pwdw_fused(o["x"] if x is None else x, *o["w1"], o["dww"], in_stat=xstat, width=k["width"], flags=o["flags"],
+                          pw_bn_scale=o["bn1"][0], pw_bn_shift=o["bn1"][1], pw_act=k["act1"], mid_stat=ystat, mid_width=k["mid_width"],
                           mid_flags=o["flags"], mid_cur_out=cur2, stride=1, dw_bn_scale=o["bn2"][0], dw_bn_shift=o["bn2"][1],
                           dw_act=k["act2"], x_codes=xcodes, **more)
 
@@ -115,7 +116,7 @@ def _stored(k, dev, ops):
     cur2, cur3 = torch.zeros(1, device=dev), torch.zeros(1, device=dev)
     z, zstat = _fused(k, o, dev, ops, xstat, xcodes, ystat, cur2)
     buf = fill(ops.pair_codes_shape(z.shape), torch.int8)
-    pstat = ops.pwconv_i8_stat(z, *o["w2"], None, in_stat=zstat, width=8, flags=o["flags"], cur_out=cur3, bn_scale=o["bn3"][0],
+    pstat = ops.pwconv_i8_stat(z, *o["w2"], None, in_stat=zstat, width=k["width"], flags=o["flags"], cur_out=cur3, bn_scale=o["bn3"][0],
                                bn_shift=o["bn3"][1], act=k["act3"], x_codes_out=buf)
     return dict(ystat=N(ystat), zstat=N(zstat), cur2=N(cur2), pstat=N(pstat), cur3=N(cur3), buf=N(buf), z=N(z))
 
@@ -136,8 +137,8 @@ def _chained(k, dev, ops, put=None, empty=None):
     buf = empty(ops.pair_codes_shape((n, cmid, h, w)), torch.int8)
     nan_z = torch.full((n, cmid, h, w), float("nan"), device=dev)
     front = dict(x_codes=ycodes, w=o["dww"], bias=None, bn_scale=o["bn2"][0], bn_shift=o["bn2"][1], act=k["act2"],
-                 in_stat=ystat, width=8, flags=o["flags"])
-    pstat = ops.pwconv_i8_stat(nan_z, *o["w2"], None, in_stat=zstat, width=8, flags=o["flags"], cur_out=cur3,
+                 in_stat=ystat, width=k["mid_width"], flags=o["flags"])
+    pstat = ops.pwconv_i8_stat(nan_z, *o["w2"], None, in_stat=zstat, width=k["width"], flags=o["flags"], cur_out=cur3,
                                bn_scale=o["bn3"][0], bn_shift=o["bn3"][1], act=k["act3"], x_codes_out=buf, front=front)
     return dict(ystat=N(ystat), zstat=N(zstat), cur2=N(cur2), pstat=N(pstat), cur3=N(cur3), buf=N(buf), ycodes=N(ycodes),
                 x=N(o["x"]))
@@ -148,8 +149,9 @@ def _host_mid_codes(k, ops, dev):
     from oracle import host as H
     n, cin, cmid, cout, h, w = k["case"]
     y, ystat = H.pwconv_i8(k["x"], k["w1"].reshape(cmid, cin, 1, 1), cmid, 8, in_stat=H.absmax_per_sample(k["x"]),
-                           signed=k["signed"], bias=None, bn_scale=k["bn1"][0], bn_shift=k["bn1"][1], act=k["act1"], want_stat=True)
-    codes = H.fake_quant_online_prestat(y, ystat, 8, H.act_flags(signed=k["signed"]), want_codes=True)[2]
+                           signed=k["signed"], bias=None, bn_scale=k["bn1"][0], bn_shift=k["bn1"][1], act=k["act1"], want_stat=True,
+                           width=k["width"])
+    codes = H.fake_quant_online_prestat(y, ystat, k["mid_width"], H.act_flags(signed=k["signed"]), want_codes=True)[2]
     return (codes.astype(np.int64) & 0xFF).astype(np.uint8).view(np.int8).reshape(n, cmid, h * w), ystat
 
 

@@ -381,26 +381,28 @@ def test_dwconv3x3_vs_oracle(dev, ops, shape, stride, mode):
     _dwconv_case(dev, ops, shape, stride, mode)
 
 
-def _dwconv_case(dev, ops, shape, stride, mode, twin=False, regime=None):
+def _dwconv_case(dev, ops, shape, stride, mode, twin=False, regime=None, width=None):
     """`twin`: also bit for bit against the host twin's true fmaf chain (the poisoned runs of tests/test_gpu_poison.py).
-    `regime`: a value regime of tests/regimes.py on the data as drawn; the host twin is then the bit-for-bit reference."""
+    `regime`: a value regime of tests/regimes.py on the data as drawn; the host twin is then the bit-for-bit reference.
+    `width`: the activation width of a quantising mode; None is the mode's own (4 under `offline_signed`, 8 otherwise)."""
+    width = width or (4 if mode == "offline_signed" else 8)
     rng = np.random.default_rng(sum(shape) * 7 + stride)
     n, c, h, w = shape
     x = (rng.standard_normal(shape) * 2).astype(np.float32)
     if "signed" not in mode:
         x = np.maximum(x, 0)
     wt = (rng.standard_normal((c, 1, 3, 3)) * 0.5).astype(np.float32)
-    x, _, rthr = R.apply(regime, x, "signed" in mode, width=4 if mode == "offline_signed" else 8)
+    x, _, rthr = R.apply(regime, x, "signed" in mode, width=width)
     twin = twin or regime is not None
     kw, okw = {}, {}
     if mode in ("online", "bn_relu_online"):
         stat = O.absmax_per_sample(x)
-        kw.update(in_stat=T(stat, dev), width=8, flags=0)
-        okw.update(in_max=O.batch_mean(stat), signed=False, width=8)
+        kw.update(in_stat=T(stat, dev), width=width, flags=0)
+        okw.update(in_max=O.batch_mean(stat), signed=False, width=width)
     if mode == "offline_signed":
         thr = np.float32(1.7)
-        kw.update(in_thr=T(np.float32([thr]), dev), width=4, flags=ops.act_flags(signed=True))
-        okw.update(in_max=thr, signed=True, width=4)
+        kw.update(in_thr=T(np.float32([thr]), dev), width=width, flags=ops.act_flags(signed=True))
+        okw.update(in_max=thr, signed=True, width=width)
     if "in_max" in okw:
         _regime_threshold(regime, rthr, kw, okw, dev, x)
         R.check(regime, x, okw["in_max"], okw["signed"], width=okw["width"])
@@ -586,8 +588,9 @@ def _regime_threshold(regime, rthr, kw, okw, dev, x=None):
         okw["in_max"] = np.float32(rthr)
 
 
-def _pwconv_case(dev, ops, case, mode, form=None, regime=None):
-    """`regime`: a value regime of tests/regimes.py, applied to the data as drawn (tests/test_gpu_value_regimes.py)."""
+def _pwconv_case(dev, ops, case, mode, form=None, regime=None, width=8):
+    """`regime`: a value regime of tests/regimes.py, applied to the data as drawn (tests/test_gpu_value_regimes.py).
+    `width`: the activation width of the launch and of both references (tests/test_gpu_act_widths.py)."""
     n, cin, cout, h, w = case
     rng = np.random.default_rng(sum(case))
     x = (rng.standard_normal((n, cin, h, w)) * 2).astype(np.float32)
@@ -596,7 +599,8 @@ def _pwconv_case(dev, ops, case, mode, form=None, regime=None):
     wt = (rng.standard_normal((cout, cin, 1, 1)) * rng.uniform(0.05, 1.0, (cout, 1, 1, 1))).astype(np.float32)
     per_channel = "channel" in mode
     wt_width = 4 if "w4" in mode else 8
-    x, wt, rthr = R.apply(regime, x, not mode.startswith("online"), wt, 1 if per_channel else cout)
+    x, wt, rthr = R.apply(regime, x, not mode.startswith("online"), wt, 1 if per_channel else cout, width=width,
+                           lo_neg_max=False if mode.startswith("dense") else None)
     codes, scales, rowsum = ops.weight_codes(T(wt, dev), 1 if per_channel else cout, wt_width)
     ocodes, oscales = O.weight_codes(wt, 1 if per_channel else cout, wt_width)
     _eq(N(codes)[:cout, :cin], ocodes.astype(np.int8), "weight codes")
@@ -606,19 +610,19 @@ def _pwconv_case(dev, ops, case, mode, form=None, regime=None):
     kw, okw = {}, {}
     if mode.startswith("online"):
         stat = O.absmax_per_sample(x)
-        kw.update(in_stat=T(stat, dev), width=8, flags=0)
-        okw.update(in_max=O.batch_mean(stat), signed=False, width=8)
+        kw.update(in_stat=T(stat, dev), width=width, flags=0)
+        okw.update(in_max=O.batch_mean(stat), signed=False, width=width)
     elif mode.startswith("offline"):
         thr = np.float32(2.3)
-        kw.update(in_thr=T(np.float32([thr]), dev), width=8, flags=ops.act_flags(signed=True))
-        okw.update(in_max=thr, signed=True, width=8)
+        kw.update(in_thr=T(np.float32([thr]), dev), width=width, flags=ops.act_flags(signed=True))
+        okw.update(in_max=thr, signed=True, width=width)
     else:   # Dense quirk: signed levels, clip at zero
         stat = O.absmax_per_sample(x)
-        kw.update(in_stat=T(stat, dev), width=8, flags=ops.act_flags(signed=True, lo_neg_max=False))
-        okw.update(in_max=O.batch_mean(stat), signed=True, width=8, lo_neg_max=False)
+        kw.update(in_stat=T(stat, dev), width=width, flags=ops.act_flags(signed=True, lo_neg_max=False))
+        okw.update(in_max=O.batch_mean(stat), signed=True, width=width, lo_neg_max=False)
     _regime_threshold(regime, rthr, kw, okw, dev, x)
     R.check(regime, x, okw["in_max"], okw["signed"], lo_neg_max=okw.get("lo_neg_max"), w=wt, rps=1 if per_channel else cout,
-            wt_width=wt_width)
+            wt_width=wt_width, width=width)
     if "bn_relu" in mode:
         sc = rng.uniform(0.3, 1.5, cout).astype(np.float32)
         sh = rng.standard_normal(cout).astype(np.float32)
@@ -655,7 +659,7 @@ PW_RES_CASES = [("split", (2, 256, 1024, 14, 14)), ("split", (3, 512, 2048, 7, 7
 
 @pytest.mark.parametrize("form,case", PW_RES_CASES, ids=["%s-%dx%d->%d@%dx%d" % ((f,) + c) for f, c in PW_RES_CASES])
 @pytest.mark.parametrize("mode", ["online_u8_bn_relu", "offline_s8_channel_w4_bn_none"])
-def test_pwconv_i8_residual_vs_oracle(dev, ops, form, case, mode, regime=None):
+def test_pwconv_i8_residual_vs_oracle(dev, ops, form, case, mode, regime=None, width=8):
     """The tail of a residual unit in the epilogue of its last 1x1 convolution: y = act(BN(conv) + shortcut) (ResNet: ReLU,
     MobileNetV2: no activation); partial channel tiles (24, 64 channels) included."""
     n, cin, cout, h, w = case
@@ -668,21 +672,21 @@ def test_pwconv_i8_residual_vs_oracle(dev, ops, form, case, mode, regime=None):
     per_channel = "channel" in mode
     wt_width = 4 if "w4" in mode else 8
     rps = 1 if per_channel else cout
-    x, wt, rthr = R.apply(regime, x, "s8" in mode, wt, rps)
+    x, wt, rthr = R.apply(regime, x, "s8" in mode, wt, rps, width=width)
     if regime in ("eps_scale", "tiny", "subnormal", "huge"):
         res = R.apply(regime, res, True)[0]                  # the shortcut of such a unit carries such values as well
     codes, scales, rowsum = ops.weight_codes(T(wt, dev), rps, wt_width)
     kw, okw = {}, {}
     if mode.startswith("online"):
         stat = O.absmax_per_sample(x)
-        kw.update(in_stat=T(stat, dev), width=8, flags=0)
-        okw.update(in_max=O.batch_mean(stat), signed=False, width=8)
+        kw.update(in_stat=T(stat, dev), width=width, flags=0)
+        okw.update(in_max=O.batch_mean(stat), signed=False, width=width)
     else:
         thr = np.float32(2.3)
-        kw.update(in_thr=T(np.float32([thr]), dev), width=8, flags=ops.act_flags(signed=True))
-        okw.update(in_max=thr, signed=True, width=8)
+        kw.update(in_thr=T(np.float32([thr]), dev), width=width, flags=ops.act_flags(signed=True))
+        okw.update(in_max=thr, signed=True, width=width)
     _regime_threshold(regime, rthr, kw, okw, dev, x)
-    R.check(regime, x, okw["in_max"], okw["signed"], w=wt, rps=rps, wt_width=wt_width)
+    R.check(regime, x, okw["in_max"], okw["signed"], w=wt, rps=rps, wt_width=wt_width, width=width)
     act = "relu" if "relu" in mode else None
     sc = rng.uniform(0.3, 1.5, cout).astype(np.float32)
     sh = rng.standard_normal(cout).astype(np.float32)
@@ -732,7 +736,7 @@ PW_S2_CASES = [(2, 256, 512, 14, 14), (3, 512, 1024, 7, 7), (2, 64, 128, 9, 11),
 
 @pytest.mark.parametrize("case", PW_S2_CASES, ids=["%dx%d->%d@%dx%d" % c for c in PW_S2_CASES])
 @pytest.mark.parametrize("mode", ["online_u8_bn_relu", "offline_s8_channel_w4"])
-def test_pwconv_i8_stride2_vs_oracle(dev, ops, case, mode, regime=None):
+def test_pwconv_i8_stride2_vs_oracle(dev, ops, case, mode, regime=None, width=8):
     """The shortcut / first 1x1 convolutions of the ResNet stages: stride 2, no padding, odd and even planes.  The batch
     statistic is the one of the WHOLE input (what the reference's fake-quant in front of the convolution sees)."""
     n, cin, cout, h, w = case
@@ -744,19 +748,19 @@ def test_pwconv_i8_stride2_vs_oracle(dev, ops, case, mode, regime=None):
     per_channel = "channel" in mode
     wt_width = 4 if "w4" in mode else 8
     rps = 1 if per_channel else cout
-    x, wt, rthr = R.apply(regime, x, "s8" in mode, wt, rps)
+    x, wt, rthr = R.apply(regime, x, "s8" in mode, wt, rps, width=width)
     codes, scales, rowsum = ops.weight_codes(T(wt, dev), rps, wt_width)
     kw, okw = {}, {}
     if mode.startswith("online"):
         stat = O.absmax_per_sample(x)
-        kw.update(in_stat=T(stat, dev), width=8, flags=0)
-        okw.update(in_max=O.batch_mean(stat), signed=False, width=8)
+        kw.update(in_stat=T(stat, dev), width=width, flags=0)
+        okw.update(in_max=O.batch_mean(stat), signed=False, width=width)
     else:
         thr = np.float32(2.3)
-        kw.update(in_thr=T(np.float32([thr]), dev), width=8, flags=ops.act_flags(signed=True))
-        okw.update(in_max=thr, signed=True, width=8)
+        kw.update(in_thr=T(np.float32([thr]), dev), width=width, flags=ops.act_flags(signed=True))
+        okw.update(in_max=thr, signed=True, width=width)
     _regime_threshold(regime, rthr, kw, okw, dev, x)
-    R.check(regime, x, okw["in_max"], okw["signed"], w=wt, rps=rps, wt_width=wt_width)
+    R.check(regime, x, okw["in_max"], okw["signed"], w=wt, rps=rps, wt_width=wt_width, width=width)
     if "bn_relu" in mode:
         sc = rng.uniform(0.3, 1.5, cout).astype(np.float32)
         sh = rng.standard_normal(cout).astype(np.float32)
@@ -813,7 +817,7 @@ C3_CASES = [  # (n, cin, cout, h, w): every K/32 (2, 4, 8, 16), both wavefront a
 
 @pytest.mark.parametrize("case", C3_CASES, ids=["%dx%d->%d@%dx%d" % c for c in C3_CASES])
 @pytest.mark.parametrize("mode", ["online_u8_bn_relu", "offline_s8_channel_w4", "online_s8_bias"])
-def test_conv3x3_i8_vs_oracle(dev, ops, case, mode, regime=None):
+def test_conv3x3_i8_vs_oracle(dev, ops, case, mode, regime=None, width=8):
     n, cin, cout, h, w = case
     rng = np.random.default_rng(sum(case) + 7)
     x = (rng.standard_normal((n, cin, h, w)) * 2).astype(np.float32)
@@ -823,7 +827,7 @@ def test_conv3x3_i8_vs_oracle(dev, ops, case, mode, regime=None):
     per_channel = "channel" in mode
     wt_width = 4 if "w4" in mode else 8
     rps = 1 if per_channel else cout
-    x, wt, rthr = R.apply(regime, x, "s8" in mode, wt, rps)
+    x, wt, rthr = R.apply(regime, x, "s8" in mode, wt, rps, width=width)
     codes, scales, rowsum = ops.weight_codes_3x3(T(wt, dev), rps, wt_width)
     ocodes, oscales = O.weight_codes(wt, rps, wt_width)
     _eq(N(scales), oscales, "weight scales")
@@ -834,14 +838,14 @@ def test_conv3x3_i8_vs_oracle(dev, ops, case, mode, regime=None):
     signed = "s8" in mode
     if mode.startswith("online"):
         stat = O.absmax_per_sample(x)
-        kw.update(in_stat=T(stat, dev), width=8, flags=ops.act_flags(signed=signed))
-        okw.update(in_max=O.batch_mean(stat), signed=signed, width=8)
+        kw.update(in_stat=T(stat, dev), width=width, flags=ops.act_flags(signed=signed))
+        okw.update(in_max=O.batch_mean(stat), signed=signed, width=width)
     else:
         thr = np.float32(2.3)
-        kw.update(in_thr=T(np.float32([thr]), dev), width=8, flags=ops.act_flags(signed=True))
-        okw.update(in_max=thr, signed=True, width=8)
+        kw.update(in_thr=T(np.float32([thr]), dev), width=width, flags=ops.act_flags(signed=True))
+        okw.update(in_max=thr, signed=True, width=width)
     _regime_threshold(regime, rthr, kw, okw, dev, x)
-    R.check(regime, x, okw["in_max"], okw["signed"], w=wt, rps=rps, wt_width=wt_width, taps=9)
+    R.check(regime, x, okw["in_max"], okw["signed"], w=wt, rps=rps, wt_width=wt_width, taps=9, width=width)
     if "bn_relu" in mode:
         sc = rng.uniform(0.3, 1.5, cout).astype(np.float32)
         sh = rng.standard_normal(cout).astype(np.float32)
@@ -882,7 +886,7 @@ C3S_CASES = [c for c in C3_CASES if c[2] % 32 == 0]
 
 @pytest.mark.parametrize("case", C3S_CASES, ids=["%dx%d->%d@%dx%d" % c for c in C3S_CASES])
 @pytest.mark.parametrize("mode", ["online_u8_bn_relu_wino", "offline_s8_bias"])
-def test_conv3x3_i8_sliced_vs_oracle(dev, ops, case, mode, regime=None):
+def test_conv3x3_i8_sliced_vs_oracle(dev, ops, case, mode, regime=None, width=8):
     """fq_weight_slices + fq_conv3x3_i8_sliced (BASELINE config 5: filters under Winograd-domain quantisation are not on one
     integer grid per channel): the three int8 digit slices and their power-of-two scale against the oracle, the convolution
     bit for bit against the oracle's exact integer form, and within 2^-20 of the fp64 convolution of the very tensors the
@@ -900,7 +904,7 @@ def test_conv3x3_i8_sliced_vs_oracle(dev, ops, case, mode, regime=None):
         wt[1] = 0.0                                      # an all-zero filter
         wt[2, 0, 0, 0] = np.float32(2.0) ** -3           # its maximum a power of two
         wt[2] = np.clip(wt[2], -0.125, 0.125)
-    x, wt, rthr = R.apply(regime, x, signed, wt, 1)
+    x, wt, rthr = R.apply(regime, x, signed, wt, 1, width=width)
     codes, pscale, rowsum = ops.weight_slices_3x3(T(wt, dev))
     m, p = O.weight_slices(wt.transpose(0, 2, 3, 1).reshape(cout, -1))
     _eq(N(pscale), p, "per-channel power-of-two scale")
@@ -912,14 +916,14 @@ def test_conv3x3_i8_sliced_vs_oracle(dev, ops, case, mode, regime=None):
     kw, okw = {}, {}
     if mode.startswith("online"):
         stat = O.absmax_per_sample(x)
-        kw.update(in_stat=T(stat, dev), width=8, flags=ops.act_flags(signed=signed))
-        okw.update(in_max=O.batch_mean(stat), signed=signed, width=8)
+        kw.update(in_stat=T(stat, dev), width=width, flags=ops.act_flags(signed=signed))
+        okw.update(in_max=O.batch_mean(stat), signed=signed, width=width)
     else:
         thr = np.float32(2.3)
-        kw.update(in_thr=T(np.float32([thr]), dev), width=8, flags=ops.act_flags(signed=True))
-        okw.update(in_max=thr, signed=True, width=8)
+        kw.update(in_thr=T(np.float32([thr]), dev), width=width, flags=ops.act_flags(signed=True))
+        okw.update(in_max=thr, signed=True, width=width)
     _regime_threshold(regime, rthr, kw, okw, dev, x)
-    R.check(regime, x, okw["in_max"], okw["signed"])
+    R.check(regime, x, okw["in_max"], okw["signed"], width=width)
     if "bn_relu" in mode:
         sc = rng.uniform(0.3, 1.5, cout).astype(np.float32)
         sh = rng.standard_normal(cout).astype(np.float32)
@@ -937,7 +941,7 @@ def test_conv3x3_i8_sliced_vs_oracle(dev, ops, case, mode, regime=None):
     _eq(N(stat_out), O.absmax_per_sample(got), "statistic")
     if "bn_relu" not in mode and regime is None:
         # against the real thing: fp64 convolution of the fake-quantised activations with the filter as given
-        xq = O.ste_forward(x, O.act_scale(okw["in_max"], okw["signed"], 8), okw["in_max"],
+        xq = O.ste_forward(x, O.act_scale(okw["in_max"], okw["signed"], width), okw["in_max"],
                            -okw["in_max"] if okw["signed"] else 0.0)
         ref = torch.nn.functional.conv2d(torch.from_numpy(xq.astype(np.float64)), torch.from_numpy(wt.astype(np.float64)),
                                          padding=1).numpy()
@@ -1105,7 +1109,7 @@ DENSE_EVAL_CASES = [(128, 1024, 1000), (7, 64, 10), (70, 100, 37), (1, 512, 3), 
 
 @pytest.mark.parametrize("n,cin,units", DENSE_EVAL_CASES, ids=["%dx%d->%d" % c for c in DENSE_EVAL_CASES])
 @pytest.mark.parametrize("mode", ["online", "offline_channel_w4"])
-def test_dense_i8_eval_vs_oracle(dev, ops, n, cin, units, mode, regime=None):
+def test_dense_i8_eval_vs_oracle(dev, ops, n, cin, units, mode, regime=None, width=8):
     """fq_dense_i8_eval = the classifier on the codes + the evaluation counters of its logits in ONE launch: logits equal the
     oracle's integer form, counters equal the oracle's counters of those logits, accumulated over three calls that reuse the
     library-side workspace (it must come back zeroed).  Ties (two identical weight rows: the first index wins, whichever
@@ -1139,21 +1143,21 @@ def test_dense_i8_eval_vs_oracle(dev, ops, n, cin, units, mode, regime=None):
             x[2] = 0
             if units > 40:
                 labels[3] = 5                                         # units 5 / 6 / 37 tie for the maximum: 5 wins
-        x, _, rthr = R.apply(regime, x, False, thr=None if mode.startswith("online") else np.float32(3.1))
+        x, _, rthr = R.apply(regime, x, False, thr=None if mode.startswith("online") else np.float32(3.1), width=width)
         kw, okw = {}, {}
         stat = O.absmax_per_sample(x)
         flags = ops.act_flags(signed=False, lo_neg_max=False)
         if mode.startswith("online"):
-            kw.update(in_stat=T(stat, dev), width=8, flags=flags)
-            okw.update(in_max=O.batch_mean(stat), signed=False, width=8)
+            kw.update(in_stat=T(stat, dev), width=width, flags=flags)
+            okw.update(in_max=O.batch_mean(stat), signed=False, width=width)
         else:
             thr = np.float32(3.1)
-            kw.update(in_thr=T(np.float32([thr]), dev), in_stat=T(stat, dev), width=8, flags=flags)
-            okw.update(in_max=thr, signed=False, width=8)
+            kw.update(in_thr=T(np.float32([thr]), dev), in_stat=T(stat, dev), width=width, flags=flags)
+            okw.update(in_max=thr, signed=False, width=width)
         if regime is not None and rthr is not None:                   # an offline regime: its threshold, the statistic on the side
             kw.update(in_thr=T(np.float32([rthr]), dev), in_stat=T(stat, dev))
             okw["in_max"] = np.float32(rthr)
-        R.check(regime, x, okw["in_max"], False)
+        R.check(regime, x, okw["in_max"], False, width=width)
         cur = torch.zeros(1, device=dev)
         y = ops.dense_i8_eval(T(x, dev), codes, scales, rowsum, torch.from_numpy(labels).to(dev), counters, bias=T(bias, dev),
                               cur_out=cur, **kw)

@@ -132,14 +132,15 @@ def _hist_sinks(dev, ops, shape, bins):
     assert torch.equal(got.hist, want.hist) and int(got.neg) == int(want.neg) == 0
 
 
-def _pair(dev, ops, case, mode, regime=None, allones=("in", "mid")):
+def _pair(dev, ops, case, mode, regime=None, allones=("in", "mid"), width=8, mid_width=8):
     """`pwconv_i8_stat` + `pwdw_fused`, without and with the handed-over codes, against the two storing launches and the
     host twins (the assertions of test_pwdw_fused_equals_the_two_launches_and_the_host_twins), and the code buffer - taken
     from poisoned memory - against the host quantiser's codes, every byte."""
     n, cin, cout, h, w, stride = case
     assert ops.pwdw_supported((n, cin, h, w), cout, stride), "shape refused: %s" % (case,)
-    PWDW.test_pwdw_fused_equals_the_two_launches_and_the_host_twins(dev, ops, case, mode, regime=regime, allones=allones)
-    k = PWDW._make(case, mode, dev, ops, regime=regime, allones=allones)
+    PWDW.test_pwdw_fused_equals_the_two_launches_and_the_host_twins(dev, ops, case, mode, regime=regime, allones=allones, width=width,
+                                                                    mid_width=mid_width)
+    k = PWDW._make(case, mode, dev, ops, regime=regime, allones=allones, width=width, mid_width=mid_width)
     two = PWDW._run_pair(k, dev, ops, fused=False)
     buf = ops.torch.empty(ops.pair_codes_shape((n, cin, h, w)), dtype=torch.int8, device=dev)     # the proxy's: poisoned
     hand = PWDW._run_pair(k, dev, ops, fused=True, codes_buf=buf)
@@ -150,9 +151,9 @@ def _pair(dev, ops, case, mode, regime=None, allones=("in", "mid")):
     _eq(hand["zstat"], host["zstat"], "fused statistic on the codes vs host twins")
     flags = H.act_flags(signed=k["signed"])
     if k["offline"]:
-        codes = H.fake_quant_offline(k["x"], k["thr1"], 8, flags, want_codes=True, want_stat=False)[2]
+        codes = H.fake_quant_offline(k["x"], k["thr1"], width, flags, want_codes=True, want_stat=False)[2]
     else:
-        codes = H.fake_quant_online_prestat(k["x"], H.absmax_per_sample(k["x"]), 8, flags, want_codes=True)[2]
+        codes = H.fake_quant_online_prestat(k["x"], H.absmax_per_sample(k["x"]), width, flags, want_codes=True)[2]
     cb = 2 * ((cin + 31) // 32)
     full = np.zeros((n, cb * 16, h * w), np.int64)
     full[:, :cin] = np.asarray(codes).reshape(n, cin, h * w)

@@ -55,10 +55,11 @@ MODES = ["online_u8_bn_relu", "online_u8_bn_relu6", "online_u8_bias_nobn", "onli
          "online_u8_w4_channel"]
 
 
-def _make(case, mode, dev, ops, seed=0, regime=None, allones=("in", "mid")):
+def _make(case, mode, dev, ops, seed=0, regime=None, allones=("in", "mid"), width=8, mid_width=8):
     """`regime`: a value regime of tests/regimes.py on the data as drawn.  One with a threshold of its own makes the pair an
     offline one; `allones` names the thresholds - of the 1x1's input, of the tensor in the middle - that `allones_divisor`
-    replaces (the other keeps the driver's)."""
+    replaces (the other keeps the driver's).  `width`, `mid_width`: the activation widths of the 1x1's input and of the tensor in
+    the middle."""
     n, cin, cout, h, w, stride = case
     rng = np.random.default_rng(seed + 17 * cin + h)
     signed = "s8" in mode
@@ -68,7 +69,8 @@ def _make(case, mode, dev, ops, seed=0, regime=None, allones=("in", "mid")):
     x[0, 0, 0, 0] = np.float32(5.5)
     w1 = (rng.standard_normal((cout, cin, 1, 1)) * 0.2).astype(np.float32)
     w2 = (rng.standard_normal((cout, 1, 3, 3)) * 0.3).astype(np.float32)
-    k = dict(case=case, signed=signed, wt_width=4 if "w4" in mode else 8, rps=1 if "channel" in mode else cout)
+    k = dict(case=case, signed=signed, wt_width=4 if "w4" in mode else 8, rps=1 if "channel" in mode else cout, width=width,
+             mid_width=mid_width)
     k["act1"] = k["act2"] = "relu6" if "relu6" in mode else ("relu" if "relu" in mode or "lo_neg" in mode else None)
     if "nobn" in mode:
         k["bn1"] = k["bn2"] = None
@@ -84,19 +86,19 @@ def _make(case, mode, dev, ops, seed=0, regime=None, allones=("in", "mid")):
         k["act1"] = None              # signed values reach the depthwise layer: its clip range is [-max, max]
     k["offline"] = "offline" in mode
     k["thr1"], k["thr2"] = np.float32(4.25), np.float32(3.5)
-    x, w1, rthr = R.apply(regime, x, signed, w1, k["rps"], thr=k["thr1"] if k["offline"] else None)
+    x, w1, rthr = R.apply(regime, x, signed, w1, k["rps"], thr=k["thr1"] if k["offline"] else None, width=width)
     if regime is not None and rthr is not None:
         k["offline"] = True
         if regime != "allones_divisor" or "in" in allones:
             k["thr1"] = np.float32(rthr)
         if regime == "allones_divisor" and "mid" in allones:
-            k["thr2"] = np.float32(rthr)
+            k["thr2"] = R.allones_threshold(signed, mid_width)
     if regime == "allones_divisor":
-        assert allones and all(R.has_allones_significand(R.divisor(k[t], signed)) == (name in allones)
-                               for name, t in (("in", "thr1"), ("mid", "thr2")))
+        assert allones and all(R.has_allones_significand(R.divisor(k[t], signed, wd)) == (name in allones)
+                               for name, t, wd in (("in", "thr1", width), ("mid", "thr2", mid_width)))
     elif regime is not None:
         R.check(regime, x, k["thr1"] if k["offline"] else R.stored_threshold(x), signed, w=w1, rps=k["rps"],
-                wt_width=k["wt_width"])
+                wt_width=k["wt_width"], width=width)
     k["x"], k["w1"], k["w2"] = x, w1, w2
     return k
 
@@ -127,16 +129,16 @@ def _run_pair(k, dev, ops, fused, codes_buf=None):
         thr2 = None
         in1 = dict(in_stat=xstat)
     if not fused:
-        y, ystat = ops.pwconv_i8(x, codes, scales, rowsum, b1, width=8, flags=flags, cur_out=cur1, bn_scale=bn1[0],
+        y, ystat = ops.pwconv_i8(x, codes, scales, rowsum, b1, width=k["width"], flags=flags, cur_out=cur1, bn_scale=bn1[0],
                                  bn_shift=bn1[1], act=k["act1"], **in1)
         in2 = dict(in_thr=thr2, in_stat=ystat) if k["offline"] else dict(in_stat=ystat)
-        z, zstat = ops.dwconv3x3(y, w2, b2, stride=stride, width=8, flags=flags, cur_out=cur2, bn_scale=bn2[0],
+        z, zstat = ops.dwconv3x3(y, w2, b2, stride=stride, width=k["mid_width"], flags=flags, cur_out=cur2, bn_scale=bn2[0],
                                  bn_shift=bn2[1], act=k["act2"], **in2)
         return dict(z=N(z), zstat=N(zstat), ystat=N(ystat), cur1=N(cur1), cur2=N(cur2))
-    ystat = ops.pwconv_i8_stat(x, codes, scales, rowsum, b1, width=8, flags=flags, cur_out=cur1, bn_scale=bn1[0],
+    ystat = ops.pwconv_i8_stat(x, codes, scales, rowsum, b1, width=k["width"], flags=flags, cur_out=cur1, bn_scale=bn1[0],
                                bn_shift=bn1[1], act=k["act1"], x_codes_out=codes_buf, **in1)
-    z, zstat = ops.pwdw_fused(x, codes, scales, rowsum, w2, pw_bias=b1, width=8, flags=flags, pw_bn_scale=bn1[0],
-                              pw_bn_shift=bn1[1], pw_act=k["act1"], mid_stat=ystat, mid_thr=thr2, mid_width=8,
+    z, zstat = ops.pwdw_fused(x, codes, scales, rowsum, w2, pw_bias=b1, width=k["width"], flags=flags, pw_bn_scale=bn1[0],
+                              pw_bn_shift=bn1[1], pw_act=k["act1"], mid_stat=ystat, mid_thr=thr2, mid_width=k["mid_width"],
                               mid_flags=flags, mid_cur_out=cur2, dw_bias=b2, stride=stride, dw_bn_scale=bn2[0],
                               dw_bn_shift=bn2[1], dw_act=k["act2"], in_stat=None if k["offline"] else xstat,
                               in_thr=in1.get("in_thr"), x_codes=codes_buf)
@@ -152,23 +154,24 @@ def _host_pair(k, ops, dev):
     bn2 = (None, None) if k["bn2"] is None else k["bn2"]
     off = k["offline"]
     y, ystat = H.pwconv_i8(x, k["w1"], k["rps"], k["wt_width"], in_max=k["thr1"] if off else None, in_stat=xstat, signed=k["signed"],
-                           bias=k["b1"], bn_scale=bn1[0], bn_shift=bn1[1], act=k["act1"], want_stat=True)
+                           bias=k["b1"], bn_scale=bn1[0], bn_shift=bn1[1], act=k["act1"], want_stat=True, width=k["width"])
     w2 = N(ops.weight_fake_quant(_t(k["w2"], dev), cout, 8))
     z, zstat = H.dwconv3x3(y, w2, k["b2"], stride, in_max=k["thr2"] if off else None, in_stat=ystat, signed=k["signed"],
-                           bn_scale=bn2[0], bn_shift=bn2[1], act=k["act2"], want_stat=True)
+                           bn_scale=bn2[0], bn_shift=bn2[1], act=k["act2"], want_stat=True, width=k["mid_width"])
     return dict(z=z, zstat=zstat, ystat=ystat)
 
 
 @pytest.mark.parametrize("case", CASES, ids=["%dx%d->%d@%dx%ds%d" % c for c in CASES])
 @pytest.mark.parametrize("mode", MODES)
-def test_pwdw_fused_equals_the_two_launches_and_the_host_twins(dev, ops, case, mode, regime=None, allones=("in", "mid")):
+def test_pwdw_fused_equals_the_two_launches_and_the_host_twins(dev, ops, case, mode, regime=None, allones=("in", "mid"), width=8,
+                                                               mid_width=8):
     n, cin, cout, h, w, stride = case
     if not ops.pwdw_supported((n, cin, h, w), cout, stride):
         assert (h, w) == (8, 8), "an instantiated shape is refused: %s" % (case,)
         with pytest.raises(Exception):
             _run_pair(_make(case, mode, dev, ops), dev, ops, fused=True)
         return
-    k = _make(case, mode, dev, ops, regime=regime, allones=allones)
+    k = _make(case, mode, dev, ops, regime=regime, allones=allones, width=width, mid_width=mid_width)
     two = _run_pair(k, dev, ops, fused=False)
     one = _run_pair(k, dev, ops, fused=True)
     _eq(one["ystat"], two["ystat"], "statistic-only pass vs the storing pointwise kernel")

@@ -53,8 +53,9 @@ CASES = [
 MODES = ["online_u8_relu", "online_s8_none", "offline_u8_relu", "mixed_relu6_bias"]
 
 
-def _make(case, mode, regime=None):
-    """`regime`: a value regime of tests/regimes.py, on both operands and both filter banks as drawn."""
+def _make(case, mode, regime=None, width=8, width2=8):
+    """`regime`: a value regime of tests/regimes.py, on both operands and both filter banks as drawn.
+    `width`, `width2`: the activation widths of the closing convolution's and of the shortcut convolution's input."""
     n, cin, cin2, cout, h, w = case
     rng = np.random.default_rng(cin + cin2 + h)
     signed = "s8" in mode
@@ -62,7 +63,7 @@ def _make(case, mode, regime=None):
     x2 = rng.standard_normal((n, cin2, h, w)).astype(np.float32) * np.float32(2.1)
     if not signed:
         x, x2 = np.maximum(x, 0), np.maximum(x2, 0)
-    k = dict(case=case, signed=signed, x=x, x2=x2, mode=mode)
+    k = dict(case=case, signed=signed, x=x, x2=x2, mode=mode, width=width, width2=width2)
     k["w"] = (rng.standard_normal((cout, cin)) * 0.1).astype(np.float32)
     k["w2"] = (rng.standard_normal((cout, cin2)) * 0.05).astype(np.float32)
     k["bn"] = ((0.5 + rng.random(cout)).astype(np.float32) * np.where(rng.random(cout) < 0.1, -1, 1).astype(np.float32),
@@ -72,12 +73,13 @@ def _make(case, mode, regime=None):
     k["act"] = "relu6" if "relu6" in mode else ("relu" if "relu" in mode else None)
     k["off1"], k["off2"] = "offline" in mode, "offline" in mode or "mixed" in mode
     k["thr1"], k["thr2"] = np.float32(3.0), np.float32(4.5)
-    for a, wname, thr, off in (("x", "w", "thr1", "off1"), ("x2", "w2", "thr2", "off2")):
-        k[a], k[wname], rthr = R.apply(regime, k[a], signed, k[wname], 1, thr=k[thr] if k[off] else None)
+    for a, wname, thr, off, wd in (("x", "w", "thr1", "off1", width), ("x2", "w2", "thr2", "off2", width2)):
+        k[a], k[wname], rthr = R.apply(regime, k[a], signed, k[wname], 1, thr=k[thr] if k[off] else None, width=wd)
         if regime is not None and rthr is not None:
             k[thr], k[off] = np.float32(rthr), True
         if regime is not None:
-            R.check(regime, k[a], k[thr] if k[off] else R.O.batch_mean(R.O.absmax_per_sample(k[a])), signed, w=k[wname], rps=1)
+            R.check(regime, k[a], k[thr] if k[off] else R.O.batch_mean(R.O.absmax_per_sample(k[a])), signed, w=k[wname], rps=1,
+                    width=wd)
     return k
 
 
@@ -94,22 +96,22 @@ def _run(k, dev, ops, fused):
     p2 = dict(in_thr=torch.full((1,), float(k["thr2"]), device=dev), in_stat=st2) if offline2 else dict(in_stat=st2)
     bn, bn2 = (_t(k["bn"][0], dev), _t(k["bn"][1], dev)), (_t(k["bn2"][0], dev), _t(k["bn2"][1], dev))
     if not fused:
-        s, _ = ops.pwconv_i8(x2, *c2, None, width=8, flags=flags, cur_out=cur2, bn_scale=bn2[0], bn_shift=bn2[1], act=None,
+        s, _ = ops.pwconv_i8(x2, *c2, None, width=k["width2"], flags=flags, cur_out=cur2, bn_scale=bn2[0], bn_shift=bn2[1], act=None,
                              want_stat=False, form="split", **p2)
-        y, stat = ops.pwconv_i8(x, *c1, _t(k["bias"], dev), width=8, flags=flags, cur_out=cur1, bn_scale=bn[0], bn_shift=bn[1],
+        y, stat = ops.pwconv_i8(x, *c1, _t(k["bias"], dev), width=k["width"], flags=flags, cur_out=cur1, bn_scale=bn[0], bn_shift=bn[1],
                                 act=k["act"], residual=s, **p1)
     else:
-        y, stat = ops.pwconv_i8_shortcut(x, *c1, _t(k["bias"], dev), width=8, flags=flags, cur_out=cur1, bn_scale=bn[0],
+        y, stat = ops.pwconv_i8_shortcut(x, *c1, _t(k["bias"], dev), width=k["width"], flags=flags, cur_out=cur1, bn_scale=bn[0],
                                          bn_shift=bn[1], act=k["act"], x2=x2, wcodes2=c2[0], wscale2=c2[1], wsum2=c2[2],
-                                         width2=8, flags2=flags, cur_out2=cur2, bn_scale2=bn2[0], bn_shift2=bn2[1],
+                                         width2=k["width2"], flags2=flags, cur_out2=cur2, bn_scale2=bn2[0], bn_shift2=bn2[1],
                                          in_stat2=p2.get("in_stat"), in_thr2=p2.get("in_thr"), **p1)
     return N(y), N(stat), N(cur1), N(cur2)
 
 
 @pytest.mark.parametrize("case", CASES, ids=["%dx%d+%d->%d@%dx%d" % c for c in CASES])
 @pytest.mark.parametrize("mode", MODES)
-def test_folded_shortcut_equals_the_two_launches_and_the_host_twin(dev, ops, case, mode, regime=None):
-    k = _make(case, mode, regime)
+def test_folded_shortcut_equals_the_two_launches_and_the_host_twin(dev, ops, case, mode, regime=None, width=8, width2=8):
+    k = _make(case, mode, regime, width=width, width2=width2)
     got = _run(k, dev, ops, True)
     want = _run(k, dev, ops, False)
     for a, b, what in zip(got, want, ("output", "statistic", "current_input_max of the closing convolution",
@@ -119,10 +121,11 @@ def test_folded_shortcut_equals_the_two_launches_and_the_host_twin(dev, ops, cas
     n, cin, cin2, cout, h, w = case
     off1, off2 = k["off1"], k["off2"]
     s = H.pwconv_i8(k["x2"], k["w2"].reshape(cout, cin2, 1, 1), 1, 8, in_max=k["thr2"] if off2 else None,
-                    in_stat=H.absmax_per_sample(k["x2"]), signed=k["signed"], bn_scale=k["bn2"][0], bn_shift=k["bn2"][1], act=None)
+                    in_stat=H.absmax_per_sample(k["x2"]), signed=k["signed"], bn_scale=k["bn2"][0], bn_shift=k["bn2"][1], act=None,
+                    width=width2)
     hy, hstat = H.pwconv_i8(k["x"], k["w"].reshape(cout, cin, 1, 1), 1, 8, in_max=k["thr1"] if off1 else None,
                             in_stat=H.absmax_per_sample(k["x"]), signed=k["signed"], bias=k["bias"], bn_scale=k["bn"][0],
-                            bn_shift=k["bn"][1], act=k["act"], want_stat=True, residual=s)
+                            bn_shift=k["bn"][1], act=k["act"], want_stat=True, residual=s, width=width)
     _eq(got[0], hy, "host twins: output")
     _eq(got[1], hstat, "host twins: statistic")
 

@@ -57,8 +57,9 @@ CASES = [
 MODES = ["online_u8_bn_res_relu", "online_s8_bn_res_none", "offline_u8_bn_res_relu", "online_u8_bias_nores_relu6", "online_u8_w4_layer"]
 
 
-def _make(case, mode, seed=0, regime=None):
-    """`regime`: a value regime of tests/regimes.py on the data as drawn (one with a threshold of its own: an offline launch)."""
+def _make(case, mode, seed=0, regime=None, width=8):
+    """`regime`: a value regime of tests/regimes.py on the data as drawn (one with a threshold of its own: an offline launch).
+    `width`: the activation width of the launch and of the host twin."""
     n, cin, cout, h, w = case
     rng = np.random.default_rng(seed + 13 * cin + h)
     signed = "s8" in mode
@@ -66,7 +67,7 @@ def _make(case, mode, seed=0, regime=None):
     if not signed:
         x = np.maximum(x, 0)
     x[0, 0, 0, 0] = np.float32(4.75)
-    k = dict(case=case, signed=signed, x=x, offline="offline" in mode)
+    k = dict(case=case, signed=signed, x=x, offline="offline" in mode, width=width)
     k["w"] = (rng.standard_normal((cout, cin)) * 0.2).astype(np.float32)
     k["wt_width"], k["rps"] = (4, cout) if "w4" in mode else (8, 1)
     k["res"] = None if "nores" in mode else (rng.standard_normal((n, cout, h, w)) * 2).astype(np.float32)
@@ -81,12 +82,13 @@ def _make(case, mode, seed=0, regime=None):
         k["bias"] = None
     k["act"] = "relu6" if "relu6" in mode else ("relu" if "relu" in mode else None)
     k["thr"] = np.float32(3.25)
-    k["x"], k["w"], rthr = R.apply(regime, k["x"], signed, k["w"], k["rps"], thr=k["thr"] if k["offline"] else None)
+    k["x"], k["w"], rthr = R.apply(regime, k["x"], signed, k["w"], k["rps"], thr=k["thr"] if k["offline"] else None,
+                                   width=width)
     if regime is not None and rthr is not None:
         k["offline"], k["thr"] = True, np.float32(rthr)
     if regime is not None:
         R.check(regime, k["x"], k["thr"] if k["offline"] else R.O.batch_mean(R.O.absmax_per_sample(k["x"])), signed, w=k["w"],
-                rps=k["rps"], wt_width=k["wt_width"])
+                rps=k["rps"], wt_width=k["wt_width"], width=width)
     return k
 
 
@@ -98,7 +100,7 @@ def _run(k, dev, ops, sub):
     cur = torch.zeros(1, device=dev)
     xstat = ops.absmax_per_sample(x)
     plan = dict(in_thr=torch.full((1,), float(k["thr"]), device=dev), in_stat=xstat) if k["offline"] else dict(in_stat=xstat)
-    y, stat = ops.pwconv_i8(x, codes, scales, rowsum, _t(k["bias"], dev), width=8, flags=flags, cur_out=cur,
+    y, stat = ops.pwconv_i8(x, codes, scales, rowsum, _t(k["bias"], dev), width=k["width"], flags=flags, cur_out=cur,
                             bn_scale=_t(k["bn"][0], dev), bn_shift=_t(k["bn"][1], dev), act=k["act"], residual=_t(k["res"], dev),
                             subsample=sub, **plan)
     return N(y), N(stat), N(cur)
@@ -106,8 +108,8 @@ def _run(k, dev, ops, sub):
 
 @pytest.mark.parametrize("case", CASES, ids=["%dx%d->%d@%dx%d" % c for c in CASES])
 @pytest.mark.parametrize("mode", MODES)
-def test_sub2_stores_the_even_pixels_of_the_whole_launch_and_keeps_its_statistic(dev, ops, case, mode, regime=None):
-    k = _make(case, mode, regime=regime)
+def test_sub2_stores_the_even_pixels_of_the_whole_launch_and_keeps_its_statistic(dev, ops, case, mode, regime=None, width=8):
+    k = _make(case, mode, regime=regime, width=width)
     n, cin, cout, h, w = case
     y, stat, cur = _run(k, dev, ops, True)
     yf, statf, curf = _run(k, dev, ops, False)
@@ -121,7 +123,7 @@ def test_sub2_stores_the_even_pixels_of_the_whole_launch_and_keeps_its_statistic
     from oracle import host as H
     hy, hstat = H.pwconv_i8(k["x"], k["w"].reshape(cout, cin, 1, 1), k["rps"], k["wt_width"], in_max=k["thr"] if k["offline"] else None,
                             in_stat=H.absmax_per_sample(k["x"]), signed=k["signed"], bias=k["bias"], bn_scale=k["bn"][0],
-                            bn_shift=k["bn"][1], act=k["act"], want_stat=True, residual=k["res"], subsample=True)
+                            bn_shift=k["bn"][1], act=k["act"], want_stat=True, residual=k["res"], subsample=True, width=k["width"])
     _eq(y, hy, "host twin: stored pixels")
     _eq(stat, hstat, "host twin: statistic")
 
@@ -221,7 +223,7 @@ DUAL_CASES = [(3, 64, 256, 56, 56), (3, 128, 512, 28, 28), (5, 256, 1024, 14, 14
 
 
 @pytest.mark.parametrize("case", DUAL_CASES, ids=["%dx%d->%d@%dx%d" % c for c in DUAL_CASES])
-def test_dual_sub2_stores_both_outputs_subsampled(dev, ops, case, regime=None):
+def test_dual_sub2_stores_both_outputs_subsampled(dev, ops, case, regime=None, width=8, out_width=8):
     """fq_pwconv_i8_c16_dual_sub2: codes in, residual added; the fp32 output and its code copy hold y[:, :, ::2, ::2] of what
     fq_pwconv_i8_c16_dual stores - same statistic - and agree with the host twin."""
     from oracle import fq_oracle as O
@@ -233,22 +235,22 @@ def test_dual_sub2_stores_both_outputs_subsampled(dev, ops, case, regime=None):
     sh = rng.standard_normal(cout).astype(np.float32)
     res = (rng.standard_normal((n, cout, h, w)) * 2).astype(np.float32)
     res[n - 1, 3, h - 1 - (h % 2), 1] = np.float32(88.0)            # a maximum on an odd column
-    x, wt, thr = R.stored(regime, x, False, wt, 1, np.float32(2.3))
-    R.check(regime, x, thr, False, w=wt, rps=1)
+    x, wt, thr = R.stored(regime, x, False, wt, 1, np.float32(2.3), width=width)
+    R.check(regime, x, thr, False, w=wt, rps=1, width=width)
     codes, scales, rowsum = ops.weight_codes(_t(wt, dev), 1, 8)
     thr2 = np.float32(3.1)
     thr_t = _t(np.float32([thr]), dev)
     stat_in = _t(O.absmax_per_sample(x), dev)
-    cx = O.ste_codes(x, O.act_scale(thr, False, 8), thr, np.float32(0))
-    xc = ops.Codes16(_t(O.to_c16(cx.astype(np.int64), 128), dev), x.shape, thr_t, 8, 0)
+    cx = O.ste_codes(x, O.act_scale(thr, False, width), thr, np.float32(0))
+    xc = ops.Codes16(_t(O.to_c16(cx.astype(np.int64), 128), dev), x.shape, thr_t, width, 0)
     cur_a, cur_b = torch.zeros(1, device=dev), torch.zeros(1, device=dev)
-    kw = dict(in_thr=thr_t, width=8, flags=0, bn_scale=_t(sc, dev), bn_shift=_t(sh, dev), act="relu", in_stat=stat_in,
+    kw = dict(in_thr=thr_t, width=width, flags=0, bn_scale=_t(sc, dev), bn_shift=_t(sh, dev), act="relu", in_stat=stat_in,
               residual=_t(res, dev))
     if regime in R.OUTPUT:
         y = N(ops.pwconv_i8(xc, codes, scales, rowsum, **kw)[0])
-        thr2 = R.output_threshold(regime, y, False, thr2)
-        R.check_output(regime, y, thr2, False)
-    side_kw = dict(thr=_t(np.float32([thr2]), dev), width=8, flags=0)
+        thr2 = R.output_threshold(regime, y, False, thr2, width=out_width)
+        R.check_output(regime, y, thr2, False, width=out_width)
+    side_kw = dict(thr=_t(np.float32([thr2]), dev), width=out_width, flags=0)
     want, want_stat, want_side = ops.pwconv_i8(xc, codes, scales, rowsum, cur_out=cur_a, side_codes=side_kw, **kw)
     got, got_stat, side = ops.pwconv_i8(xc, codes, scales, rowsum, cur_out=cur_b, side_codes=side_kw, subsample=True, **kw)
     hs, ws = (h + 1) // 2, (w + 1) // 2

@@ -34,6 +34,11 @@ CASES = [
     ("resnet34_v1-channel-online", "resnet34_v1", dict(quant_type="channel"), 0, 4, dict()),
     ("resnet101_v1-channel-online", "resnet101_v1", dict(quant_type="channel"), 0, 4, R50),
     ("resnet50_v1-last_gamma-online", "resnet50_v1", dict(quant_type="channel", last_gamma=True), 0, 4, R50),
+    # four bits on both sides (the reference's published c10_r56_uint4_int4 configurations): the gate is measured against the
+    # fp32 composition at that width and follows it by itself
+    ("mobilenet1.0-w4a4-online", "mobilenet1.0", dict(wt=4, in_w=4), 0, 8, dict(pairs=2, gap=1)),
+    ("mobilenetv2_1.0-w4a4-offline", "mobilenetv2_1.0", dict(quant_type="channel", wt=4, in_w=4), 2, 8, dict(codes=1)),
+    ("resnet18_v1-channel-w4a4-offline", "resnet18_v1", dict(quant_type="channel", wt=4, in_w=4), 1, 4, dict(codes=1)),
 ]
 
 

@@ -35,7 +35,8 @@ pytestmark = pytest.mark.gpu
 _eq, N, T = P._eq, P.N, P.T
 
 IN = R.INPUT
-ONLINE = ("zero", "zero_sample", "eps_scale", "tiny", "subnormal", "huge")     # regimes without a threshold of their own
+# regimes without a threshold of their own - and `boundaries`, whose planted per-sample maxima make the online statistic its threshold
+ONLINE = ("zero", "zero_sample", "eps_scale", "tiny", "subnormal", "huge", "boundaries")
 NO_QUANTISER = ("zero", "zero_sample", "tiny", "subnormal", "huge")             # a layer that takes fp32 as it is
 OUT = R.OUTPUT
 
@@ -60,39 +61,39 @@ def took_fast_path(dev, d):
     return int(N(took)[0])
 
 
-def _pair(dev, ops, case, mode, regime, allones=("in", "mid")):
+def _pair(dev, ops, case, mode, regime, allones=("in", "mid"), width=8, mid_width=8):
     """`pwconv_i8_stat` + `pwdw_fused` without and with the code buffer (the driver of the poisoned runs).  The fused kernel
     reads at most 256 input channels: 256 * 255 * 127 < 2^24, no shape of it reaches the large sums.  Under `allones_divisor`
     the launch takes the general body for exactly one known cause per named threshold: that divisor - and no other - is one
     `make_fast_quot` declines, both clip ranges start at 0."""
-    POISON._pair(dev, ops, case, mode, regime=regime, allones=allones)
+    POISON._pair(dev, ops, case, mode, regime=regime, allones=allones, width=width, mid_width=mid_width)
     if regime == "allones_divisor":
-        k = PWDW._make(case, mode, dev, ops, regime=regime, allones=allones)
+        k = PWDW._make(case, mode, dev, ops, regime=regime, allones=allones, width=width, mid_width=mid_width)
         assert not k["signed"] and k["offline"]
-        for name, thr in (("in", k["thr1"]), ("mid", k["thr2"])):
-            d = R.divisor(thr, False)
+        for name, thr, wd in (("in", k["thr1"], width), ("mid", k["thr2"], mid_width)):
+            d = R.divisor(thr, False, wd)
             assert R.has_allones_significand(d) == (name in allones)
             assert took_fast_path(dev, d) == (0 if name in allones else 1), "threshold %r of %s" % (thr, name)
 
 
-def _front(dev, ops, case, mode, regime):
+def _front(dev, ops, case, mode, regime, front_width=8, width=8):
     """The folded front layer (tests/test_gpu_front_dw.py): both ways on the regime's data, every byte of both code buffers."""
     n, cin, cout, h, w = case
     assert ops.pwconv_front_supported((n, cin, h, w), cout), "shape refused: %s" % (case,)
-    k = FRONT._make(case, mode, regime=regime)
+    k = FRONT._make(case, mode, regime=regime, front_width=front_width, width=width)
     want = FRONT._two_launches(k, dev, ops)
     got = FRONT._front(k, dev, ops)
     FRONT._compare(got, want, k, regime=regime)
     _eq(got["ycodes"], FRONT._input_codes(k), "codes of the depthwise input vs the host oracle's quantiser")
     if regime == "allones_divisor":
-        assert took_fast_path(dev, R.divisor(k["thrB"], k["s_pw"])) == 0
+        assert took_fast_path(dev, R.divisor(k["thrB"], k["s_pw"], width)) == 0
 
 
-def _chain(dev, ops, monkeypatch, case, signed, regime):
+def _chain(dev, ops, monkeypatch, case, signed, regime, width=8, mid_width=8):
     """The fused launch in statistic mode + the statistic pass that recomputes the depthwise layer (tests/test_gpu_pair_chain.py)."""
     n, cin, cmid, cout, h, w = case
     assert ops.pwdw_chain_supported((n, cin, h, w), cmid) and ops.pwconv_front_supported((n, cmid, h, w), cout), case
-    k = CHAIN._make(case, signed, regime=regime)
+    k = CHAIN._make(case, signed, regime=regime, width=width, mid_width=mid_width)
     CHAIN._set_bands(monkeypatch, case)
     want, host = CHAIN._stored(k, dev, ops), CHAIN._host_mid_codes(k, ops, dev)
     got = CHAIN._chained(k, dev, ops)

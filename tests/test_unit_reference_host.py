@@ -15,7 +15,8 @@ MOBILENETS = ["mobilenet1.0", "mobilenet0.75", "mobilenet0.5", "mobilenet0.25",
 RESNETS = ["resnet18_v1", "resnet34_v1", "resnet50_v1"]
 SMALL = ["cifar_resnet20_v1", "vgg11_bn"]
 CASES = [(m, q, False) for m in MOBILENETS + RESNETS + SMALL for q in ("layer", "channel")] + \
-    [("mobilenet1.0", "group", False), ("resnet50_v1", "channel", True), ("resnet50_v1", "channel-F43", False)]
+    [("mobilenet1.0", "group", False), ("resnet50_v1", "channel", True), ("resnet50_v1", "channel-F43", False)] + \
+    [("mobilenet1.0", "layer-w4a4", False), ("mobilenetv2_1.0", "channel-w4a4", False), ("resnet18_v1", "channel-w4a4", False)]
 
 
 def _size(model):
@@ -40,8 +41,10 @@ def test_every_fused_unit_is_the_reference_composition_of_its_raw_parameters(pla
     fuse = plain_forms
     hw = _size(model)
     with oracle_ops():
-        quant_type, _, wino = quant_type.partition("-")
-        net = U.build(model, 10, quant_type=quant_type, wino=wino or "none", rand_bn=3, last_gamma=last_gamma)
+        quant_type, _, variant = quant_type.partition("-")
+        widths = dict(wt=4, in_w=4) if variant == "w4a4" else dict()
+        net = U.build(model, 10, quant_type=quant_type, wino="none" if widths else variant or "none", rand_bn=3, last_gamma=last_gamma,
+                      **widths)
         X = mx.nd.array(np.random.default_rng(5).standard_normal((2, 3, hw, hw)).astype(np.float32))
         if model.startswith("vgg"):
             net(X)                                  # (the first Dense layer's input width follows from the image size)

@@ -51,6 +51,16 @@ def test_the_threshold_constants_are_the_scanned_ones():
         d = R.divisor(R.allones_threshold(signed, width), signed, width)
         assert int(d.view(np.uint32)) == 0x3CFFFFFF and R.has_allones_significand(d)
     assert not R.has_allones_significand(R.divisor(np.float32(2.3), True))
+    # `boundaries` stores 2.75: the divisor's significand exceeds 4 / 3 for every level count, so an input just below 0.5 * d has
+    # the quotient pred(0.5) - the only one on which trunc(Q + 0.5f) is not roundf(Q); 2.5 gives that with 3, 7 and 15 levels only
+    assert R.BOUNDARY_THRESHOLD == np.float32(2.75)
+    for signed in (False, True):
+        for width in range(2, 9):
+            assert R.reaches_half_pred(R.boundary_table(signed, width), R.BOUNDARY_THRESHOLD, signed, width), (signed, width)
+            d = int(R.divisor(R.BOUNDARY_THRESHOLD, signed, width).view(np.uint32)) & 0x7FFFFF
+            assert d > 0x2AAAAA                                     # significand > 4 / 3
+    row = np.nextafter(np.float32(0.5) * R.divisor(np.float32(2.5), False), np.float32(0))
+    assert not R.reaches_half_pred(row, np.float32(2.5), False)
 
 
 @pytest.mark.parametrize("signed", [False, True], ids=["u8", "s8"])
