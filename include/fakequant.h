@@ -448,6 +448,24 @@ int fq_pwconv_i8_stat(const float* x, const int8_t* wcodes, const float* wscale,
                       const float* front_bn_scale, const float* front_bn_shift, int front_act, const float* front_in_stat,
                       const float* front_in_thr, int front_width, unsigned front_flags, int64_t front_h, int64_t front_wdt);
 int fq_pwdw_fused_supported(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w, int stride, int stat_mode);
+/* The STORING 1x1 with a front layer (libraries from fq_version() 103 on): fq_pwconv_i8_stat(front_codes != NULL)'s contract with
+ * y and the layer's stat_out as results instead of the extreme sums.  front_codes ([n][cin][h * w] int8, what the stride-1
+ * fq_dwconv3x3 in front kept as a statistic pass) are dequantised with the front layer's input threshold (front_in_stat /
+ * front_in_thr, front_width, front_flags), fq_dwconv3x3's chain and epilogue run on them (front_w, front_bias, front_bn_scale /
+ * front_bn_shift, front_act), the values are quantised with the threshold of the depthwise OUTPUT (in_stat / in_thr, in_width,
+ * in_flags), the exact int32 1x1 and bias / BatchNorm / activation follow, and y (n, cout, h, w) fp32 and stat_out[n] <-
+ * max|y[n]| are stored; out_current_max <- the 1x1 block's `current_input_max`.  x is never dereferenced and may be NULL: the
+ * depthwise output never exists in memory.  Every value is bit for bit what fq_dwconv3x3 followed by fq_pwconv_i8 produce.  act may carry
+ * FQ_STAT_PREZEROED.  Shapes: fq_pwconv_i8_front_supported - cin == cout == 256, w % 4 == 0 and at most 256; any other shape,
+ * stride or quantiser (widths above 8, FQ_ACT_NO_ABS / FQ_ACT_NO_EPS) is refused with an error and nothing is launched.           */
+int fq_pwconv_i8_front_supported(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w);
+int fq_pwconv_i8_front(const float* x, const int8_t* wcodes, const float* wscale, const int32_t* wsum, const float* bias, float* y,
+                       int64_t n, int64_t cin, int64_t cin_pad, int64_t cout_pad, int64_t cout, int64_t h, int64_t w, const float* in_stat,
+                       const float* in_thr, int in_width, unsigned in_flags, float* out_current_max, const float* bn_scale,
+                       const float* bn_shift, int act, float* stat_out, fqStream_t stream, const void* front_codes,
+                       const float* front_w, const float* front_bias, const float* front_bn_scale, const float* front_bn_shift,
+                       int front_act, const float* front_in_stat, const float* front_in_thr, int front_width,
+                       unsigned front_flags);
 /* Test hook: out[i] <- the fp32 quotient c[i] / d[0] as the two kernels above compute it (the fp32 correction step of
  * csrc/fq_common.h: fast_quot, or the fp64-reciprocal form when d[0] does not qualify; took_fast_path[0] says which) - must
  * equal the IEEE fp32 division bit for bit wherever a code depends on it (tests/test_gpu_pwdw.py).                         */

@@ -215,6 +215,29 @@ int fq_qconv2d_forward_host(const float* x, const float* w, const void* wbuf, co
 int fq_unfused_chain_host(const float* x, float* y, int64_t n, int64_t inner, int width, unsigned flags,
                           float* out_current_max, float* tmp, fqStream_t stream);
 
+/* The storing 1x1 with a front layer (fq_pwconv_i8_front): on the host the tensor between the layers exists, so the twin IS the
+ * two storing twins back to back - fq_dwconv3x3_host (stride 1) on front_x, the depthwise layer's fp32 INPUT (the host keeps no
+ * codes), into z (n * cin * h * w floats of the caller's), then fq_pwconv_i8_host on z with front_stat_out[n] = max|z[n]| as its
+ * online statistic when in_stat is NULL.  That composition is the whole contract of the device entry point, which is why the two
+ * are DEFINED here (plain, not inline: the one unit that includes this header, oracle/fq_host.cpp, exports them).              */
+int fq_pwconv_i8_front_supported_host(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w) {
+  return n > 0 && h >= 1 && w >= 4 && w % 4 == 0 && w / 4 <= 64 && cin == 256 && cout == 256 ? 1 : 0;
+}
+int fq_pwconv_i8_front_host(const float* front_x, float* z, float* front_stat_out, const int8_t* wcodes, const float* wscale,
+                            const int32_t* wsum, const float* bias, float* y, int64_t n, int64_t cin, int64_t cin_pad,
+                            int64_t cout, int64_t h, int64_t w, const float* in_stat, const float* in_thr, int in_width,
+                            unsigned in_flags, float* out_current_max, const float* bn_scale, const float* bn_shift, int act,
+                            float* stat_out, const float* front_w, const float* front_bias, const float* front_bn_scale,
+                            const float* front_bn_shift, int front_act, const float* front_in_stat, const float* front_in_thr,
+                            int front_width, unsigned front_flags, float* front_current_max, fqStream_t stream) {
+  int rc = fq_dwconv3x3_host(front_x, front_w, front_bias, z, n, cin, h, w, 1, front_in_stat, front_in_thr, front_width,
+                             front_flags, front_current_max, front_bn_scale, front_bn_shift, front_act, front_stat_out, stream);
+  if (rc != 0) return rc;
+  return fq_pwconv_i8_host(z, wcodes, wscale, wsum, bias, y, n, cin, cin_pad, cout, h * w,
+                           in_stat != 0 || in_thr != 0 ? in_stat : front_stat_out, in_thr, in_width, in_flags, out_current_max,
+                           bn_scale, bn_shift, act, stat_out, 0, stream);
+}
+
 #ifdef __cplusplus
 }
 #endif

@@ -71,6 +71,12 @@ EXPORTS = {
     "fq_pwconv_i8_stat": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _int, _uint, _vp, _vp,
                                  _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _int, _uint, _i64, _i64]),
     "fq_pwdw_fused_supported": (_int, [_i64, _i64, _i64, _i64, _i64, _int, _int]),      # ..., stride, stat_mode
+    "fq_pwconv_i8_front_supported": (_int, [_i64, _i64, _i64, _i64, _i64]),      # n, cin, cout, h, w
+    # x, wcodes, wscale, wsum, bias, y, n, cin, cin_pad, cout_pad, cout, h, w, in_stat, in_thr, in_width, in_flags, cur, bn_scale,
+    # bn_shift, act, stat_out, stream, front_codes, front_w, front_bias, front_bn_scale, front_bn_shift, front_act, front_in_stat,
+    # front_in_thr, front_width, front_flags
+    "fq_pwconv_i8_front": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _int, _uint,
+                                  _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _int, _uint]),
     # x, wcodes, wscale, wsum, pw_bias, n, cin, cin_pad, cout_pad, cout, h, w, in_stat, in_thr, in_width, in_flags, pw_bn_scale,
     # pw_bn_shift, pw_act, mid_stat, mid_thr, mid_width, mid_flags, mid_cur, dw_w, dw_bias, dw_stride, dw_bn_scale, dw_bn_shift,
     # dw_act, y, stat_out, x_codes, stream, mid_codes_out
@@ -139,6 +145,9 @@ EXPORTS = {
                                   _int, _int, _f32, _f32, _vp, _int, _vp, _vp, _vp, _vp, _int, _vp]),
 }
 
+# entry points that came after fq_version() 102, with the version that has them: an older library may lack these, and only these
+SINCE = {"fq_pwconv_i8_front_supported": 103, "fq_pwconv_i8_front": 103}
+
 FQ_ACT_SIGNED, FQ_ACT_LO_NEG_MAX, FQ_ACT_NO_ABS, FQ_ACT_NO_EPS = 1, 2, 4, 8
 FQ_CODES_INT8, FQ_CODES_UINT8, FQ_CODES_RANGE, FQ_CODES_SCALE = 0, 1, 2, 3
 
@@ -174,7 +183,11 @@ def load(path=None):
     except OSError as e:            # pragma: no cover
         return _Missing(str(e))
     for name, (restype, argtypes) in EXPORTS.items():
-        fn = getattr(lib, name)
+        fn = getattr(lib, name, None)
+        if fn is None and lib.fq_version() < SINCE.get(name, 0):
+            continue            # (an older build loaded through FQ_LIB_PATH for an A/B: callers ask fq_version() before they use it)
+        if fn is None:
+            raise AttributeError("%s (fq_version() %d) does not export %s: rebuild it" % (path, lib.fq_version(), name))
         fn.restype = restype
         fn.argtypes = argtypes
     return lib

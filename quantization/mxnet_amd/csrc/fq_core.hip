@@ -92,7 +92,7 @@ using namespace fqi;
 extern "C" {
 
 const char* fq_last_error(void) { return g_err; }
-int fq_version(void) { return 102; }
+int fq_version(void) { return 103; }
 // sha1 of the sources this library was built from (csrc/build.py: source_id); "FQ_BUILD_ID=<40 hex>" is also what
 // build.py looks for in the file's bytes to decide whether a built library belongs to the tree it sits in
 #ifndef FQ_BUILD_ID

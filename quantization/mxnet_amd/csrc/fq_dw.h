@@ -32,6 +32,7 @@ struct DwCall {
 // them in this order, and the tiles take every shape.
 bool dw_flat_applies(const DwCall& d, int form), dw_planes_applies(const DwCall& d, int form);      // K2p fq_dw_flat.hip, K2o fq_dw_planes.hip
 bool dw_cols4_applies(const DwCall& d, int form), dw_cols_applies(const DwCall& d, int form);       // K2e, K2d fq_dw_cols.hip
+bool dw_flat_stat_applies(const DwCall& d);                                                        // ... K2p as a statistic pass (y == NULL)
 int dw_run_flat(const DwCall& d), dw_run_planes(const DwCall& d), dw_run_cols4(const DwCall& d), dw_run_cols(const DwCall& d);
 int dw_run_tiles(const DwCall& d);                                                                  // K2c fq_dw_tiles.hip
 // fq_dwconv.hip: the depthwise layer of nn.Conv2D(quantized=True) (fq_qconv.hip)

@@ -123,6 +123,8 @@ __global__ __launch_bounds__(kBlock) void dwconv3x3_flat_kernel(
     const unsigned left = base < planes ? planes - base : 0u;
     const unsigned np = left < (unsigned)P ? left : (unsigned)P;
     const unsigned lim_out = TAIL_OK ? np * (OUT / 4) : (np == (unsigned)P ? (unsigned)NFO : 0u);
+    // (phases A and B of the PAIR shape have a TWIN, word for word: dwconv3x3_flat_stat_kernel below, the statistic pass - a change
+    // to the quantiser, the tap chain or the epilogue here is a change there; tests/test_gpu_front_store.py compares the two)
     // ---- A: quantise in flat order, stage ---------------------------------------------------------------------------
 #pragma unroll
     for (int i = 0; i < NLI; ++i) {
@@ -230,6 +232,136 @@ __global__ __launch_bounds__(kBlock) void dwconv3x3_flat_kernel(
   PW_STAMP(5);
 }
 
+// The STATISTIC PASS of the form (stride 1, quantised input, even W), as the four-columns form has one (fq_dw_cols.hip: NOSTORE):
+// every output is computed and joins the maximum, none is stored - phase B leaves the tile alone and there is no phase C.  `y` is
+// no output: when not null it is the int8 buffer [n][c][h * w] that receives the low byte of the CODE of every input element (two's
+// complement for signed codes).  Phase A holds the four codes of each 16-byte group it loads and the buffer is in the same flat
+// order: one coalesced dword per lane and group.  A kernel of its own, phases A and B of dwconv3x3_flat_kernel's PAIR shape word
+// for word: as a mode of that kernel - a template argument, or a shared body - it renames or re-schedules every existing
+// instantiation (tools/kdiff.py).
+template <bool ONLINE, int H, int W, int EPI>
+__global__ __launch_bounds__(kBlock) void dwconv3x3_flat_stat_kernel(
+    const float* __restrict__ x, const float* __restrict__ wgt, const float* __restrict__ bias,
+    float* __restrict__ y, DwFlatGeom g, const float* __restrict__ in_stat, int n, const float* __restrict__ in_thr,
+    float levels, int lo_neg_max, float eps, float* __restrict__ cur_max_out, const float* __restrict__ bn_scale,
+    const float* __restrict__ bn_shift, int act, float* __restrict__ stat_out) {
+  static_assert(W % 2 == 0 && (H * W) % 4 == 0, "two columns per lane, planes of whole 16-byte groups");
+  constexpr int IN = H * W;                          // floats per plane
+  constexpr int LPP = W / 2;                         // lanes per plane in phase B
+  constexpr int P = 64 / LPP;                        // planes per wavefront and block
+  constexpr int NFI = P * IN / 4;                    // 16-byte groups per wavefront and block
+  constexpr int NLI = (NFI + 63) / 64;
+  constexpr unsigned kOob = 0x80000000u;   // beyond every resource of this kernel (host: tensors < 2 GiB)
+  __shared__ f4 tile[kBlock / 64][NLI * 64];
+  __shared__ unsigned k_stat[kDwStatSlots];
+  if (threadIdx.x < kDwStatSlots) k_stat[threadIdx.x] = 0u;
+  const unsigned lane = threadIdx.x & 63u;
+  const unsigned wave = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const unsigned b = blockIdx.x;
+  const unsigned blk_begin = b * g.per + (b < g.rem ? b : g.rem);
+  const unsigned blk_end = blk_begin + g.per + (b < g.rem ? 1u : 0u);
+  const unsigned planes = g.planes;
+  const unsigned n_samples = (unsigned)n;
+  unsigned s_base;
+  {
+    const unsigned p0 = blk_begin * (P * (kBlock / 64));
+    s_base = fast_div(p0 < planes ? p0 : planes - 1, g.by_c);
+  }
+  const bool has_bn = bn_scale != nullptr, has_stat = stat_out != nullptr, has_bias = bias != nullptr;
+  const fq_rsrc rx = make_rsrc(x, (int64_t)planes * IN * 4), rc = make_rsrc(y, y != nullptr ? (int64_t)planes * IN : 0);
+  const fq_rsrc rw = make_rsrc(wgt, (int64_t)g.C * 36);
+  const unsigned j = lane / LPP, pos = lane - j * LPP;
+  const bool b_lane = lane < P * LPP;
+  const bool first = pos == 0, last = pos == LPP - 1;
+  float* const my_tile = reinterpret_cast<float*>(tile[wave]);
+
+  struct Blk {
+    f4 raw[NLI];
+    f4 w03, w47;
+    float w8, bch, bsc, bsh;
+  };
+  auto issue = [&](unsigned blk, Blk& k) __attribute__((always_inline)) {
+    const unsigned base = (blk * (kBlock / 64) + wave) * P;                  // first plane of this wavefront (uniform)
+    const unsigned left = base < planes ? planes - base : 0u;
+    const unsigned np = left < (unsigned)P ? left : (unsigned)P;
+    const unsigned lim = np * (IN / 4);                                      // 16-byte groups that exist
+#pragma unroll
+    for (int i = 0; i < NLI; ++i)
+      k.raw[i] = buf_ld_v4f_nt(rx, (lane + 64u * i) < lim ? lane * 16u : kOob, base * (IN * 4u) + 1024u * i);
+    const unsigned ch = (b_lane && j < left) ? fast_mod(base + j, g.by_c) : 0u;
+    k.w03 = buf_ld_v4f(rw, ch * 36u, 0);
+    k.w47 = buf_ld_v4f(rw, ch * 36u, 16);
+    k.w8 = buf_ld_f32(rw, ch * 36u, 32);
+    k.bch = has_bias ? bias[ch] : 0.0f;
+    k.bsc = has_bn ? bn_scale[ch] : 1.0f;
+    k.bsh = has_bn ? bn_shift[ch] : 0.0f;
+  };
+
+  Blk nxt;
+  const ThresholdReq treq = threshold_request(in_stat, n, ONLINE ? nullptr : in_thr, blockIdx.x == 0);   // first in the memory queue
+  FQ_PIN();
+  if (blk_begin < blk_end) issue(blk_begin, nxt);
+  FQ_PIN();
+  const QParams q = dw_qparams_finish<ONLINE>(treq, in_stat, n, in_thr, levels, lo_neg_max, eps, cur_max_out);
+  __syncthreads();                                        // statistic table zeroed
+  for (unsigned blk = blk_begin; blk < blk_end; ++blk) {
+    Blk cur = nxt;
+    FQ_PIN();
+    if (blk + 1 < blk_end) issue(blk + 1, nxt);
+    FQ_PIN();
+    const unsigned base = (blk * (kBlock / 64) + wave) * P;
+    const unsigned left = base < planes ? planes - base : 0u;
+    const unsigned np = left < (unsigned)P ? left : (unsigned)P;
+    const unsigned lim = np * (IN / 4);
+    // ---- A: quantise in flat order, keep the codes, stage --------------------------------------------------------------------
+#pragma unroll
+    for (int i = 0; i < NLI; ++i) {
+      const f4 k = fq_code4(cur.raw[i], q);
+      const unsigned wd = ((unsigned)(int)k.x & 255u) | (((unsigned)(int)k.y & 255u) << 8) | (((unsigned)(int)k.z & 255u) << 16) |
+                          (((unsigned)(int)k.w & 255u) << 24);
+      buf_st_f32(rc, (lane + 64u * i) < lim ? lane * 4u : kOob, base * (unsigned)IN + 256u * i, __uint_as_float(wd));
+      tile[wave][lane + 64 * i] = k * q.scale;
+    }
+    FQ_DWF_PHASE();
+    // ---- B: 3x3 on the tile, the maximum only ---------------------------------------------------------------------------------
+    float m = 0.0f;
+    const bool is_out = b_lane && j < left;
+    if (b_lane) {
+      const f4 w03 = cur.w03, w47 = cur.w47;
+      const float* lp = my_tile + j * IN + pos * 2;
+      f2 aL = {0.f, 0.f}, aC = {0.f, 0.f}, aR = {0.f, 0.f};     // row r-1: (L, q0), (q0, q1), (q1, R)
+      f2 bL, bC, bR;
+      {
+        const f2 v = *reinterpret_cast<const f2*>(lp);
+        bL = (f2){left_of(v.y, first), v.x};
+        bC = v;
+        bR = (f2){v.y, right_of(v.x, last)};
+      }
+#pragma unroll
+      for (int r = 0; r < H; ++r) {
+        f2 cL = {0.f, 0.f}, cC = {0.f, 0.f}, cR = {0.f, 0.f};
+        if (r + 1 < H) {
+          const f2 v = *reinterpret_cast<const f2*>(lp + (r + 1) * W);
+          cL = (f2){left_of(v.y, first), v.x};
+          cC = v;
+          cR = (f2){v.y, right_of(v.x, last)};
+        }
+        f2 acc = dw_taps2(w03.x, w03.y, w03.z, w03.w, w47.x, w47.y, w47.z, w47.w, cur.w8, aL, aC, aR, bL, bC, bR, cL, cC, cR);
+        acc = dw_finish2<EPI>(acc, has_bias, cur.bch, has_bn, cur.bsc, cur.bsh, act);
+        m = fmaxf(m, fmaxf(fabsf(acc.x), fabsf(acc.y)));
+        aL = bL; aC = bC; aR = bR;
+        bL = cL; bC = cC; bR = cR;
+      }
+    }
+    if (has_stat) {
+      const unsigned sample = fast_div(base + (is_out ? j : 0u), g.by_c);
+      dw_stat_update(k_stat, s_base, sample, is_out, m, (int)lane, stat_out);
+    }
+    FQ_DWF_PHASE();                                       // (the next block's phase A overwrites the tile)
+  }
+  if (has_stat) dw_stat_flush(k_stat, s_base, n_samples, stat_out);
+}
+
 // ---- K2p, flat: 14x14 (stride 1 and 2), 7x7 and 28x28 (stride 1 and 2) planes ------------------------------------------------
 // tuning: bit 0 14x14 s1, bit 1 14x14 s2, bit 2 7x7, bit 3 28x28 s1, bit 4 28x28 s2
 // (28x28: 40.1 -> 34.6 us stride 1.  Stride 2 on 28x28 was dropped in round 2 because 0.05 % of its outputs changed from run
@@ -257,6 +389,13 @@ bool dw_flat_applies(const DwCall& d, int form) {
   return kind >= 0 && (form == 5 || (form == 0 && ((flat_on >> kind) & 1))) && whole && aligned16(d.x) && aligned16(d.y) &&
          d.n * d.c * d.h * d.wdt * 4 < (1ll << 31);
 }
+// the statistic pass (y == NULL) of a 28 x 28 plane: this form instead of the four-columns one, whose every memory instruction
+// touches many short rows there (fq_dwconv.hip asks before it falls back to that form)
+bool dw_flat_stat_applies(const DwCall& d) {
+  static const int flat_on = env_int("FQ_DW_FLAT", 31) & 31;
+  return d.y == nullptr && d.quant && d.lo_neg != kRangeMode && dw_flat_kind(d) == 3 && ((flat_on >> 3) & 1) && aligned16(d.x) &&
+         aligned16(d.x_codes_out) && d.n * d.c * d.h * d.wdt * 4 < (1ll << 31);
+}
 int dw_run_flat(const DwCall& d) {
   const int kind = dw_flat_kind(d);
   DwFlatGeom fg;
@@ -270,6 +409,8 @@ int dw_run_flat(const DwCall& d) {
   const int grid = dw_grid(nblk, fl_tune > 0 ? fl_tune : 3);
   fg.per = (unsigned)(nblk / grid);
   fg.rem = (unsigned)(nblk % grid);
+  if (d.y == nullptr)
+    return dw_launch(d, grid, 0, [](auto, auto o, auto e) { return dwconv3x3_flat_stat_kernel<o(), 28, 28, e()>; }, fg);
   auto go = [&](auto s, auto hw) {
     return dw_launch(d, grid, 0, [](auto q, auto o, auto e) {
       return dwconv3x3_flat_kernel<decltype(s)::value, q(), o(), decltype(hw)::value, decltype(hw)::value, e()>;

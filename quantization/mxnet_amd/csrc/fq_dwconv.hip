@@ -44,7 +44,8 @@ static int dwconv3x3_impl(const float* x, const float* w, const float* bias, flo
   // 0 auto, 1 LDS tiles, 2 one column per lane, 3 four columns per lane, 4 whole planes, 5 flat.  A forced form that does
   // not take the shape falls through to the next one that does.
   static const int form = env_int("FQ_DW_FORM", 0);
-  if (y == nullptr) {         // the statistic pass: one form
+  if (y == nullptr) {         // the statistic pass: the flat form on 28 x 28 planes, else the four-columns form
+    if (stride == 1 && dw_flat_stat_applies(d)) return dw_run_flat(d);
     FQ_REQUIRE(quant && stride == 1 && dw_cols4_applies(d, 3),
                "fq_dwconv3x3: without y (statistic pass) only stride 1, a quantised input and rows of a multiple of 4 floats, "
                "16-byte aligned, are taken (n=%lld c=%lld h=%lld w=%lld stride %d)", (long long)n, (long long)c, (long long)h,

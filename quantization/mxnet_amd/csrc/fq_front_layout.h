@@ -196,4 +196,23 @@ inline FrontPlan front_plan(int64_t n, int64_t cin, int64_t cout, int64_t h, int
   return p;
 }
 
+// ---- the STORING 1x1 with a front layer (fq_pw_stat.hip: pw_front_store_kernel, fq_pwconv_i8_front) ------------------------------
+// The same band buffer and the same phase 1; phase 2 takes the band's pixels as the B operand (lane = pixel: a channel's 32
+// pixels leave as one 128-byte run) and keeps the weight fragments in registers, so beside the band the launch holds only the
+// epilogue's per-channel constants (five words per output channel) and the front layer's 12 floats per input channel - no weight
+// fragments, no max / min tables, whatever the workgroup size.
+inline size_t front_store_fixed_lds(int64_t cin, int64_t cout) { return (size_t)cout * 5 * 4 + (size_t)cin * 12 * 4; }
+
+// front_plan's rules with that fixed part: eight wavefronts against four by front_waves_pick, rows by front_rows_pick.
+inline FrontPlan front_store_plan(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w, int num_cu, int wg_cap = kFrontWgCap,
+                                  int forced_rows = 0, int forced_waves = 0) {
+  const size_t fixed = front_store_fixed_lds(cin, cout);
+  FrontPlan p;
+  if (forced_waves == kFrontWaves || forced_waves == kFrontWavesWide) p.waves = forced_waves;
+  else p.waves = front_waves_pick(n, h, w, (int)cin, fixed, fixed, num_cu, wg_cap);
+  p.rows = front_rows_pick(n, h, w, (int)cin, fixed, num_cu, wg_cap, forced_rows, p.waves);
+  p.lds = p.rows >= 1 ? fixed + front_band_bytes((int)(w / 4), p.rows, (int)cin) : 0;
+  return p;
+}
+
 }  // namespace fqi

@@ -70,6 +70,9 @@ struct PwCall {
 bool pw_stat_shape_ok(int64_t n, int64_t cin, int64_t cout, int64_t hw);
 bool pw_stat_front_shape_ok(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w);      // ... with a front layer
 int pw_stat_launch(const PwCall& c);
+//      ... and the STORING 1x1 with a front layer (fq_pwconv_i8_front): c.front is set, c.x is not read, c.y and c.stat_out are written
+bool pw_front_store_shape_ok(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w);
+int pw_front_store_launch(const PwCall& c);
 // K2s  fq_pw_short.hip: the closing 1x1 of a residual unit (a) with the unit's shortcut convolution (b) in the same launch
 bool pw_short_shape_ok(int64_t cin, int64_t cin2, int64_t cout);
 int pw_short_launch(const PwCall& a, const PwCall& b);

@@ -292,6 +292,8 @@ __global__ __launch_bounds__(64 * NW, NW == kFrontWaves ? 3 : 2) void pw_stat_ke
     }
   };
   // FRONT: band by band - recompute the depthwise values into the band buffer as codes, then the tiles of the band
+  // (phase 1 has a TWIN, word for word: pw_front_store_kernel's phase1 below - a change to the dequantiser, the tap chain, the
+  // epilogue or the quantiser here is a change there, and tests/test_gpu_front_store.py compares that copy with the storing launches)
   auto run_front = [&](auto nn_c) __attribute__((always_inline)) {
     constexpr bool NN = decltype(nn_c)::value;
     constexpr int FE = FRONT ? FEPI : kEpiRuntime;
@@ -410,6 +412,227 @@ __global__ __launch_bounds__(64 * NW, NW == kFrontWaves ? 3 : 2) void pw_stat_ke
   __syncthreads();
   mma_stat_flush(k_stat, stat_out, s_base, cols, HW);
 }
+
+// ---- fq_pwconv_i8_front: the STORING 1x1 behind a stride-1 depthwise 3x3 that was never stored --------------------------------
+// 256 -> 256 channels (MobileNet1.0's 28 x 28 layers: the fp32 tensor between the two is written once and read once, only to be
+// quantised).  Phase 1 is run_front's above, word for word - the band of codes in the fq_front_layout.h buffer.  Phase 2 turns the
+// operands round: the WEIGHTS are the A operand and the band's pixels the B operand (the fragment read from the band buffer is the
+// same four dwords per slab either way), so lane = pixel, register = channel 8 g + 4 h + r of the tile, and the 32 pixels of a
+// channel leave as one 128-byte run - the epilogue and the store pattern of the sample form (fq_pw_sample.hip), whose values
+// these are bit for bit.  With lane = channel (the statistic pass's roles) a store would be 16 bytes per lane on 64 planes.
+// A wavefront owns CTW = 8 / NW channel tiles and keeps their 8 CTW weight fragments in registers for the whole launch (32 or 64
+// VGPRs); it walks all pixel tiles of every band with them.  Beside the band, LDS holds the per-channel constants only.
+struct PwFrontStoreGeom {
+  int Cin, KTS, Cout, HW, zoff;
+  int n;                     // samples
+};
+
+template <int FEPI, bool FSIGNED, int NW>
+__global__ __launch_bounds__(64 * NW, NW == kFrontWavesWide ? 4 : 2) void pw_front_store_kernel(
+    const int8_t* __restrict__ wfrag, const float* __restrict__ wscale, const int* __restrict__ wsum,
+    const float* __restrict__ bias, float* __restrict__ y, PwFrontStoreGeom g, const float* __restrict__ in_stat,
+    const float* __restrict__ in_thr, float levels, int lo_neg, float eps, float* __restrict__ cur_max_out,
+    const float* __restrict__ bn_scale, const float* __restrict__ bn_shift, int act, float* __restrict__ stat_out,
+    PwFrontArgs fa) {
+  constexpr int KT = 8, CTW = 8 / NW;            // 256 input channels, 256 output channels
+  constexpr int kThreads = 64 * NW;
+  extern __shared__ __attribute__((aligned(16))) unsigned char pfs_smem[];
+  int* c_zs = reinterpret_cast<int*>(pfs_smem);                                             // [Cout]
+  float* c_k = reinterpret_cast<float*>(c_zs + g.Cout);                                     // [4][Cout]: sx * w scale, bias, BN scale / shift
+  float* dwk = c_k + 4 * g.Cout;                                                            // [Cin][12] taps, bias, BN scale / shift
+  unsigned char* zbuf = reinterpret_cast<unsigned char*>(dwk + g.Cin * 12);                 // [Cin / 4][lay.pl] dwords, band of codes
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int h = lane >> 5, i32 = lane & 31;
+  const unsigned HW = (unsigned)g.HW;
+  // the workgroup's bands (band b of sample s is number s * bands + b)
+  const int64_t n_bands = (int64_t)g.n * fa.bands;
+  const int64_t t_begin = n_bands * blockIdx.x / gridDim.x, t_end = n_bands * (blockIdx.x + 1) / gridDim.x;
+  __shared__ unsigned k_stat[kStatSlots];
+  mma_stat_init(k_stat);
+  const unsigned s_base = (unsigned)((t_begin < n_bands ? t_begin : n_bands - 1) / fa.bands);
+  // this wavefront's weight fragments (fq_weight_codes' fragment-major copy: one coalesced 16-byte load each)
+  v4i wf[CTW][KT];
+#pragma unroll
+  for (int c = 0; c < CTW; ++c)
+#pragma unroll
+    for (int kt = 0; kt < KT; ++kt)
+      wf[c][kt] = *reinterpret_cast<const v4i*>(wfrag + (((int64_t)(wave * CTW + c) * g.KTS + kt) << 10) + (lane << 4));
+  const float fscale = input_threshold(fa.in_stat, g.n, fa.in_thr, nullptr, false) / fa.levels;
+  const float max_ = input_threshold(in_stat, g.n, in_thr, cur_max_out, blockIdx.x == 0);
+  const QParams q = make_qparams(max_, levels, lo_neg != 0, eps);
+  const int ubias = 128 - g.zoff;
+  const unsigned nn_xor = fq_nonneg_xor(ubias);
+  const bool has_bn = bn_scale != nullptr;
+  for (int i = threadIdx.x; i < g.Cout; i += kThreads) {
+    c_zs[i] = g.zoff * wsum[i];
+    c_k[i] = q.scale * wscale[i];
+    c_k[g.Cout + i] = bias != nullptr ? bias[i] : 0.0f;
+    c_k[2 * g.Cout + i] = has_bn ? bn_scale[i] : 1.0f;
+    c_k[3 * g.Cout + i] = has_bn ? bn_shift[i] : 0.0f;
+  }
+  for (int i = threadIdx.x; i < g.Cin; i += kThreads) {
+#pragma unroll
+    for (int t = 0; t < 9; ++t) dwk[i * 12 + t] = fa.w[i * 9 + t];
+    dwk[i * 12 + 9] = fa.bias != nullptr ? fa.bias[i] : 0.0f;
+    dwk[i * 12 + 10] = fa.bn_scale != nullptr ? fa.bn_scale[i] : 1.0f;
+    dwk[i * 12 + 11] = fa.bn_scale != nullptr ? fa.bn_shift[i] : 0.0f;
+  }
+  __syncthreads();
+  const FastQuot fqx = make_fast_quot(q.denom);
+  const int Q = fa.Q, W = fa.W, H = fa.H;
+
+  // ---- 1: the depthwise layer on rows r0 - 1 .. r0 + Rb of `segs` channels per wavefront and turn (pw_stat_kernel's run_front) ----
+  auto phase1 = [&](auto nn_c, unsigned smp, int r0, int Rb) __attribute__((always_inline)) {
+    constexpr bool NN = decltype(nn_c)::value;
+    const int seg = lane / Q, pos = lane - seg * Q;
+    const bool first = pos == 0, last = pos == Q - 1;
+    const bool has_fb = fa.bias != nullptr, has_fbn = fa.bn_scale != nullptr;
+    QParams qc = q;                               // compile-time epilogue, clip range from 0: ReLU / ReLU6 and the clip are one median
+    if (NN && FEPI != kEpiRuntime) qc.hi = FEPI == kEpiBnRelu6 ? fminf(q.hi, 6.0f) : q.hi;
+    const unsigned* xc32 = reinterpret_cast<const unsigned*>(fa.codes);
+    auto deq = [&](unsigned wd, int b) __attribute__((always_inline)) {
+      const int code = FSIGNED ? (int)(int8_t)(wd >> (8 * b)) : (int)((wd >> (8 * b)) & 255u);
+      return (float)code * fscale;
+    };
+    for (int c0 = 0; c0 < g.Cin; c0 += NW * fa.segs) {
+      const int c = front_channel(c0, wave, fa.segs, seg);
+      const bool c_ok = seg < fa.segs && c < g.Cin;
+      const int cc = c_ok ? c : 0;
+      const float* kc = dwk + cc * 12;
+      const float w00 = kc[0], w01 = kc[1], w02 = kc[2], w10 = kc[3], w11 = kc[4], w12 = kc[5], w20 = kc[6], w21 = kc[7],
+                  w22 = kc[8], bch = kc[9], bsc = kc[10], bsh = kc[11];
+      const unsigned* src = xc32 + ((int64_t)(smp * (unsigned)g.Cin + (unsigned)cc) * H) * Q + pos;
+      unsigned raw_c[kFrontRows + 2];           // (unconditional loads from clamped rows, masked: a row outside the plane is zero codes)
+#pragma unroll
+      for (int k = 0; k < kFrontRows + 2; ++k) {
+        const int t = r0 - 1 + k, tc = t < 0 ? 0 : (t > H - 1 ? H - 1 : t);
+        raw_c[k] = src[tc * Q] & ((t >= 0 && t < H) ? 0xFFFFFFFFu : 0u);
+      }
+      // this launch's code of one depthwise sum (the stored byte of the C16 layout)
+      auto zcode = [&](float acc) __attribute__((always_inline)) {
+        if constexpr (NN) {
+          const float v = FEPI == kEpiRuntime ? dw_finish<kEpiRuntime>(acc, has_fb, bch, has_fbn, bsc, bsh, fa.act)
+                                              : dw_finish<FEPI, false>(acc, false, 0.0f, true, bsc, bsh, 0);
+          return (unsigned)fq_code_nonneg(v, qc, fqx) ^ (nn_xor & 255u);
+        } else {
+          const float v = dw_finish<FEPI>(acc, has_fb, bch, has_fbn, bsc, bsh, fa.act);
+          return (unsigned)(fq_code_int(v, q) + ubias) ^ 0x80u;
+        }
+      };
+      float a[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, b[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      unsigned dst = (unsigned)front_byte(fa.lay, cc, 4 * pos);
+      const unsigned jstep = (unsigned)(front_byte(fa.lay, 0, 1) - front_byte(fa.lay, 0, 0));
+      const unsigned rstep = (unsigned)(front_byte(fa.lay, 0, 4 * Q) - front_byte(fa.lay, 0, 0));
+#pragma unroll
+      for (int k = 0; k < kFrontRows + 2; ++k) {
+        if (k <= Rb + 1) {                      // (the same for the whole workgroup)
+          float cv[6];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) cv[j + 1] = deq(raw_c[k], j);
+          const float lp = lane_prev(cv[4]), ln = lane_next(cv[1]);      // (taken by every lane, masked afterwards)
+          cv[0] = first ? 0.0f : lp;
+          cv[5] = last ? 0.0f : ln;
+          if (k >= 2) {                         // input row r0 + k - 1 closes output row r0 + k - 2
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              const unsigned code = zcode(dw_taps(w00, w01, w02, w10, w11, w12, w20, w21, w22, a[j], a[j + 1], a[j + 2], b[j],
+                                                  b[j + 1], b[j + 2], cv[j], cv[j + 1], cv[j + 2]));
+              if (c_ok) zbuf[dst + j * jstep] = (unsigned char)code;
+            }
+            dst += rstep;
+            asm volatile("" : "+v"(dst));
+          }
+#pragma unroll
+          for (int j = 0; j < 6; ++j) {
+            a[j] = b[j];
+            b[j] = cv[j];
+          }
+        }
+      }
+    }
+  };
+
+  // ---- 2: the band's pixels as 32-pixel tiles, lane = pixel (the last tile may be short: its lanes past the band repeat the last
+  // pixel and store nothing); FAST: BatchNorm + ReLU, no bias, fixed at compile time ----
+  float m = 0.0f;
+  auto phase2 = [&](auto fast_c, unsigned smp, int r0, int Rb) __attribute__((always_inline)) {
+    constexpr bool FAST = decltype(fast_c)::value;
+    const int npix = Rb * W, ntile = (npix + 31) >> 5;
+    const unsigned plane4 = HW * 4u;
+    // the wavefront's window on y: its first channel tile of sample smp, to the end of the sample
+    const int ch0 = wave * CTW * 32;
+    const fq_rsrc yr = make_rsrc(reinterpret_cast<char*>(y) + ((int64_t)smp * g.Cout + ch0) * plane4,
+                                 (int64_t)(g.Cout - ch0) * plane4);
+    for (int tl = 0; tl < ntile; ++tl) {
+      const int pt = tl * 32 + i32;
+      const bool ok = pt < npix;
+      const int pp = ok ? pt : npix - 1;
+      // channels 32 kt + 16 h .. + 15 of pixel pp: byte 0 of planes 8 kt + 4 h .. + 3
+      const unsigned* zp = reinterpret_cast<const unsigned*>(zbuf + front_byte(fa.lay, 16 * h, pp));
+      v4i bf[KT];
+#pragma unroll
+      for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) bf[kt][u] = (int)zp[(8 * kt + u) * fa.lay.pl];
+      const unsigned po = ok ? (unsigned)(4 * h) * plane4 + (unsigned)(r0 * W + pt) * 4u : kOobOffset;
+      // (the constants' offset is made opaque once per tile: they are the same for every tile, and hoisted out of this loop
+      // their 20 registers per group of four channels would push the weight fragments out of the register file)
+      int kb = ch0 + 4 * h;
+      asm volatile("" : "+v"(kb));
+#pragma unroll
+      for (int c = 0; c < CTW; ++c) {
+        v16i acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int kt = 0; kt < KT; ++kt) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(wf[c][kt], bf[kt], acc, 0, 0, 0);
+#pragma unroll
+        for (int gq = 0; gq < 4; ++gq) {
+          const int c0 = kb + c * 32 + 8 * gq;
+          const v4i zs = *reinterpret_cast<const v4i*>(c_zs + c0);
+          const f4 sxw = *reinterpret_cast<const f4*>(c_k + c0);
+          const f4 bch = *reinterpret_cast<const f4*>(c_k + g.Cout + c0);
+          const f4 bsc = *reinterpret_cast<const f4*>(c_k + 2 * g.Cout + c0);
+          const f4 bsh = *reinterpret_cast<const f4*>(c_k + 3 * g.Cout + c0);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            float v = (float)(acc[4 * gq + r] + zs[r]);
+            v = v * sxw[r];
+            if (FAST) {
+              v = v * bsc[r];
+              v = v + bsh[r];
+              v = fmaxf(v, 0.0f);
+            } else {
+              if (bias != nullptr) v = v + bch[r];
+              if (has_bn) {
+                v = v * bsc[r];
+                v = v + bsh[r];
+              }
+              v = act_rt(v, act);
+            }
+            buf_st_f32(yr, po, (unsigned)(c * 32 + 8 * gq + r) * plane4, v);
+            m = fmaxf(m, ok ? fabsf(v) : 0.0f);
+          }
+        }
+      }
+    }
+  };
+
+  const bool nn = fq_nonneg(q) && fqx.ok, fast_epi = bias == nullptr && has_bn && act == FQ_ACT_RELU;
+  for (int64_t bt = t_begin; bt < t_end; ++bt) {
+    const unsigned smp = (unsigned)(bt / fa.bands);
+    const int r0 = (int)(bt - (int64_t)smp * fa.bands) * fa.R;
+    const int Rb = H - r0 < fa.R ? H - r0 : fa.R;
+    if (nn) phase1(std::true_type{}, smp, r0, Rb);
+    else phase1(std::false_type{}, smp, r0, Rb);
+    __syncthreads();
+    if (fast_epi) phase2(std::true_type{}, smp, r0, Rb);
+    else phase2(std::false_type{}, smp, r0, Rb);
+    mma_stat_update(k_stat, stat_out, smp, s_base, m);      // (every lane of the wavefront sits in sample smp)
+    m = 0.0f;
+    __syncthreads();                              // (the next band overwrites the buffer)
+  }
+  mma_stat_flush(k_stat, stat_out, s_base, (int64_t)g.n * g.HW, HW);
+}
 }  // namespace
 
 namespace fqi {
@@ -513,6 +736,64 @@ int pw_stat_launch(const PwCall& c) {
              })) {
     return fail(FQ_ERR_INVALID, "fq_pwconv_i8_stat: K / 32 = %d is not instantiated", kt);
   }
+  if (rc != FQ_OK) return rc;
+  FQ_LAUNCH_CHECK();
+  return FQ_OK;
+}
+
+// ---- fq_pwconv_i8_front ----------------------------------------------------------------------------------------------------
+// front_store_plan of fq_front_layout.h, with the statistic pass's knobs: FQ_PWSTAT_FRONT_ROWS / FQ_PWSTAT_FRONT_WAVES
+static FrontPlan pw_front_store_plan(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w) {
+  const char* e = getenv("FQ_PWSTAT_FRONT_ROWS");
+  const char* ew = getenv("FQ_PWSTAT_FRONT_WAVES");
+  return front_store_plan(n, cin, cout, h, w, num_cu(), kFrontWgCap, e != nullptr ? atoi(e) : 0, ew != nullptr ? atoi(ew) : 0);
+}
+
+bool pw_front_store_shape_ok(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w) {
+  if (n <= 0 || h < 1 || w < 4 || w % 4 != 0 || w / 4 > 64 || cin != 256 || cout != 256) return false;
+  if (n * h * w >= (1ll << 31) - 512 || n * cin * h * w * 4 >= (1ll << 32)) return false;
+  // (the depthwise statistic pass in front must take the plane too: fq_dwconv3x3 without y)
+  return pw_front_store_plan(n, cin, cout, h, w).rows >= 1 && n * cin * ((w / 4 + 61) / 62) < (1ll << 31) - 1024;
+}
+
+template <int FEPI, bool FSIGNED, int NW>
+static int pw_front_store_go(const PwCall& c, const PwFrontStoreGeom& g, const PwFrontArgs& fa, int64_t grid, size_t lds) {
+  static const bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&pw_front_store_kernel<FEPI, FSIGNED, NW>),
+                                                  hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024) == hipSuccess;
+  FQ_REQUIRE(attr_ok, "fq_pwconv_i8_front: cannot raise the dynamic LDS limit");
+  hipLaunchKernelGGL((pw_front_store_kernel<FEPI, FSIGNED, NW>), dim3((unsigned)grid), dim3(64 * NW), lds, c.st, c.wcodes,
+                     c.wscale, (const int*)c.wsum, c.bias, c.y, g, c.in_stat, c.in_thr, c.levels, c.lo_neg, kEps,
+                     c.out_current_max, c.bn_scale, c.bn_shift, c.act, c.stat_out, fa);
+  return FQ_OK;
+}
+
+int pw_front_store_launch(const PwCall& c) {
+  const PwFront& f = *c.front;
+  PwFrontArgs fa = {};
+  fa.codes = static_cast<const int8_t*>(f.codes);
+  fa.w = f.w; fa.bias = f.bias; fa.bn_scale = f.bn_scale; fa.bn_shift = f.bn_shift;
+  fa.in_stat = f.in_stat; fa.in_thr = f.in_thr; fa.levels = f.levels; fa.act = f.act;
+  fa.H = (int)f.h; fa.W = (int)f.wdt; fa.Q = fa.W / 4; fa.segs = 64 / fa.Q;
+  const FrontPlan plan = pw_front_store_plan(c.n, c.cin, c.cout, f.h, f.wdt);
+  fa.R = plan.rows;
+  FQ_REQUIRE(fa.R >= 1, "fq_pwconv_i8_front: no band of the front layer fits the LDS");
+  fa.bands = (fa.H + fa.R - 1) / fa.R;
+  fa.lay = front_layout(fa.Q, fa.R);
+  PwFrontStoreGeom g;
+  g.Cin = (int)c.cin; g.KTS = (int)(c.cin_pad / 32); g.Cout = (int)c.cout; g.HW = (int)c.hw; g.zoff = c.zoff; g.n = (int)c.n;
+  if (int rc = pw_zero_stat(c)) return rc;
+  int64_t grid = (int64_t)num_cu() * stat_wg_per_cu(plan.lds, stat_wg_cap(kFrontWgCap, plan.waves));
+  if (grid > c.n * fa.bands) grid = c.n * fa.bands;
+  int rc = FQ_OK;
+  const int epi = (f.epi == kEpiBnRelu || f.epi == kEpiBnRelu6) ? f.epi : kEpiRuntime;
+  pair_pick<kEpiBnRelu, kEpiBnRelu6, kEpiRuntime>(epi, [&](auto epi_c) {
+    pair_pick<0, 1>(f.is_signed ? 1 : 0, [&](auto sg_c) {
+      constexpr int EPI = decltype(epi_c)::value;
+      constexpr bool SG = decltype(sg_c)::value != 0;
+      if (plan.waves == kFrontWavesWide) rc = pw_front_store_go<EPI, SG, kFrontWavesWide>(c, g, fa, grid, plan.lds);
+      else rc = pw_front_store_go<EPI, SG, kFrontWaves>(c, g, fa, grid, plan.lds);
+    });
+  });
   if (rc != FQ_OK) return rc;
   FQ_LAUNCH_CHECK();
   return FQ_OK;

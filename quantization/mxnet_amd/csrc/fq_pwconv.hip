@@ -307,6 +307,64 @@ int fq_pwconv_i8_stat(const float* x, const int8_t* wcodes, const float* wscale,
   return pw_stat_launch(c);
 }
 
+// The storing 1x1 with a front layer: fq_pwconv_i8_stat(front_codes != NULL)'s contract with y and stat_out as results
+// (fq_pw_stat.hip: pw_front_store_kernel).  x is never dereferenced.
+int fq_pwconv_i8_front_supported(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w) {
+  return pw_front_store_shape_ok(n, cin, cout, h, w) ? 1 : 0;
+}
+
+int fq_pwconv_i8_front(const float* x, const int8_t* wcodes, const float* wscale, const int32_t* wsum, const float* bias, float* y,
+                       int64_t n, int64_t cin, int64_t cin_pad, int64_t cout_pad, int64_t cout, int64_t h, int64_t w,
+                       const float* in_stat, const float* in_thr, int in_width, unsigned in_flags, float* out_current_max,
+                       const float* bn_scale, const float* bn_shift, int act, float* stat_out, fqStream_t stream,
+                       const void* front_codes, const float* front_w, const float* front_bias, const float* front_bn_scale,
+                       const float* front_bn_shift, int front_act, const float* front_in_stat, const float* front_in_thr,
+                       int front_width, unsigned front_flags) {
+  (void)x;
+  FQ_REQUIRE(wcodes && wscale && wsum && y && stat_out && front_codes && front_w, "fq_pwconv_i8_front: null pointer");
+  FQ_REQUIRE(pw_front_store_shape_ok(n, cin, cout, h, w), "fq_pwconv_i8_front: shape not taken (n=%lld cin=%lld cout=%lld "
+             "%lldx%lld): see fq_pwconv_i8_front_supported", (long long)n, (long long)cin, (long long)cout, (long long)h, (long long)w);
+  FQ_REQUIRE(cin_pad == cin && cout_pad == cout, "fq_pwconv_i8_front: cin_pad / cout_pad must be those of fq_weight_codes");
+  FQ_REQUIRE(in_stat != nullptr || in_thr != nullptr, "fq_pwconv_i8_front: give in_stat (online), in_thr (offline) or both");
+  FQ_REQUIRE(in_width >= 2 && in_width <= 8, "fq_pwconv_i8_front: input width %d does not fit int8 codes", in_width);
+  FQ_REQUIRE(!(in_flags & ~(FQ_ACT_SIGNED | FQ_ACT_LO_NEG_MAX)), "fq_pwconv_i8_front: unsupported activation flags");
+  FQ_REQUIRE((bn_scale == nullptr) == (bn_shift == nullptr), "fq_pwconv_i8_front: bn_scale and bn_shift go together");
+  PwCall c;
+  c.prezeroed = (act & FQ_STAT_PREZEROED) != 0;
+  act &= ~FQ_STAT_PREZEROED;
+  FQ_REQUIRE(act >= FQ_ACT_NONE && act <= FQ_ACT_RELU6, "fq_pwconv_i8_front: unknown activation %d", act);
+  FQ_REQUIRE(aligned16(wcodes) && aligned16(front_codes) && aligned16(y), "fq_pwconv_i8_front: wcodes, front_codes and y must "
+             "be 16-byte aligned");
+  FQ_REQUIRE(front_in_stat || front_in_thr, "fq_pwconv_i8_front: the front layer needs in_stat or in_thr");
+  FQ_REQUIRE(front_width >= 2 && front_width <= 8 && !(front_flags & ~(FQ_ACT_SIGNED | FQ_ACT_LO_NEG_MAX)) &&
+                 ((front_flags & FQ_ACT_SIGNED) || !(front_flags & FQ_ACT_LO_NEG_MAX)),
+             "fq_pwconv_i8_front: the front layer's input codes are at most 8 bits wide, flags signed / lo_neg_max only");
+  FQ_REQUIRE((front_bn_scale == nullptr) == (front_bn_shift == nullptr) && front_act >= FQ_ACT_NONE && front_act <= FQ_ACT_RELU6,
+             "fq_pwconv_i8_front: bad BatchNorm or activation of the front layer");
+  PwFront front = {};
+  front.codes = front_codes; front.w = front_w; front.bias = front_bias; front.bn_scale = front_bn_scale;
+  front.bn_shift = front_bn_shift; front.act = front_act; front.in_stat = front_in_stat; front.in_thr = front_in_thr;
+  front.epi = (front_bn_scale != nullptr && front_bias == nullptr)
+                  ? (front_act == FQ_ACT_RELU ? kEpiBnRelu : front_act == FQ_ACT_RELU6 ? kEpiBnRelu6 : kEpiRuntime)
+                  : kEpiRuntime;
+  front.levels = act_levels(front_width, front_flags);
+  front.is_signed = (front_flags & FQ_ACT_SIGNED) != 0;
+  front.h = h; front.wdt = w;
+  c.front = &front;
+  c.x = nullptr; c.wcodes = wcodes + cout_pad * cin_pad; c.wscale = wscale; c.wsum = wsum; c.bias = bias; c.y = y;
+  c.n = n; c.cin = cin; c.cin_pad = cin_pad; c.cout = cout; c.hw = h * w; c.stride = 1; c.h_in = c.w_in = c.w_out = 0;
+  c.in_stat = in_stat; c.in_thr = in_thr;
+  c.levels = act_levels(in_width, in_flags);
+  c.lo_neg = (in_flags & FQ_ACT_LO_NEG_MAX) ? 1 : 0;
+  c.zoff = (in_flags & FQ_ACT_SIGNED) ? 0 : 128;
+  c.out_current_max = out_current_max; c.bn_scale = bn_scale; c.bn_shift = bn_shift; c.act = act;
+  c.stat_out = stat_out; c.residual = nullptr; c.ws = nullptr; c.st = (hipStream_t)stream; c.form = 0;
+  // algorithmic bytes: the pointwise layer's (this launch stands for it); moved: one byte per element of the front layer's input, y
+  const double in_elems = (double)n * cin * h * w, out_elems = (double)n * cout * h * w;
+  ProfScope prof(FQ_KERNEL_PWCONV, 4.0 * (in_elems + out_elems), c.st, in_elems + 4.0 * out_elems);
+  return pw_front_store_launch(c);
+}
+
 int fq_pwconv_i8_strided(const float* x, const int8_t* wcodes, const float* wscale, const int32_t* wsum,
                          const float* bias, float* y, int64_t n, int64_t cin, int64_t cin_pad, int64_t cout, int64_t h,
                          int64_t w, int stride, const float* in_stat, const float* in_thr, int in_width,

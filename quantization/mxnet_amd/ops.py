@@ -688,6 +688,58 @@ def pwconv_front_supported(xshape, cout):
     return bool(_lib_().fq_pwconv_i8_stat_supported(n, cin, int(cout), h * w, h, w))
 
 
+def pwconv_front_store_supported(xshape, cout):
+    """True when `pwconv_i8(front=)` takes a STORING 1x1 to `cout` channels whose (N, Cin, H, W) input is the output of a stride-1
+    depthwise 3x3 recomputed in front of it (fq_pwconv_i8_front_supported; False under an older build of the library loaded
+    through FQ_LIB_PATH: the two storing launches remain)."""
+    n, cin, h, w = (int(v) for v in xshape)
+    lib = _lib_()
+    return lib.fq_version() >= 103 and bool(lib.fq_pwconv_i8_front_supported(n, cin, int(cout), h, w))
+
+
+def _pwconv_i8_front(xshape, wcodes, wscale, wsum, front, bias=None, in_stat=None, in_thr=None, width=8, flags=0, cur_out=None,
+                     bn_scale=None, bn_shift=None, act=None, x=None):
+    """`pwconv_i8(front=)`: a fused 1x1 convolution whose (N, Cin, H, W) = `xshape` input is the output of a stride-1 depthwise 3x3
+    that was not stored (fq_pwconv_i8_front).  `x` is handed through and never read.  Returns (y, stat)."""
+    _check(wcodes, "wcodes", torch.int8)
+    _check(wscale, "wscale")
+    _check(wsum, "wsum", torch.int32)
+    for name, t in (("bias", bias), ("in_stat", in_stat), ("in_thr", in_thr), ("bn_scale", bn_scale),
+                    ("bn_shift", bn_shift), ("cur_out", cur_out)):
+        if t is not None:
+            _check(t, name)
+    xshape = tuple(int(v) for v in xshape)
+    unknown = set(front) - {"x_codes", "w", "bias", "bn_scale", "bn_shift", "act", "in_stat", "in_thr", "width", "flags"}
+    if unknown or len(xshape) != 4:
+        raise ValueError("pwconv_i8(front=) wants x (N, Cin, H, W) and the keys of a depthwise call; got %s, %s"
+                         % (xshape, sorted(unknown)))
+    n, cin, h, w = xshape
+    dev = wcodes.device
+    cout = wscale.numel()
+    cin_pad = wcodes.shape[1]
+    if (cin + 63) // 64 * 64 != cin_pad:
+        raise ValueError("x has %d channels but the weight codes were made for a row length that pads to %d" % (cin, cin_pad))
+    fw = _check(front["w"], "front['w']")
+    if tuple(fw.shape) != (cin, 1, 3, 3):
+        raise ValueError("front['w'] must be (%d,1,3,3); got %s" % (cin, tuple(fw.shape)))
+    _check_front_codes(front["x_codes"], "front['x_codes']", xshape, dev)
+    for name in ("bias", "bn_scale", "bn_shift", "in_stat", "in_thr"):
+        if front.get(name) is not None:
+            _check(front[name], "front['%s']" % name)
+    if in_stat is not None and cur_out is None:
+        cur_out = torch.empty(1, dtype=torch.float32, device=dev)
+    y = torch.empty((n, cout, h, w), dtype=torch.float32, device=dev)
+    stat, zflag = _stat_target(n, dev, True)
+    check_call(_lib_().fq_pwconv_i8_front(_ptr(x), _ptr(wcodes), _ptr(wscale), _ptr(wsum), _ptr(bias), _ptr(y), n, cin, cin_pad,
+                                          wcodes.shape[0], cout, h, w, _ptr(in_stat), _ptr(in_thr), int(width), int(flags),
+                                          _ptr(cur_out), _ptr(bn_scale), _ptr(bn_shift), _ACTS[act] | zflag, _ptr(stat),
+                                          _stream(wcodes), _ptr(front["x_codes"]), _ptr(fw), _ptr(front.get("bias")),
+                                          _ptr(front.get("bn_scale")), _ptr(front.get("bn_shift")), _ACTS[front.get("act")],
+                                          _ptr(front.get("in_stat")), _ptr(front.get("in_thr")), int(front.get("width", 8)),
+                                          int(front.get("flags", 0))))
+    return y, stat
+
+
 def pair_codes_shape(xshape):
     """Shape of the int8 buffer in which `pwconv_i8_stat` hands the codes of an (N, Cin, H, W) input to `pwdw_fused`: the C16
     layout of include/fakequant.h over whole 32-channel slabs."""
@@ -1012,7 +1064,7 @@ def pwconv_sub2_supported(cin, cout):
 
 def pwconv_i8(x, wcodes, wscale, wsum, bias=None, in_stat=None, in_thr=None, width=8, flags=0, cur_out=None,
               bn_scale=None, bn_shift=None, act=None, want_stat=True, form=None, stride=1, residual=None, out_codes=None,
-              side_codes=None, subsample=False):
+              side_codes=None, subsample=False, front=None):
     """1x1 convolution on the integer codes (int8 MFMA, exact int32 accumulation) with quantise-on-load and fused
     BatchNorm / activation / statistic.  x: (N, Cin, H, W) raw activations; stride 1 or 2 (no padding); `residual` (the
     output's shape) is added after BatchNorm and before the activation.  `form` names one of PW_FORMS ("stream", "sample",
@@ -1026,7 +1078,20 @@ def pwconv_i8(x, wcodes, wscale, wsum, bias=None, in_stat=None, in_thr=None, wid
 
     `subsample=True` (fq_pwconv_i8_sub2; fp32 x (N, Cin, H, W), stride 1): the returned y is y[:, :, ::2, ::2] of the tensor
     the call stands for - (N, Cout, ceil(H/2), ceil(W/2)), all its stride-2 readers need - while `stat` and `residual` keep the
-    whole planes."""
+    whole planes.
+
+    `front` (fq_pwconv_i8_front): x is the output of a stride-1 depthwise 3x3 that was not stored - the launch recomputes it from
+    the codes of that layer's input and stores what `dwconv3x3` followed by this call store, bit for bit.  The dict of the depthwise
+    call that `pwconv_i8_stat(front=)` takes; in_stat / in_thr of this call are the statistic / threshold of the depthwise OUTPUT.
+    x is never read: a tensor of the (N, Cin, H, W) shape, or the shape itself.  See `pwconv_front_store_supported`."""
+    if front is not None:
+        if form is not None or stride != 1 or residual is not None or out_codes is not None or side_codes is not None \
+                or subsample or not want_stat or isinstance(x, Codes16):
+            raise ValueError("pwconv_i8(front=) is the plain storing launch: fp32 out, stride 1, no residual, with its statistic")
+        is_t = isinstance(x, torch.Tensor)
+        return _pwconv_i8_front(tuple(x.shape) if is_t else tuple(x), wcodes, wscale, wsum, front, bias, in_stat=in_stat,
+                                in_thr=in_thr, width=width, flags=flags, cur_out=cur_out, bn_scale=bn_scale, bn_shift=bn_shift,
+                                act=act, x=x if is_t else None)
     in16 = isinstance(x, Codes16)
     if subsample:
         if (in16 and side_codes is None) or out_codes is not None or stride != 1 or len(x.shape) != 4:

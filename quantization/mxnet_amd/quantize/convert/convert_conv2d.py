@@ -171,14 +171,19 @@ def depthwise_fused(block, x, weight_q, bias, plan):
     call = dict(x=contiguous(x._t), w=contiguous(weight_q._t), bias=None if bias is None else bias._t,
                 stride=block._kwargs["stride"][0], bn_scale=scale, bn_shift=shift, act=fz["act"], **plan)
     front = front_target(block, fz, x, plan) if c16_in is None else None
+    # (no pair behind: the 1x1 may still be a STORING launch that recomputes this block's values - `front_store_target`)
+    mode = "pair" if front is not None else "store"
+    if front is None and c16_in is None:
+        front = front_store_target(block, fz, x, plan)
     if front is not None:
         # statistic only, and the codes of the input: the 1x1 convolution behind recomputes the values inside its own statistic
-        # pass (a fresh code buffer of the current stream per forward, like the pair's)
+        # pass or its storing launch (a fresh code buffer of the current stream per forward, like the pair's); the record carries
+        # the storing depthwise call for any other reader (`_materialise`)
         xcodes = torch.empty(ops.front_codes_shape(call["x"].shape), dtype=torch.int8, device=call["x"].device)
         stat = _dwconv3x3(call, store=False, x_codes_out=xcodes)[1]
         out = NDArray(_placeholder(tuple(call["x"].shape), call["x"].device))
         out._fq_stat = stat
-        out._fq_deferred = dict(kind="front", consumer=front, call=call, x_codes=xcodes)
+        out._fq_deferred = dict(kind="front", consumer=front, call=call, x_codes=xcodes, mode=mode)
         return out
     y, stat = _dwconv3x3(call)
     out = NDArray(y)
@@ -201,26 +206,69 @@ def front_target(block, fz, x, plan, level=None):
     the tensor between the two (no hooks, no KL collection, no multi-GPU exchange of the 1x1's statistic).  Returns the 1x1 block
     or None.  `level`: the knob that decides in place of `fuse.PAIR_FRONT` (`chain_target`: `fuse.PAIR_CHAIN`)."""
     from .. import fuse as _fuse
-    nxt = fz.get("front_pw")
     level = int(_fuse.PAIR_FRONT) if level is None else int(level)
     # (FQ_PWDW_FRONT / FQ_PWDW_CHAIN: 1 - among batches in flight, where it pays; 2 - in every forward)
-    if nxt is None or not _fuse.PAIR_CODES or not (level >= 2 or (level and ops.in_flight())) \
+    nxt = _front_link(block, fz, plan, level) if _fuse.PAIR_CODES else None
+    if nxt is None:
+        return None
+    # the pair behind: the same question the 1x1 block will ask itself, with the only things it looks at in its input and plan
+    if recompute_target(nxt, nxt._fq_pw_fused, x, dict(in_stat=None), None) is None or handover_target(nxt) is not None:
+        return None
+    if not ops.pwconv_front_supported(tuple(x._t.shape), nxt._kwargs["num_filter"]):
+        return None
+    return nxt
+
+
+def _front_link(block, fz, plan, level):
+    """What `front_target` and `front_store_target` both ask: the 1x1 block quantize/fuse.py linked behind this depthwise block
+    (`front_pw`) when the knob's `level` admits this forward (1: declared as batches in flight, 2: every forward), this block
+    quantises its input online with stride 1 and without a folded fake-BN, the 1x1 quantises online on integer codes, and no
+    hook sits on this block or on what it folded.  The block or None."""
+    nxt = fz.get("front_pw")
+    if nxt is None or not (level >= 2 or (level and ops.in_flight())) \
             or block._kwargs["stride"] != (1, 1) \
             or block.quantize_args.fake_bn or "in_stat" not in plan or "in_thr" in plan or plan["width"] > 8:
         return None
-    pz, a = nxt._fq_pw_fused, nxt.quantize_args
+    a = nxt.quantize_args
     if not (nxt.enable_quantize and a.quantize_input and nxt.quantize_input and not nxt.quantize_input_offline
             and a.in_width <= 8 and a.wt_width <= 8 and not getattr(nxt, "_fq_no_int8", False) and not a.fake_bn
             and getattr(nxt, "_fq_global_stat", None) is None and getattr(nxt, "_fq_residual", None) is None):
         return None
     if any(_hooked(b) for b in (block, fz.get("bn"), fz.get("act_block"))):
         return None
-    # the pair behind: the same question the 1x1 block will ask itself, with the only things it looks at in its input and plan
-    if recompute_target(nxt, pz, x, dict(in_stat=None), None) is None or handover_target(nxt) is not None:
+    return nxt
+
+
+def front_store_target(block, fz, x, plan):
+    """The fused 1x1 convolution behind this stand-alone depthwise block when that convolution is NOT the first half of a
+    recompute pair and may still recompute this block's values - inside its STORING launch (fq_pwconv_i8_front): this block then
+    runs as a statistic pass that keeps its input's codes, as in front of a pair.  `_front_link`'s conditions with
+    `fuse.PW_FRONT_STORE` as the knob; on top, the call is part of the rewired net's forward (a caller that runs this block on its
+    own must get a tensor), nothing observes the tensor between the two (no hooks, no KL collection, no multi-GPU exchange of the
+    1x1's statistic), and the 1x1 will take its plain storing path in this forward (`front_store_taken`).  The block or None."""
+    from .. import fuse as _fuse
+    nxt = _front_link(block, fz, plan, int(_fuse.PW_FRONT_STORE))
+    if nxt is None or x._t.dim() != 4 or x._t.shape[2] * x._t.shape[3] < _fuse.PW_FRONT_STORE_MIN_PIXELS or autograd.is_recording() or _fuse._collection is not None \
+            or getattr(ops.StatArena._tls, "current", None) is None:
         return None
-    if not ops.pwconv_front_supported(tuple(x._t.shape), nxt._kwargs["num_filter"]):
+    # (stride 1: this block's output has its input's shape, the only thing the 1x1 looks at in it)
+    if not front_store_taken(nxt, nxt._fq_pw_fused, x, dict(in_stat=None, width=nxt.quantize_args.in_width)):
         return None
     return nxt
+
+
+def front_store_taken(block, fz, x, plan):
+    """The 1x1 block's side of `front_store_target`, asked again by the block itself when the deferred record arrives: it
+    quantises online on integer codes with stride 1, hands no codes on, adds no residual, is neither the first half of a pair nor
+    pooled nor a deferred shortcut, no hook sits on it, and fq_pwconv_i8_front takes the shape."""
+    if "in_stat" not in plan or "in_thr" in plan or plan["width"] > 8 or block._kwargs["stride"] != (1, 1) \
+            or fz.get("kind") != "1x1" or getattr(block, "_fq_residual", None) is not None \
+            or getattr(block, "_fq_defer_short", False) or _hooked(block) or handover_target(block) is not None:
+        return False
+    xshape = tuple(x._t.shape)
+    if recompute_target(block, fz, x, plan, None) is not None or gap_target(block, fz, None, xshape, False) is not None:
+        return False
+    return ops.pwconv_front_store_supported(xshape, block._kwargs["num_filter"])
 
 
 def _weight_rows_per_scale(block, args):
@@ -603,9 +651,13 @@ def pointwise_fused(block, F, x, weight_raw, weight_q, bias, plan, weights_quant
     front = getattr(x, "_fq_deferred", None)             # (only the record of a depthwise block in front reaches this function)
     if front is not None:
         from .. import fuse as _fuse
-        if not (on_codes and fz.get("kind") == "1x1" and _fuse.PAIR_CODES and getattr(block, "_fq_residual", None) is None
-                and handover_target(block) is None and recompute_target(block, fz, x, plan, None) is not None):
-            x, front = _materialise(x), None             # (the pair is not taken after all: the depthwise block's storing launch)
+        if front.get("mode") == "store":                 # (this block's storing launch recomputes the depthwise values)
+            taken = on_codes and front["consumer"] is block and front_store_taken(block, fz, x, plan)
+        else:
+            taken = (on_codes and fz.get("kind") == "1x1" and _fuse.PAIR_CODES and getattr(block, "_fq_residual", None) is None
+                     and handover_target(block) is None and recompute_target(block, fz, x, plan, None) is not None)
+        if not taken:
+            x, front = _materialise(x), None             # (not taken after all: the depthwise block's storing launch)
     res0 = getattr(block, "_fq_residual", None)
     if res0 is not None and res0.get("short") is not None and not (on_codes and fz.get("kind") == "1x1"):
         res0["t"], res0["short"] = materialise_shortcut_record(res0["short"]), None      # (no integer path here: the tensor after all)
@@ -631,7 +683,7 @@ def pointwise_fused(block, F, x, weight_raw, weight_q, bias, plan, weights_quant
         if front is not None:
             # (neither launch of the pair reads the fp32 tensor - the statistic pass recomputes it, the fused launch loads the
             # codes that pass leaves - but both are told its shape by it: an allocation nothing is written to or read from)
-            x_arg = torch.empty(tuple(x._t.shape), dtype=torch.float32, device=x._t.device)
+            x_arg = torch.empty(tuple(x._t.shape), dtype=torch.float32, device=x._t.device) if front.get("mode") != "store" else None
         else:
             x_arg = c16_in if c16_in is not None else contiguous(x._t)
         if fz.get("kind") == "3x3":
@@ -749,10 +801,20 @@ def pointwise_fused(block, F, x, weight_raw, weight_q, bias, plan, weights_quant
                                          plan=dict(in_stat=plan["in_stat"], width=plan["width"], flags=plan["flags"],
                                                    cur_out=plan.get("cur_out")), consumer=pair, x_codes=xcodes, front=front)
                 return res_
-            out = ops.pwconv_i8(x_arg, codes, scales, rowsum, None if bias is None else bias._t,
-                                bn_scale=scale, bn_shift=shift,
-                                act=res["act"] if "residual" in extra else fz["act"],
-                                stride=stride_, **extra, **plan)
+            if front is not None:
+                # (`front_store_taken`: no pair, no pooling, nothing in `extra` - the plain storing launch, with the depthwise
+                # block in front recomputed inside it)
+                c_ = front["call"]
+                out = ops.pwconv_i8(tuple(x._t.shape), codes, scales, rowsum, None if bias is None else bias._t,
+                                    front=dict(x_codes=front["x_codes"], w=c_["w"], bias=c_["bias"], bn_scale=c_["bn_scale"],
+                                               bn_shift=c_["bn_shift"], act=c_["act"], in_stat=c_["in_stat"], width=c_["width"],
+                                               flags=c_["flags"]),
+                                    bn_scale=scale, bn_shift=shift, act=fz["act"], **plan)
+            else:
+                out = ops.pwconv_i8(x_arg, codes, scales, rowsum, None if bias is None else bias._t,
+                                    bn_scale=scale, bn_shift=shift,
+                                    act=res["act"] if "residual" in extra else fz["act"],
+                                    stride=stride_, **extra, **plan)
             y, stat = out[0], out[1]
             if sub_link is not None and side_blk is None:
                 trunk = NDArray(y)

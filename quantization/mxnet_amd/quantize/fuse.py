@@ -183,6 +183,16 @@ PAIR_FRONT = int(_os.environ.get("FQ_PWDW_FRONT", "1"))
 # FQ_PWDW_FRONT: 1 - in forwards declared as batches in flight, 2 - in every forward, 0 - never.  DESIGN 3.7 has the measurements
 # behind the default.
 PAIR_CHAIN = int(_os.environ.get("FQ_PWDW_CHAIN", "1"))
+# FQ_PW_FRONT_STORE: a stride-1 depthwise 3x3 that stands alone in front of a STORING 1x1 (no recompute pair behind it; MobileNet1.0:
+# dw5 -> pw5, 256 channels at 28 x 28) runs as a statistic pass that keeps its input's codes, and the 1x1's storing launch recomputes
+# the depthwise values from them (fq_pwconv_i8_front; convert_conv2d.front_store_target; results identical either way).  Levels
+# as FQ_PWDW_FRONT: 1 - in forwards declared as batches in flight, 2 - in every forward, 0 - never.  DESIGN 3.7 has the
+# measurements behind the default.
+PW_FRONT_STORE = int(_os.environ.get("FQ_PW_FRONT_STORE", "1"))
+# (smallest plane, in pixels, the fold is taken on.  The launch takes every 256 -> 256 plane with W % 4 == 0, and the same link has
+# other planes at other input sizes - 16 x 16 at 128 x 128 images: from 14 x 14 down the launches are bound by set-up and latency,
+# not by the bytes the fold saves, and nothing was measured there)
+PW_FRONT_STORE_MIN_PIXELS = int(_os.environ.get("FQ_PW_FRONT_STORE_MIN_PIXELS", "784"))
 # Subsampled trunk (round 6, fq_pwconv_i8_sub2): the closing 1x1 of a ResNet-v1 stage stores only the pixels its two readers -
 # the next stage's first 1x1 and shortcut 1x1, both stride 2 without padding - look at (FQ_SUBSAMPLE=0: the whole tensor; A/B)
 SUBSAMPLE = _os.environ.get("FQ_SUBSAMPLE", "1") != "0"

@@ -2,6 +2,7 @@
 read) against fq_pwconv_i8_stat + fq_pwdw_fused, on MobileNet1.0's pointwise -> depthwise pairs at batch 128.
 
     python tools/pwdwbench.py [--batch 128] [--reps 30] [--pairs 1,2,3,4,5] [--codes 0] [--front 1] [--chain 1] [--sweep 1]
+                              [--front-store 1]
 
 --codes 1 (default): the statistic pass keeps the int8 codes of x and the fused launch loads them; 0: both read the fp32 x.
 --front 1: ONLY the table of the depthwise layer in front of the first pair - fq_dwconv3x3 (storing) + fq_pwconv_i8_stat against
@@ -11,6 +12,9 @@ MobileNet1.0's and MobileNet0.5's dw1 -> pw1 at the batch size.
 fq_pwdw_fused in statistic mode (mid_codes_out: the codes of its depthwise input kept, no z) + fq_pwconv_i8_stat with the depthwise
 layer recomputed in front - on MobileNet1.0's and MobileNet0.5's shapes, the four launches alternating repetition by repetition.
 Under a library without the statistic mode (FQ_LIB_PATH = the parent's) the stored pair alone is timed.
+--front-store 1: ONLY the storing 1x1 behind a stand-alone depthwise layer, dw5 -> pw5 (256 channels at 28 x 28; MobileNet0.5's 128
+channels where the library takes them) - fq_dwconv3x3 (storing) + fq_pwconv_i8 against fq_dwconv3x3 without y + fq_pwconv_i8_front,
+the four launches alternating repetition by repetition.
 --sweep 1: with --front 1 or --chain 1, ONLY the statistic pass with the front layer, under FQ_PWSTAT_FRONT_ROWS = 1 .. 8 and
 FQ_PWSTAT_FRONT_WAVES = 4 and 8 (the library reads both at every call) and under the launch's own choice, all configurations
 alternating repetition by repetition in this one process; median +- standard deviation, every configuration's values compared
@@ -225,6 +229,72 @@ def chain_table(n, reps, dev, sweep=False):
               % ("", reps, sds[0], sds[1], sds[2], sds[3]))
 
 
+FRONT_STORES = {"mobilenet1.0": (256, 256, 28), "mobilenet0.5": (128, 128, 28)}
+
+
+def front_store_table(n, reps, dev):
+    """--front-store 1: the storing 1x1 behind a stand-alone depthwise layer, MobileNet's dw5 -> pw5 - fq_dwconv3x3 (storing) +
+    fq_pwconv_i8 against fq_dwconv3x3 without y (statistic pass, input codes kept) + fq_pwconv_i8_front; the four launches
+    alternating repetition by repetition."""
+    print("front-store    shape              stored: dw + pw = total (us)          folded: dw-stat + pw-front = total (us)   "
+          "MB moved stored / folded   speed-up")
+    for name, (cin, cout, hw) in FRONT_STORES.items():
+        shape = (n, cin, hw, hw)
+        if not ops.pwconv_front_store_supported(shape, cout):
+            print("%-14s %s: shape not taken" % (name, (n, cin, cout, hw)))
+            continue
+        y0 = torch.relu(torch.randn(*shape, device=dev)) * 1.7
+        dww = ops.weight_fake_quant(torch.randn(cin, 1, 3, 3, device=dev) * 0.3, cin, 8)
+        codes, scales, rowsum = ops.weight_codes(torch.randn(cout, cin, device=dev) * 0.2, cout, 8)
+        scA, shA = torch.rand(cin, device=dev) + 0.5, torch.randn(cin, device=dev) * 0.3
+        scB, shB = torch.rand(cout, device=dev) + 0.5, torch.randn(cout, device=dev) * 0.3
+        s0 = ops.absmax_per_sample(y0)
+        curA, curB = torch.zeros(1, device=dev), torch.zeros(1, device=dev)
+        yc = torch.empty(ops.front_codes_shape(shape), dtype=torch.int8, device=dev)
+        dwk = dict(stride=1, in_stat=s0, cur_out=curA, bn_scale=scA, bn_shift=shA, act="relu")
+        pwk = dict(cur_out=curB, bn_scale=scB, bn_shift=shB, act="relu")
+        st = {}
+
+        def dw():
+            st["z"], st["zs"] = ops.dwconv3x3(y0, dww, None, **dwk)
+
+        def pw():
+            st["y"], st["ys"] = ops.pwconv_i8(st["z"], codes, scales, rowsum, None, in_stat=st["zs"], **pwk)
+
+        def ds():
+            st["zs1"] = ops.dwconv3x3(y0, dww, None, store=False, x_codes_out=yc, **dwk)[1]
+
+        def pf():
+            st["y1"], st["ys1"] = ops.pwconv_i8(shape, codes, scales, rowsum, None, in_stat=st["zs1"],
+                                                front=dict(x_codes=yc, w=dww, bn_scale=scA, bn_shift=shA, act="relu", in_stat=s0), **pwk)
+        fns = [dw, pw, ds, pf]
+        for _ in range(3):
+            for f in fns:
+                f()
+        torch.cuda.synchronize()
+        ok = torch.equal(st["zs"], st["zs1"]) and torch.equal(st["ys"], st["ys1"]) and torch.equal(st["y"], st["y1"])
+        ts = [[] for _ in fns]
+        for _ in range(reps):                              # alternating: every repetition times each launch once
+            for i, f in enumerate(fns):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                f()
+                b.record()
+                b.synchronize()
+                ts[i].append(a.elapsed_time(b) * 1e3)
+        med = [float(np.median(t)) for t in ts]
+        sds = [float(np.std(t)) for t in ts]
+        zb, yb = 4e-6 * n * cin * hw * hw, 4e-6 * n * cout * hw * hw        # the depthwise input = its output, the 1x1 output, fp32
+        mb2, mb1 = 3 * zb + yb, zb + zb / 4 + zb / 4 + yb                  # (folded: without the halo rows of the bands)
+        print("%-14s %3d->%3d @%3dx%-3d   %6.1f + %6.1f = %6.1f (%4.2f TB/s)        %6.1f + %6.1f = %6.1f (%4.2f TB/s)          "
+              "%6.0f / %5.0f            %5.2fx  %s" % (name, cin, cout, hw, hw, med[0], med[1], med[0] + med[1],
+                                                    mb2 / (med[0] + med[1]), med[2], med[3], med[2] + med[3],
+                                                    mb1 / (med[2] + med[3]), mb2, mb1, (med[0] + med[1]) / (med[2] + med[3]),
+                                                    "bit-equal" if ok else "VALUES DIFFER"))
+        print("%-14s sd over the %d repetitions (us): dw %.2f  pw %.2f  dw-stat %.2f  pw with the front layer %.2f"
+              % ("", reps, sds[0], sds[1], sds[2], sds[3]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=128)
@@ -234,10 +304,14 @@ def main():
     ap.add_argument("--front", type=int, default=0)
     ap.add_argument("--chain", type=int, default=0)
     ap.add_argument("--sweep", type=int, default=0)
+    ap.add_argument("--front-store", type=int, default=0)
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
     n = a.batch
+    if a.front_store:
+        front_store_table(n, a.reps, dev)
+        return
     if a.front:
         front_table(n, a.reps, dev, bool(a.sweep))
         return
