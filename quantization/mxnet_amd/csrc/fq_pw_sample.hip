@@ -508,6 +508,8 @@ namespace fqi {
 //   planes of a multiple of 4 pixels that cut into blocks of 96..128 pixels (14x14: two, 28x28: seven), K / 32 in {4, 8, 16}, or
 //   whole planes of 45..64 pixels with 0 or 1 pixel past a multiple of four (7x7, 8x8), K / 32 in {16, 32, 64} (a residual operand: 16).
 // grid = samples x channel groups x pixel blocks (rounded to whole rounds over the 8 XCDs).
+// One sample of x and one of y below 2 GiB each: the resources are per sample (a wavefront's window on y and on the residual
+// operand runs to the end of the sample) and pixels past a block's end are masked with the lane offset 2^31.
 int pw_try_sample(const PwCall& a, bool* taken) {
   *taken = false;
   // 0 never, 1 blocked planes up to 1024 pixels without a residual operand (rounds 2-4), 2 every shape it takes (round 5)
@@ -521,7 +523,8 @@ int pw_try_sample(const PwCall& a, bool* taken) {
                                                                  (kt == 10 && a.gap && a.residual == nullptr)))
                               : (a.hw % 4 == 0 && quads / nb >= 24 && (kt == 4 || kt == 8 || kt == 16 || kt == 32));
   const bool shape_ok = plane_ok && a.stride == 1 && a.cin == a.cin_pad && a.cout % 256 == 0 &&
-                        a.n < (1 << 20) && a.cin * a.hw * 4 < (1ll << 31) && (small || aligned16(a.x)) &&
+                        a.n < (1 << 20) && a.cin * a.hw * 4 < (1ll << 31) && a.cout * a.hw * 4 < (1ll << 31) &&
+                        (small || aligned16(a.x)) &&
                         (small || a.residual == nullptr || aligned16(a.residual));    // (16-byte LDS-DMA of the residual operand)
   // by shape: the small and middle planes (measured in the model against the split form: 512 -> 512 @14x14 32.0 -> 25.2 us,
   // 256 -> 512 @14x14 24.0 -> 20.7, 256 -> 256 @28x28 48.0 -> 39.7, 128 -> 256 @28x28 38.8 -> 33.7); the streaming form keeps

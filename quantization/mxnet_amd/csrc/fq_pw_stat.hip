@@ -644,7 +644,11 @@ bool pw_stat_shape_ok(int64_t n, int64_t cin, int64_t cout, int64_t hw) {
   if (n <= 0 || cin <= 0 || cout <= 0 || hw < 32 || hw >= (1ll << 30) || n * hw >= (1ll << 31) - 512) return false;
   const int kt = (int)((cin + 31) / 32), ct = (int)((cout + 31) / 32);
   if (!(kt == 1 || kt == 2 || kt == 4 || kt == 8) || cin % 16 != 0) return false;
-  return pw_stat_lds(kt, ct) <= (size_t)kStatLdsMax && n * cin * hw * 4 < (1ll << 32);
+  // (the kernel's one resource spans all of x and its lane offsets are 32-bit: x below 4 GiB.  A half-slab past Cin - Cin % 32
+  // == 16 - is masked with the lane offset 2^31, which only lies outside a resource of at most 2 GiB: beyond, the masked lanes
+  // would load values of sample n / 2 and x_codes_out would carry their codes in its padding block)
+  const int64_t x_bytes = n * cin * hw * 4;
+  return pw_stat_lds(kt, ct) <= (size_t)kStatLdsMax && x_bytes < (1ll << 32) && (cin % 32 == 0 || x_bytes <= (1ll << 31));
 }
 
 // wavefronts per workgroup, rows per band and LDS of the front-layer mode: front_plan of fq_front_layout.h.

@@ -379,7 +379,11 @@ bool pw_stream_shape_ok(const PwCall& c) {
   const int ct = (int)((c.cout + 31) / 32);
   const size_t lds = (size_t)ct * kt * 1024 + (size_t)ct * 32 * 5 * sizeof(float);
   const bool kt_ok = kt == 1 || kt == 2 || kt == 3 || kt == 4 || kt == 6 || kt == 8;
-  return c.cin % 16 == 0 && c.cout % 32 == 0 && kt_ok && lds <= 72 * 1024;
+  // (lane_off / yoff of the kernel are 32-bit byte offsets from the tensors' bases: x and an fp32 y below 4 GiB - beyond, the
+  // split form, which re-bases its resources per workgroup, takes the shape.  A C16 code output is stored through 64-bit
+  // pointers: no bound on it)
+  return c.cin % 16 == 0 && c.cout % 32 == 0 && kt_ok && lds <= 72 * 1024 &&
+         (c.out_thr != nullptr || c.n * c.cout * c.hw * 4 < (1ll << 32)) && c.n * c.cin * c.hw * 4 < (1ll << 32);
 }
 
 // the thin instantiations (IN16 / PART): any Cin up to 192, any Cout (a multiple of 16 for a C16 output)
@@ -398,8 +402,12 @@ static bool pw_stream_thin_ok(const PwCall& c) {
   static const int both_wide = env_int("FQ_PWS_THIN_WIDE", 1);           // A/B: 0 leaves them to the split form
   const bool both = c.in_c16 && c.out_thr != nullptr;
   const bool wide = both && both_wide && (kt == 8 || kt == 16) && c.cin % 32 == 0 && c.cout % 32 == 0 && c.residual == nullptr;
+  // (a partial channel tile of an fp32 output - Cout % 32 != 0 - masks its stores and residual loads with the lane offset
+  // kOobOffset = 2^31 on a resource over the whole tensor: out of range only while that tensor is at most 2 GiB; beyond, the
+  // split form, whose windows are capped below 2 GiB, takes the shape)
+  const bool masks_ok = c.cout % 32 == 0 || c.out_thr != nullptr || c.n * c.cout * c.hw * 4 <= (1ll << 31);
   return thin && kt >= 1 && (kt <= 6 || wide) && lds <= 72 * 1024 && c.stride == 1 && (c.out_thr == nullptr || c.cout % 16 == 0) &&
-         !(both && kt != 1 && !wide) && !(c.out_thr != nullptr && c.residual != nullptr) &&
+         !(both && kt != 1 && !wide) && !(c.out_thr != nullptr && c.residual != nullptr) && masks_ok &&
          (c.n * c.hw + 31) / 32 > thin_min_tiles && c.n * c.cout * c.hw * 4 < (1ll << 32) && c.n * c.cin * c.hw * 4 < (1ll << 32);
 }
 
