@@ -470,6 +470,34 @@ int fq_pwconv_i8_front(const float* x, const int8_t* wcodes, const float* wscale
  * csrc/fq_common.h: fast_quot, or the fp64-reciprocal form when d[0] does not qualify; took_fast_path[0] says which) - must
  * equal the IEEE fp32 division bit for bit wherever a code depends on it (tests/test_gpu_pwdw.py).                         */
 int fq_debug_fast_quotient(const float* c, int64_t n, const float* d, float* out, int* took_fast_path, fqStream_t stream);
+/* Test hook (libraries from fq_version() 104 on): which instantiation of an int8 MFMA family the CALLING THREAD launched last.
+ * The note is written at the launch itself from the template arguments of the kernel that was launched; a call that is refused
+ * leaves it as it was.  No device work.  Returns the family (FQ_LAUNCH_*; FQ_LAUNCH_NONE before the first such launch of the
+ * thread), *kernel_id <- the FQ_KERNEL_* value of the launch (-1 before the first), vals[0 .. nvals) <- the family's values in
+ * the order below, -1 in the slots a family does not use (at most FQ_LAUNCH_VALS are kept):
+ *   FQ_LAUNCH_CONV3X3  fq_conv3x3_i8 / _sliced / _c16:  KT (Cin / 32), PTW (pixel tiles per wavefront), WC (channel tiles per
+ *                      workgroup), NW (wavefronts per workgroup), NSL (weight slices), IN16, OUT16 (C16 codes in / out)
+ *   FQ_LAUNCH_SPLIT    split form of fq_pwconv_i8 and its C16 / sub2 entry points:  KT, CW (channel tiles per wavefront), LB
+ *                      (wavefronts per SIMD), NW, bits (1 IN16 | 2 OUT16 | 4 second output | 8 subsampled)
+ *   FQ_LAUNCH_SAMPLE   sample form and fq_pwconv_i8_gap:  KT, CTW (channel tiles per wavefront), PT (pixel tiles per item), RES
+ *                      (residual operand), gap (pooling epilogue)
+ *   FQ_LAUNCH_SHORT    fq_pwconv_i8_shortcut / _c16:  KT, KT2 (shortcut operand), NW, bits (1 A16 | 2 B16 | 4 second output), nts
+ *                      (nontemporal stores)
+ *   FQ_LAUNCH_STREAM   streaming form:  KT, thin, RES, O16, I16, NT (1 nontemporal loads | 2 stores), dual (second output)
+ *   FQ_LAUNCH_STAT     fq_pwconv_i8_stat:  KT, waves, front (the front layer's epilogue kEpi*, -1 without a front layer), table (1
+ *                      the maxima through the LDS table, 0 straight to memory)
+ *   FQ_LAUNCH_PAIR     fq_pwdw_fused:  KT, CW, S (stride), LZ, FAST (compile-time epilogue), CODES (code input), NS (statistic
+ *                      mode), rb (rows per band)                                                                          */
+#define FQ_LAUNCH_NONE 0
+#define FQ_LAUNCH_CONV3X3 1
+#define FQ_LAUNCH_SPLIT 2
+#define FQ_LAUNCH_SAMPLE 3
+#define FQ_LAUNCH_SHORT 4
+#define FQ_LAUNCH_STREAM 5
+#define FQ_LAUNCH_STAT 6
+#define FQ_LAUNCH_PAIR 7
+#define FQ_LAUNCH_VALS 8
+int fq_debug_last_launch(int* kernel_id, int* vals, int nvals);
 int fq_pwdw_fused(const float* x, const int8_t* wcodes, const float* wscale, const int32_t* wsum, const float* pw_bias,
                   int64_t n, int64_t cin, int64_t cin_pad, int64_t cout_pad, int64_t cout, int64_t h, int64_t w,
                   const float* in_stat, const float* in_thr, int in_width, unsigned in_flags, const float* pw_bn_scale,

@@ -83,6 +83,7 @@ EXPORTS = {
     "fq_pwdw_fused": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _int, _uint, _vp,
                              _vp, _int, _vp, _vp, _int, _uint, _vp, _vp, _vp, _int, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp]),
     "fq_debug_fast_quotient": (_int, [_vp, _i64, _vp, _vp, _vp, _vp]),
+    "fq_debug_last_launch": (_int, [ctypes.POINTER(_int), ctypes.POINTER(_int), _int]),      # returns the family, not a status
     "fq_dense_i8_eval_workspace_bytes": (ctypes.c_size_t, [_i64, _i64]),
     "fq_dense_i8_eval": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _int, _uint, _vp, _vp, _vp,
                                 _vp, _vp, _vp]),
@@ -146,7 +147,7 @@ EXPORTS = {
 }
 
 # entry points that came after fq_version() 102, with the version that has them: an older library may lack these, and only these
-SINCE = {"fq_pwconv_i8_front_supported": 103, "fq_pwconv_i8_front": 103}
+SINCE = {"fq_pwconv_i8_front_supported": 103, "fq_pwconv_i8_front": 103, "fq_debug_last_launch": 104}
 
 FQ_ACT_SIGNED, FQ_ACT_LO_NEG_MAX, FQ_ACT_NO_ABS, FQ_ACT_NO_EPS = 1, 2, 4, 8
 FQ_CODES_INT8, FQ_CODES_UINT8, FQ_CODES_RANGE, FQ_CODES_SCALE = 0, 1, 2, 3

@@ -68,6 +68,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
 #include <vector>
 
@@ -83,6 +84,10 @@ int num_cu();                                       // compute units of the CURR
 int max_lds_bytes();                                // LDS a workgroup may ask for on the CURRENT device (cached per device)
 int env_int(const char* name, int dflt);
 int stream_policy(int kernel_id, int64_t numel);    // kPol* bits by kernel and tensor size
+// What the calling thread launched last (fq_debug_last_launch).  Written by the instantiation macros and launchers of the int8
+// MFMA families AT the launch and from the template arguments themselves, so that the note says what ran, not what the rule
+// above it planned.  family: FQ_LAUNCH_* of fakequant.h, where the meaning of the values is written per family.
+void note_launch(int kernel_id, int family, std::initializer_list<int> vals);
 
 struct ProfRec {
   int kid;

@@ -117,7 +117,7 @@ int conv3x3_launch(const float* x, const int8_t* wcodes, const float* wscale, co
   const int8_t* wfrag = wcodes + rows_pad * row_pad;                      // fragment-major copy (fq_weight_codes)
   // wavefront arrangement: four channel tiles per workgroup when the layer has them, else two and two pixel halves
   // eight wavefronts (256 channels per workgroup) for wide layers on small planes: half the channel groups
-  static const int nw_tune = env_int("FQ_C3_NW", 0);
+  const int nw_tune = env_int("FQ_C3_NW", 0);                              // tuning: 4 / 8, read per call
   // (measured in the ResNet-50 step: 256 @14x14 32.8 -> 28.6 us; 512 @7x7, where only 196 workgroups would remain, 34.1 -> 35.1)
   const bool nw8_fills = ((cols + 63) / 64) * ((cout + 255) / 256) >= (int64_t)num_cu();
   int nw = (nw_tune == 4 || nw_tune == 8) ? nw_tune : ((cout >= 256 && (kt == 8 || kt == 16) && nw8_fills) ? 8 : 4);
@@ -183,6 +183,7 @@ int conv3x3_launch(const float* x, const int8_t* wcodes, const float* wscale, co
                        x,                                                                                              \
                        wfrag, wscale, (const int*)wsum, bias, y, g, in_stat, (int)n, in_thr, levels, lo_neg, kEps,     \
                        out_current_max, bn_scale, bn_shift, act, stat_out, (const float*)nullptr);                     \
+    note_launch(FQ_KERNEL_CONV3X3, FQ_LAUNCH_CONV3X3, {KT_, PTW_, WC_, NW_, NSL_, 0, 0});                              \
     launched = true;                                                                                                   \
   }
 #define FQ_C3_CASE_NW(KT_, PTW_, WC_, D_, LB_, NW_) FQ_C3_CASE_NS(KT_, PTW_, WC_, D_, LB_, NW_, 1)

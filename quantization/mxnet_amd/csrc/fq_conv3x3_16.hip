@@ -20,6 +20,7 @@ int conv3x3_c16_launch(const float* x, const int8_t* wfrag, const float* wscale,
     hipLaunchKernelGGL((conv3x3_i8_kernel<KT_, PTW_, WC_, D_, 4, 4, 1, IN_, OUT_>), dim3((unsigned)grid), dim3(256), lds, st, \
                        x, wfrag, wscale, (const int*)wsum, bias, y, g, in_stat, n, in_thr, levels, lo_neg, kEps,       \
                        out_current_max, bn_scale, bn_shift, act, stat_out, out_thr);                                   \
+    note_launch(FQ_KERNEL_CONV3X3, FQ_LAUNCH_CONV3X3, {KT_, PTW_, WC_, 4, 1, IN_ ? 1 : 0, OUT_ ? 1 : 0});              \
     *launched = true;                                                                                                  \
   }
 #define FQ_C316_IO(KT_, PTW_, WC_, D_)                                                                                 \
@@ -40,6 +41,7 @@ int conv3x3_c16_launch(const float* x, const int8_t* wfrag, const float* wscale,
     hipLaunchKernelGGL((conv3x3_i8_kernel<KT_, PTW_, 8, D_, 4, 8, 1, true, true>), dim3((unsigned)grid), dim3(512), lds, st, \
                        x, wfrag, wscale, (const int*)wsum, bias, y, g, in_stat, n, in_thr, levels, lo_neg, kEps,       \
                        out_current_max, bn_scale, bn_shift, act, stat_out, out_thr);                                   \
+    note_launch(FQ_KERNEL_CONV3X3, FQ_LAUNCH_CONV3X3, {KT_, PTW_, 8, 8, 1, 1, 1});                                     \
     *launched = true;                                                                                                  \
   }
   FQ_C316_CASE8(8, 1, 6) FQ_C316_CASE8(8, 2, 4)

@@ -14,6 +14,22 @@ int fail(int code, const char* fmt, ...) {
   return code;
 }
 
+// ---- the note of the last launch (fq_debug_last_launch) ---------------------------------------------------------
+struct LaunchNote {
+  int kid = -1, family = FQ_LAUNCH_NONE;
+  int vals[FQ_LAUNCH_VALS];
+};
+thread_local LaunchNote g_note;
+
+void note_launch(int kernel_id, int family, std::initializer_list<int> vals) {
+  g_note.kid = kernel_id;
+  g_note.family = family;
+  int i = 0;
+  for (int v : vals)
+    if (i < FQ_LAUNCH_VALS) g_note.vals[i++] = v;
+  for (; i < FQ_LAUNCH_VALS; ++i) g_note.vals[i] = -1;
+}
+
 // ---- optional per-kernel event timing (fq_profile_*) -----------------------------------------------------------
 bool g_prof_on = false;
 std::mutex g_prof_mu;
@@ -92,7 +108,7 @@ using namespace fqi;
 extern "C" {
 
 const char* fq_last_error(void) { return g_err; }
-int fq_version(void) { return 103; }
+int fq_version(void) { return 104; }
 // sha1 of the sources this library was built from (csrc/build.py: source_id); "FQ_BUILD_ID=<40 hex>" is also what
 // build.py looks for in the file's bytes to decide whether a built library belongs to the tree it sits in
 #ifndef FQ_BUILD_ID
@@ -115,6 +131,12 @@ int fq_device_info(char* arch, int arch_len, int* compute_units, int* wavefront)
   if (compute_units) *compute_units = prop.multiProcessorCount;
   if (wavefront) *wavefront = prop.warpSize;
   return FQ_OK;
+}
+
+int fq_debug_last_launch(int* kernel_id, int* vals, int nvals) {
+  if (kernel_id != nullptr) *kernel_id = g_note.kid;
+  for (int i = 0; vals != nullptr && i < nvals; ++i) vals[i] = (i < FQ_LAUNCH_VALS && g_note.family != FQ_LAUNCH_NONE) ? g_note.vals[i] : -1;
+  return g_note.family;
 }
 
 int fq_profile_enable(int on) {

@@ -546,7 +546,7 @@ int pw_try_sample(const PwCall& a, bool* taken) {
   // split form's finer items win (MobileNet images/s +3.5 % at batch 8, equal at 16: profiles/r6_small_batch_forms_ab.txt)
   if (a.form != 7 && !a.gap && a.n * (a.cout / 256) * nb < num_cu() / 4) return FQ_OK;
   const int64_t rows_pad = (a.cout + 31) / 32 * 32;
-  static const int ctw_tune = env_int("FQ_PWSMP_CTW", 0);               // tuning: 1 = 256 channels per workgroup everywhere
+  const int ctw_tune = env_int("FQ_PWSMP_CTW", 0);                      // tuning: 1 = 256 channels per workgroup everywhere (read per call)
   // two channel tiles per wavefront (512 channels per workgroup, every value quantised once) from K = 512 up; below that
   // two workgroups of 256 channels per CU are faster (256 -> 512 @14x14: 20.1 -> 18.4 us; 512 -> 512: 25.2 against 25.7)
   // ... unless the 512-channel workgroups would be fewer than 3/8 of the CUs (batch 32 and below on the 14x14 and 7x7
@@ -589,6 +589,7 @@ int pw_try_sample(const PwCall& a, bool* taken) {
                        a.x, wfrag, a.wscale, (const int*)a.wsum, a.bias, a.y, t, a.in_stat, (int)a.n, a.in_thr,         \
                        a.levels, a.lo_neg, kEps, a.out_current_max, a.bn_scale, a.bn_shift, a.act, a.stat_out,          \
                        a.residual);                                                                                    \
+    note_launch(FQ_KERNEL_PWCONV, FQ_LAUNCH_SAMPLE, {KT_, CTW_, PT_, RES_ ? 1 : 0, 0});                                \
     launched = true;                                                                                                   \
   }
 #define FQ_PWSMP_CASE(KT_, CTW_, PT_) FQ_PWSMP_CASE_R(KT_, CTW_, PT_, false)
@@ -615,6 +616,7 @@ int pw_try_sample(const PwCall& a, bool* taken) {
                        (size_t)(256 * CTW_) * (size_t)a.hw * sizeof(float), a.st, a.x, wfrag, a.wscale, (const int*)a.wsum, \
                        a.bias, a.y, t, a.in_stat, (int)a.n, a.in_thr, a.levels, a.lo_neg, kEps, a.out_current_max,     \
                        a.bn_scale, a.bn_shift, a.act, a.stat_out, a.residual);                                         \
+    note_launch(FQ_KERNEL_PWCONV, FQ_LAUNCH_SAMPLE, {KT_, CTW_, 2, RES_ ? 1 : 0, 1});                                  \
     launched = true;                                                                                                   \
   }
   FQ_PWSMP_GAP(16, 1, false) FQ_PWSMP_GAP(16, 2, false) FQ_PWSMP_GAP(32, 1, false) FQ_PWSMP_GAP(32, 2, false)

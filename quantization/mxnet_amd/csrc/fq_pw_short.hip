@@ -305,7 +305,7 @@ int pw_short_launch(const PwCall& a, const PwCall& b) {
   const int64_t tiles = (a.n * a.hw + 31) / 32;
   FQ_REQUIRE((32 / a.hw + 2) * a.cout * a.hw * 4 < (1ll << 31) && (32 / a.hw + 2) * b.cin * a.hw * 4 < (1ll << 31),
              "fq_pwconv_i8_shortcut: a tile must stay within 2 GiB of its first sample");
-  static const int nw_tune = env_int("FQ_PWSH_NW", 0);                   // tuning: 4 / 8 wavefronts per workgroup
+  const int nw_tune = env_int("FQ_PWSH_NW", 0);                          // tuning: 4 / 8 wavefronts per workgroup (read per call)
   const int nw = (nw_tune == 4 || nw_tune == 8) ? (a.cout % 512 == 0 ? nw_tune : 4) : (a.cout % 512 == 0 && kt >= 4 ? 8 : 4);
   PwShortGeom t;
   t.Cin = (int)a.cin; t.Cin2 = (int)b.cin; t.Cout = (int)a.cout; t.HW = (int)a.hw;
@@ -316,7 +316,7 @@ int pw_short_launch(const PwCall& a, const PwCall& b) {
   t.CBi = (int)((a.cin + 15) / 16); t.CBi2 = (int)((b.cin + 15) / 16); t.CBo = (int)((a.cout + 15) / 16);
   t.out_levels = a.out_levels; t.out_lo_neg = a.out_lo_neg; t.out_zoff = a.out_zoff;
   t.y16 = (char*)a.y16; t.dual_thr = a.dual_thr;
-  static const int nts_mb = env_int("FQ_PWSH_NTS_MB", 150);              // (the streaming form's policy, FQ_PWS_NTS_MB)
+  const int nts_mb = env_int("FQ_PWSH_NTS_MB", 150);                     // (the streaming form's policy, FQ_PWS_NTS_MB; read per call)
   t.nts = 4e-6 * (double)a.n * a.cout * a.hw >= nts_mb ? 1 : 0;
   const bool a16 = a.in_c16, b16 = b.in_c16, dual = a.y16 != nullptr;
   FQ_REQUIRE((!a16 && !b16 && !dual) || (a16 && dual), "fq_pwconv_i8_shortcut_c16: built for fp32 on every side, or for codes in + "
@@ -344,6 +344,7 @@ int pw_short_launch(const PwCall& a, const PwCall& b) {
     hipLaunchKernelGGL((pwconv_short_kernel<KT_, KT2_, NW_, A_, B_, D_>), dim3((unsigned)grid), dim3(NW_ * 64), lds, a.st, a.x, wfrag, \
                        a.wscale, (const int*)a.wsum, a.bias, a.y, t, a.in_stat, (int)a.n, a.in_thr, a.levels, a.lo_neg, \
                        kEps, a.out_current_max, a.bn_scale, a.bn_shift, a.act, a.stat_out, s2);                        \
+    note_launch(FQ_KERNEL_PWCONV, FQ_LAUNCH_SHORT, {KT_, KT2_, NW_, (A_ ? 1 : 0) | (B_ ? 2 : 0) | (D_ ? 4 : 0), t.nts}); \
     launched = true;                                                                                                   \
   }
   FQ_PWSH_CASE(2, 2, 4) FQ_PWSH_CASE(4, 8, 4) FQ_PWSH_CASE(8, 16, 4) FQ_PWSH_CASE(4, 8, 8) FQ_PWSH_CASE(8, 16, 8)

@@ -45,14 +45,14 @@ int pw_try_split(const PwCall& a, bool* taken) {
     // tiles get 5 % slower that way (round 3: hence "few tiles only"); among three batches in flight what counts is the work
     // saved: ResNet-50 online +0.75 % with the limit at 1024 tiles, +1.2 % at 4096 = 16 tiles per CU (28x28 planes included),
     // +1.1 % without limit (round 5, alternating runs: profiles/r5_r50_nw8_ab.txt)
-    static const int nw_tune = env_int("FQ_PWS_NW", 0);
+    const int nw_tune = env_int("FQ_PWS_NW", 0);                        // tuning: 4 / 8 (this and the next two: read per call)
     const bool nw8_built = kt == 8 || kt == 16 || kt == 32 || kt == 64;
-    static const int nw8_tiles = env_int("FQ_PWS_NW8_TILES", 0);        // tuning: most tiles a layer may have to take nw = 8
+    const int nw8_tiles = env_int("FQ_PWS_NW8_TILES", 0);        // tuning: most tiles a layer may have to take nw = 8
     const int64_t nw8_max = nw8_tiles > 0 ? nw8_tiles : 16 * (int64_t)num_cu();
     int nw = (nw_tune == 4 || nw_tune == 8) ? nw_tune : ((a.cout >= 512 && tiles <= nw8_max) ? 8 : 4);
     // (C16 code tensors: four wavefronts - except the dual form of the 14x14 / 7x7 stages, K = 256 / 512, round 6: eight, i.e. 512
     // channels per workgroup and half as many workgroups copying the same tile's codes - FQ_PWS16_DUAL_NW8=0 for the A/B)
-    static const int dual_nw8 = env_int("FQ_PWS16_DUAL_NW8", 1);
+    const int dual_nw8 = env_int("FQ_PWS16_DUAL_NW8", 1);
     const bool dual8 = c16 && a.y16 != nullptr && !a.sub && dual_nw8 && (kt == 8 || kt == 16) && a.cout >= 512 && tiles <= nw8_max;
     if (!nw8_built || (c16 && !dual8) || a.sub) nw = 4;
     if (dual8) nw = 8;
@@ -107,6 +107,7 @@ int pw_try_split(const PwCall& a, bool* taken) {
                        wfrag, a.wscale, (const int*)a.wsum, a.bias, a.y, t, a.in_stat, (int)a.n, a.in_thr, a.levels,   \
                        a.lo_neg, kEps, a.out_current_max, a.bn_scale, a.bn_shift, a.act, a.stat_out, a.residual,       \
                        (const float*)nullptr);                                                                         \
+    note_launch(FQ_KERNEL_PWCONV, FQ_LAUNCH_SPLIT, {KT_, CW_, LB_, NW_, 0});                                           \
     launched = true;                                                                                                   \
   }
 #define FQ_PWS_CASE(KT_, CW_, D_, LB_) FQ_PWS_CASE_NW(KT_, CW_, D_, LB_, 4)

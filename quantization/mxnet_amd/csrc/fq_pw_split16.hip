@@ -25,6 +25,8 @@ int pw_split16_launch(const PwCall& a, const void* geom, int kt, int cw, int64_t
                        a.x, wfrag, a.wscale, (const int*)a.wsum, a.bias, a.y, t, a.in_stat, (int)a.n, a.in_thr, a.levels, \
                        a.lo_neg, kEps, a.out_current_max, a.bn_scale, a.bn_shift, a.act, a.stat_out, a.residual,       \
                        a.out_thr);                                                                                     \
+    note_launch(FQ_KERNEL_PWCONV, FQ_LAUNCH_SPLIT,                                                                     \
+                {KT_, CW_, LB_, 4, (IN_ ? 1 : 0) | (OUT_ ? 2 : 0) | (DUAL_ ? 4 : 0) | (SUB_ ? 8 : 0)});                \
     *launched = true;                                                                                                  \
   }
 #define FQ_PWS16_KT(KT_)                                                                                               \
@@ -58,6 +60,7 @@ int pw_split16_launch(const PwCall& a, const void* geom, int kt, int cw, int64_t
                        dim3(512), lds, a.st, a.x, wfrag, a.wscale, (const int*)a.wsum, a.bias, a.y, t, a.in_stat, (int)a.n, \
                        a.in_thr, a.levels, a.lo_neg, kEps, a.out_current_max, a.bn_scale, a.bn_shift, a.act, a.stat_out, \
                        a.residual, a.out_thr);                                                                         \
+    note_launch(FQ_KERNEL_PWCONV, FQ_LAUNCH_SPLIT, {KT_, 2, kDualLB, 8, 1 | 4});                                       \
     *launched = true;                                                                                                  \
   }
   FQ_PWS16_DUAL8(8) FQ_PWS16_DUAL8(16)

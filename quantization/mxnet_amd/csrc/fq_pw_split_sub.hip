@@ -25,6 +25,7 @@ int pw_split_sub_launch(const PwCall& a, const void* geom, int kt, int64_t grid,
                        a.st, a.x, wfrag, a.wscale, (const int*)a.wsum, a.bias, a.y, t, a.in_stat, (int)a.n, a.in_thr,   \
                        a.levels, a.lo_neg, kEps, a.out_current_max, a.bn_scale, a.bn_shift, a.act, a.stat_out,         \
                        a.residual, (const float*)nullptr);                                                             \
+    note_launch(FQ_KERNEL_PWCONV, FQ_LAUNCH_SPLIT, {KT_, 2, 4, 4, 8});                                                 \
     *launched = true;                                                                                                  \
   }
   FQ_PWSUB_CASE(2, 2) FQ_PWSUB_CASE(4, 3) FQ_PWSUB_CASE(8, 3) FQ_PWSUB_CASE(16, 3)

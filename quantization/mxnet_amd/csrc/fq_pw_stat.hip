@@ -679,6 +679,7 @@ static int pw_stat_go(const PwCall& c, const PwStatGeom& g, const PwFrontArgs& f
   hipLaunchKernelGGL((pw_stat_kernel<KT, FEPI, FSIGNED, NW>), dim3((unsigned)grid), dim3(64 * NW), lds, c.st, c.x, c.wcodes,
                      c.wscale, (const int*)c.wsum, c.bias, g, c.in_stat, (int)c.n, c.in_thr, c.levels, c.lo_neg, kEps,
                      c.out_current_max, c.bn_scale, c.bn_shift, c.act, c.stat_out, (int8_t*)c.x_codes_out, fa);
+  note_launch(FQ_KERNEL_PWCONV, FQ_LAUNCH_STAT, {KT, NW, FEPI, g.table});
   return FQ_OK;
 }
 
@@ -712,7 +713,7 @@ int pw_stat_launch(const PwCall& c) {
   int64_t grid = (int64_t)num_cu() * per_cu;
   const int64_t need = c.front != nullptr ? c.n * fa.bands : (g.tiles + 3) / 4;
   if (grid > need) grid = need;
-  static const int table_env = env_int("FQ_PWSTAT_TABLE", -1);
+  const int table_env = env_int("FQ_PWSTAT_TABLE", -1);                 // tuning: 0 / 1, read per call
   g.table = table_env >= 0 ? table_env : (g.tiles < grid * waves * 10 ? 1 : 0);
   int rc = FQ_OK;
   if (c.front != nullptr) {

@@ -394,7 +394,7 @@ static bool pw_stream_thin_ok(const PwCall& c) {
   static const int thin = env_int("FQ_PWS_THIN", 1);                    // A/B: 0 leaves these shapes to the split form
   // (r4: 3000 instead of 4096 - the 28 x 28 planes of a batch of 128 are 3136 tiles: MobileNetV2 W4 offline 144.8 -> 146.9 k
   // images/s, ResNet-50 offline unchanged; 1500 / 700 add nothing, profiles/r4_thin_tiles_ab.txt)
-  static const int thin_min_tiles = env_int("FQ_PWS_THIN_MIN_TILES", 3000);
+  const int thin_min_tiles = env_int("FQ_PWS_THIN_MIN_TILES", 3000);    // (read per call)
   // (codes in AND codes out: K = 32 - MobileNetV2's first 1x1 behind a first convolution that hands its codes over - and, round 6,
   // K = 256 / 512: the first 1x1 of ResNet-50's units on the 56x56 and 28x28 planes, which the split form ran as 12 544 / 3 136
   // one-tile workgroups at 2.2 / 2.0 TB/s of their 1-byte-per-element traffic: ResNet-50 offline +2.4 % images/s,
@@ -466,7 +466,8 @@ int pw_try_stream(const PwCall& c, bool* taken) {
   // keep (the 50-100 MB tensors of the middle layers) is then still there.  Measured with three batches in flight, 18 runs
   // alternating in three calls: +1.6 ... +3.0 % images/s (profiles/r5_pws_nt_ab.txt, r5_pws_nt_sweep.txt, r5_nt_sweep2.txt; a
   // box wanders by +-3 % between runs, and the kernels timed ALONE do not show it: the gain is what the OTHER launches find).
-  static const int ntl_mb = env_int("FQ_PWS_NTL_MB", 0), nts_mb = env_int("FQ_PWS_NTS_MB", 150);
+  static const int ntl_mb = env_int("FQ_PWS_NTL_MB", 0);
+  const int nts_mb = env_int("FQ_PWS_NTS_MB", 150);                     // (read per call)
   const double in_mb = 4e-6 * (double)c.n * c.cin * c.hw, out_mb = 4e-6 * (double)c.n * c.cout * c.hw;
   const int nt = (in_mb >= ntl_mb ? 1 : 0) | (out_mb >= nts_mb ? 2 : 0);
 #define FQ_PWS_LAUNCH(KT_, RES_, O16_)                                                                                 \
@@ -478,6 +479,7 @@ int pw_try_stream(const PwCall& c, bool* taken) {
                        c.wcodes, c.wscale, (const int*)c.wsum, c.bias, c.y, s, c.in_stat, (int)c.n, c.in_thr, c.levels, \
                        c.lo_neg, kEps, c.out_current_max, c.bn_scale, c.bn_shift, c.act, c.stat_out, c.residual,       \
                        c.out_thr);                                                                                     \
+    note_launch(FQ_KERNEL_PWCONV, FQ_LAUNCH_STREAM, {KT_, 0, RES_ ? 1 : 0, O16_ ? 1 : 0, 0, 0, 0});                    \
   }
 #define FQ_PWS_LAUNCH_NT(KT_, NT_) FQ_PWS_LAUNCH_NT_R(KT_, false, NT_)
 #define FQ_PWS_LAUNCH_NT_R(KT_, RES_, NT_)                                                                             \
@@ -490,6 +492,7 @@ int pw_try_stream(const PwCall& c, bool* taken) {
                        dim3(kBlock), lds, c.st, c.x, c.wcodes, c.wscale, (const int*)c.wsum, c.bias, c.y, s, c.in_stat, \
                        (int)c.n, c.in_thr, c.levels, c.lo_neg, kEps, c.out_current_max, c.bn_scale, c.bn_shift, c.act,  \
                        c.stat_out, c.residual, c.out_thr);                                                             \
+    note_launch(FQ_KERNEL_PWCONV, FQ_LAUNCH_STREAM, {KT_, 0, RES_ ? 1 : 0, 0, 0, NT_, 0});                             \
   }
 #define FQ_PWS_CASE(KT_)                                                                                               \
   case KT_:                                                                                                            \
@@ -509,6 +512,7 @@ int pw_try_stream(const PwCall& c, bool* taken) {
                        c.st, c.x, c.wcodes, c.wscale, (const int*)c.wsum, c.bias, c.y, s, c.in_stat, (int)c.n, c.in_thr, \
                        c.levels, c.lo_neg, kEps, c.out_current_max, c.bn_scale, c.bn_shift, c.act, c.stat_out,         \
                        c.residual, c.out_thr);                                                                         \
+    note_launch(FQ_KERNEL_PWCONV, FQ_LAUNCH_STREAM, {KT_, 1, RES_ ? 1 : 0, O16_ ? 1 : 0, I16_ ? 1 : 0, 0, 0});         \
   }
 #define FQ_PWS_THIN_DUAL(KT_)                                                                                          \
   {                                                                                                                    \
@@ -520,6 +524,7 @@ int pw_try_stream(const PwCall& c, bool* taken) {
                        c.st, c.x, c.wcodes, c.wscale, (const int*)c.wsum, c.bias, c.y, s, c.in_stat, (int)c.n, c.in_thr, \
                        c.levels, c.lo_neg, kEps, c.out_current_max, c.bn_scale, c.bn_shift, c.act, c.stat_out,         \
                        c.residual, c.out_thr);                                                                         \
+    note_launch(FQ_KERNEL_PWCONV, FQ_LAUNCH_STREAM, {KT_, 1, 1, 0, 1, 0, 1});                                          \
   }
 #define FQ_PWS_THIN_CASE(KT_)                                                                                          \
   case KT_:                                                                                                            \

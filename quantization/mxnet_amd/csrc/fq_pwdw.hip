@@ -610,11 +610,12 @@ int fq_pwdw_fused_supported(int64_t n, int64_t cin, int64_t cout, int64_t h, int
 
 // one instantiation's launch: it owns the raised dynamic LDS limit; `args` are pwdw_kernel's, written out by the one caller
 template <int KT, int CW, int S, int LZ, int FAST, int CODES, int NS, class... Args>
-static int pwdw_go(unsigned grid, int threads, size_t lds, hipStream_t st, Args... args) {
+static int pwdw_go(unsigned grid, int threads, size_t lds, hipStream_t st, int rb, Args... args) {
   static const bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&pwdw_kernel<KT, CW, S, LZ, FAST, CODES, NS>),
                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) == hipSuccess;
   FQ_REQUIRE(attr_ok, "fq_pwdw_fused: cannot raise the dynamic LDS limit");
   hipLaunchKernelGGL((pwdw_kernel<KT, CW, S, LZ, FAST, CODES, NS>), dim3(grid), dim3((unsigned)threads), lds, st, args...);
+  note_launch(FQ_KERNEL_DWCONV, FQ_LAUNCH_PAIR, {KT, CW, S, LZ, FAST, CODES, NS, rb});
   return FQ_OK;
 }
 
@@ -704,7 +705,7 @@ extern "C" int fq_pwdw_fused(const float* x, const int8_t* wcodes, const float* 
                               NS = decltype(ns_c)::value;
                 if constexpr ((S == 1 || LZ == 0) && (NS == 0 || (S == 1 && CODES == 1)))
                   rc = pwdw_go<KT, CW, S, LZ, FAST, CODES, NS>(
-                      grid, p.threads, lds, st, x, xc, wfrag, wscale, (const int*)wsum, pw_bias, g, in_stat, (int)n, in_thr,
+                      grid, p.threads, lds, st, p.rb, x, xc, wfrag, wscale, (const int*)wsum, pw_bias, g, in_stat, (int)n, in_thr,
                       levels1, lo1, kEps, pw_bn_scale, pw_bn_shift, pw_act, mid_stat, mid_thr, levels2, lo2, mid_current_max,
                       dw_w, dw_bias, dw_bn_scale, dw_bn_shift, dw_act, y_arg, stat_out);
               });

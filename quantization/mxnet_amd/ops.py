@@ -102,6 +102,31 @@ KERNEL_IDS = {"stat": 0, "apply_online": 1, "apply_offline": 2, "weight": 3, "hi
               "dwconv": 6, "pwconv": 7, "stem": 8, "pool": 9, "global_max": 10, "conv3x3": 11, "dense": 12}
 
 
+# fq_debug_last_launch: family (FQ_LAUNCH_* of include/fakequant.h) -> (name, the names of its values in order)
+LAUNCH_FAMILIES = {
+    1: ("conv3x3", ("KT", "PTW", "WC", "NW", "NSL", "IN16", "OUT16")),
+    2: ("split", ("KT", "CW", "LB", "NW", "bits")),
+    3: ("sample", ("KT", "CTW", "PT", "RES", "gap")),
+    4: ("short", ("KT", "KT2", "NW", "bits", "nts")),
+    5: ("stream", ("KT", "thin", "RES", "O16", "I16", "NT", "dual")),
+    6: ("stat", ("KT", "waves", "front", "table")),
+    7: ("pair", ("KT", "CW", "S", "LZ", "FAST", "CODES", "NS", "rb")),
+}
+
+
+def last_launch():
+    """Which instantiation of an int8 MFMA family this thread launched last: `(family name, value, ...)` with the values in the
+    order of LAUNCH_FAMILIES (include/fakequant.h: fq_debug_last_launch), or None before the first such launch.  Written by the
+    library at the launch from the kernel's template arguments; a refused call leaves it unchanged.  No device work."""
+    kid = ctypes.c_int(-1)
+    vals = (ctypes.c_int * 8)()
+    family = _lib_().fq_debug_last_launch(ctypes.byref(kid), vals, 8)
+    if family == 0:
+        return None
+    name, fields = LAUNCH_FAMILIES[family]
+    return (name,) + tuple(vals[:len(fields)])
+
+
 def profile_enable(on=True):
     """Bracket every streaming-kernel launch with HIP events on its launch stream (include/fakequant.h)."""
     check_call(_lib_().fq_profile_enable(1 if on else 0))

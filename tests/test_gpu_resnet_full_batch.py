@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import test_gpu_launch_plans as LP
 import test_gpu_shortcut as S
 import test_gpu_sub2 as B
 
@@ -193,8 +194,21 @@ def _np(t):
     return t.detach().cpu().numpy()
 
 
+def _launched(ops, note):
+    """What a full-size layer runs is an instantiation the small ragged shapes of tests/test_gpu_launch_plans.py pin - and, on the
+    256 compute units the rules were derived for below, it is the one the launch just left its note of."""
+    assert note in LP.INSTANTIATIONS[note[0]], "%s is not in the list of tests/test_gpu_launch_plans.py" % (note,)
+    if ops.device_info()["compute_units"] == 256:
+        assert ops.last_launch() == note, (ops.last_launch(), note)
+
+
 # (n, c, h, w): the 3x3 of every stage (c -> c)
 C3 = [(128, 64, 56, 56), (128, 128, 28, 28), (128, 256, 14, 14), (128, 512, 7, 7)]
+# (NW, WC, PTW) on 256 compute units (fq_conv3x3.hip).  WC: two channel tiles for 64 channels, else four; eight wavefronts (WC = 8) where
+# ceil(pixels / 64) * ceil(c / 256) >= 256 and K / 32 is 8 or 16: 6272 * 1, 1568 * 1 (K / 32 = 2, 4: never), 392 * 1 (yes), 98 * 2 = 196
+# (no).  PTW = 2 while ceil(pixels / (64 * NW / WC)) * ceil(c / (32 * WC)) >= 256: 3136 * 1, 1568 * 1, 392 * 1, 98 * 4 = 392 - all four.
+# The sliced form is built for eight wavefronts at K / 32 = 8, i.e. on the same layer.
+C3_PLANS = {64: (4, 2, 2), 128: (4, 4, 2), 256: (8, 8, 2), 512: (4, 4, 2)}
 
 
 @pytest.mark.parametrize("case", C3, ids=["%dx%d@%dx%d" % c for c in C3])
@@ -222,6 +236,8 @@ def test_dense3x3_at_batch_128_against_the_host_twin(dev, ops, case, sliced):
     y, ystat = ops.conv3x3_i8(x, *codes, cur_out=cur, **kw)
     y2, ystat2 = ops.conv3x3_i8(x, *codes, cur_out=torch.zeros(1, device=dev), **kw)
     assert torch.equal(y, y2) and torch.equal(ystat, ystat2), "repeats differ"
+    nw, wc, ptw = C3_PLANS[c]
+    _launched(ops, LP.c3(c // 32, ptw, wc, nw, 3 if sliced else 1))
     twin = H.conv3x3_i8_sliced if sliced else (lambda *a, **k: H.conv3x3_i8(a[0], a[1], 1, 8, **k))
     want, wstat = twin(_np(x), _np(wt), in_stat=_np(stat), bn_scale=_np(sc), bn_shift=_np(sh), act="relu", want_stat=True)
     S._eq(_np(y), want, "output")
@@ -234,6 +250,19 @@ def test_dense3x3_at_batch_128_against_the_host_twin(dev, ops, case, sliced):
 PW = [(128, 256, 64, 56, 56, 1, False), (128, 512, 128, 28, 28, 1, False), (128, 1024, 256, 14, 14, 1, False),
       (128, 2048, 512, 7, 7, 1, False), (128, 256, 128, 56, 56, 2, False), (128, 64, 256, 56, 56, 1, True),
       (128, 128, 512, 28, 28, 1, True), (128, 256, 1024, 14, 14, 1, True), (128, 512, 2048, 7, 7, 1, True)]
+# What fq_pwconv_i8's shape-based choice takes on 256 compute units, in the order of PW (tiles = pixels / 32):
+#   256 -> 64 @56x56: 12 544 tiles > 16 * 256, no sample form (Cout % 256), the weights fit LDS: streaming form, K / 32 = 8, input
+#     411 MB (nontemporal loads: always), output 103 MB < 150 (plain stores): NT = 1
+#   512 -> 128 @28x28: 3136 tiles <= 4096: split form, K / 32 = 16, Cout <= 128: one channel tile per wavefront, four wavefronts
+#   1024 -> 256 @14x14: sample form (two blocks of 24 / 25 pixel groups, K / 32 = 32; 128 * 1 * 2 workgroups >= 64), Cout % 512 != 0:
+#     256 channels per workgroup, four pixel tiles
+#   2048 -> 512 @7x7: sample form on whole planes (two pixel tiles), K / 32 = 64; 128 workgroups of 512 channels >= 96: CTW = 2
+#   256 -> 128 stride 2: only the split form reads strided inputs; K / 32 = 8, Cout <= 128: one tile per wavefront
+#   64 -> 256 @56x56 + residual: K / 32 = 2 is no sample form; more than 4096 tiles, but a residual operand with Cin <= 64 goes to
+#     the split form (FQ_PWS_RES_SPLIT): two tiles per wavefront (Cout > 128), four wavefronts (Cout < 512)
+#   the other closing 1x1 (K / 32 = 4, 8 on blocked planes, 16 on whole 7x7 planes): sample form, a residual operand takes CTW = 2
+PW_PLANS = [LP.stream(8, 0, nt=1), LP.split(16, 1, 4, 4), LP.sample(32, 1, 4), LP.sample(64, 2, 2), LP.split(8, 1, 4, 4),
+            LP.split(2, 2, 4, 4), LP.sample(4, 2, 4, 1), LP.sample(8, 2, 4, 1), LP.sample(16, 2, 2, 1)]
 
 
 @pytest.mark.parametrize("case", PW, ids=["%dx%d->%d@%dx%d-s%d%s" % (c[:6] + ("-res" if c[6] else "",)) for c in PW])
@@ -257,6 +286,7 @@ def test_pointwise_at_batch_128_against_the_host_twin(dev, ops, case):
     y, ystat = ops.pwconv_i8(x, *codes, None, cur_out=cur, **kw)
     y2, ystat2 = ops.pwconv_i8(x, *codes, None, cur_out=torch.zeros(1, device=dev), **kw)
     assert torch.equal(y, y2) and torch.equal(ystat, ystat2), "repeats differ"
+    _launched(ops, PW_PLANS[PW.index(case)])
     want, wstat = H.pwconv_i8(_np(x), _np(wt), 1, 8, in_stat=_np(stat), bn_scale=_np(sc), bn_shift=_np(sh), act="relu",
                               want_stat=True, stride=stride, residual=None if r is None else _np(r))
     S._eq(_np(y), want, "output")
