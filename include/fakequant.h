@@ -71,7 +71,8 @@ int fq_device_info(char* arch, int arch_len, int* compute_units, int* wavefront)
 #define FQ_KERNEL_GLOBAL_MAX 10   /* minmax_kernel (calibration)   : 4 B/elem                                       */
 #define FQ_KERNEL_CONV3X3 11      /* conv3x3_i8_kernel             : 4 B/in elem + 4 B/out elem                     */
 #define FQ_KERNEL_DENSE 12        /* pwconv_rows_kernel (the classifier on the codes: planes of one pixel; latency-bound)  */
-#define FQ_KERNEL_COUNT 13
+#define FQ_KERNEL_GCONV3X3 13     /* gconv3x3_i8_kernel            : 4 B/in elem + 4 B/out elem                     */
+#define FQ_KERNEL_COUNT 14
 int fq_profile_enable(int on);
 int fq_profile_reset(void);
 int fq_profile_read(int kernel_id, double* total_ms, int64_t* launches, double* total_bytes);
@@ -487,7 +488,9 @@ int fq_debug_fast_quotient(const float* c, int64_t n, const float* d, float* out
  *   FQ_LAUNCH_STAT     fq_pwconv_i8_stat:  KT, waves, front (the front layer's epilogue kEpi*, -1 without a front layer), table (1
  *                      the maxima through the LDS table, 0 straight to memory)
  *   FQ_LAUNCH_PAIR     fq_pwdw_fused:  KT, CW, S (stride), LZ, FAST (compile-time epilogue), CODES (code input), NS (statistic
- *                      mode), rb (rows per band)                                                                          */
+ *                      mode), rb (rows per band)
+ *   FQ_LAUNCH_GCONV3X3 fq_gconv3x3_i8 (libraries from fq_version() 105 on):  WC (slabs of 32 channels per workgroup), PTW (pixel
+ *                      tiles per wavefront), NB (pixel blocks a workgroup walks), CG (channels per group)                  */
 #define FQ_LAUNCH_NONE 0
 #define FQ_LAUNCH_CONV3X3 1
 #define FQ_LAUNCH_SPLIT 2
@@ -496,6 +499,7 @@ int fq_debug_fast_quotient(const float* c, int64_t n, const float* d, float* out
 #define FQ_LAUNCH_STREAM 5
 #define FQ_LAUNCH_STAT 6
 #define FQ_LAUNCH_PAIR 7
+#define FQ_LAUNCH_GCONV3X3 8
 #define FQ_LAUNCH_VALS 8
 int fq_debug_last_launch(int* kernel_id, int* vals, int nvals);
 int fq_pwdw_fused(const float* x, const int8_t* wcodes, const float* wscale, const int32_t* wsum, const float* pw_bias,
@@ -562,6 +566,22 @@ int fq_conv3x3_i8(const float* x, const int8_t* wcodes, const float* wscale, con
                   float* y, int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w, const float* in_stat,
                   const float* in_thr, int in_width, unsigned in_flags, float* out_current_max, const float* bn_scale,
                   const float* bn_shift, int act, float* stat_out, fqStream_t stream);
+
+/* GROUPED 3x3 convolution (stride 1, padding 1, no dilation) on the integer codes - the 3x3 layers of the ResNeXt bottlenecks
+ * (libraries from fq_version() 105 on).  cin == cout == c, c % 32 == 0, groups > 1 and c / groups in {4, 8, 16, 32}
+ * (fq_gconv3x3_i8_supported; any other shape is refused), w <= FQ_GCONV3X3_MAX_W.  Same contract as fq_conv3x3_i8: quantise on
+ * load from in_stat / in_thr, exact int32 sums, one fp32 multiply by sx * wscale[co], bias / folded BatchNorm / activation /
+ * per-sample statistic on store, FQ_STAT_PREZEROED; fp32 NCHW on both sides.
+ * wcodes / wscale / wsum: what fq_weight_codes writes for the filter EXPANDED to (c, 3, 3, 32): with cg = c / groups, row co
+ * holds the cg codes of tap (ky, kx) at [ky][kx][((co % 32) / cg) * cg + j] and zeros elsewhere - rows = c, row_len = 288,
+ * row_pad = 320, rows_pad = c rounded up to 64 - with rows_per_scale = c (one scale), cg (one per group) or 1 (per channel):
+ * zeros change neither a scale nor a row sum.  An output tile of 32 channels then multiplies with ITS 32 input channels only. */
+#define FQ_GCONV3X3_MAX_W 384
+int fq_gconv3x3_i8_supported(int64_t cin, int64_t cout, int64_t groups);
+int fq_gconv3x3_i8(const float* x, const int8_t* wcodes, const float* wscale, const int32_t* wsum, const float* bias,
+                   float* y, int64_t n, int64_t c, int64_t groups, int64_t h, int64_t w, const float* in_stat,
+                   const float* in_thr, int in_width, unsigned in_flags, float* out_current_max, const float* bn_scale,
+                   const float* bn_shift, int act, float* stat_out, fqStream_t stream);
 
 /* fq_conv3x3_i8 with C16 code tensors on either side or both (see fq_pwconv_i8_c16): the 3x3 convolution in the middle
  * of a ResNet bottleneck takes the codes its 1x1 predecessor wrote and writes the codes its 1x1 successor reads.            */

@@ -238,6 +238,68 @@ int fq_pwconv_i8_front_host(const float* front_x, float* z, float* front_stat_ou
                            bn_scale, bn_shift, act, stat_out, 0, stream);
 }
 
+/* The grouped 3x3 convolution on the codes (fq_gconv3x3_i8), restated plainly: codes of x by clip -> IEEE divide -> roundf, the
+ * int32 sum of every output channel over its own group's taps read from the EXPANDED code rows (wcodes: rows of 320 bytes, tap
+ * t's 32 slab positions at [32 t, 32 t + 32)), one fp32 multiply by sx * wscale[co], bias, BatchNorm, activation, statistic.
+ * DEFINED here like the pair above (the one unit that includes this header exports them).                                     */
+int fq_gconv3x3_i8_supported_host(int64_t cin, int64_t cout, int64_t groups) {
+  if (cin != cout || cin <= 0 || cin % 32 != 0 || groups <= 1 || cin % groups != 0) return 0;
+  return cin / groups == 4 || cin / groups == 8 || cin / groups == 16 || cin / groups == 32 ? 1 : 0;
+}
+int fq_gconv3x3_i8_host(const float* x, const int8_t* wcodes, const float* wscale, const int32_t* wsum, const float* bias,
+                        float* y, int64_t n, int64_t c, int64_t groups, int64_t h, int64_t w, const float* in_stat,
+                        const float* in_thr, int in_width, unsigned in_flags, float* out_current_max, const float* bn_scale,
+                        const float* bn_shift, int act, float* stat_out, fqStream_t stream) {
+  (void)wsum;
+  if (!x || !wcodes || !wscale || !y || !fq_gconv3x3_i8_supported_host(c, c, groups) || (!in_stat && !in_thr)) return 1;
+  float mean = 0.0f;
+  if (in_stat != 0) {
+    int rc = fq_batch_mean_host(in_stat, n, &mean, stream);
+    if (rc != 0) return rc;
+    if (out_current_max != 0) out_current_max[0] = mean;
+  }
+  const float max_ = in_thr != 0 ? in_thr[0] : mean;
+  const int sgn = (in_flags & FQ_ACT_SIGNED) != 0;
+  const float levels = sgn ? (float)((1 << (in_width - 1)) - 1) : (float)((1 << in_width) - 1);
+  const float lo = (in_flags & FQ_ACT_LO_NEG_MAX) ? -max_ : 0.0f, sx = max_ / levels, den = sx + 1e-10f;
+  const int64_t cg = c / groups;
+  act &= ~FQ_STAT_PREZEROED;
+  for (int64_t s = 0; s < n; ++s) {
+    float m = 0.0f;
+    for (int64_t co = 0; co < c; ++co) {
+      const int64_t ci0 = co / cg * cg, p0 = ci0 % 32;                    /* the group's first channel, its slab position */
+      for (int64_t oh = 0; oh < h; ++oh)
+        for (int64_t ow = 0; ow < w; ++ow) {
+          int32_t acc = 0;
+          for (int t = 0; t < 9; ++t) {
+            const int64_t ih = oh + t / 3 - 1, iw = ow + t % 3 - 1;
+            if (ih < 0 || ih >= h || iw < 0 || iw >= w) continue;
+            for (int64_t j = 0; j < cg; ++j) {
+              float v = x[((s * c + ci0 + j) * h + ih) * w + iw];
+              v = v < lo ? lo : (v > max_ ? max_ : v);
+              if (v != v) v = lo;
+              const float q = v / den, r = (float)(int32_t)(q + (q < 0.0f ? -0.49999997f : 0.49999997f));
+              acc += (int32_t)r * (int32_t)wcodes[co * 320 + 32 * t + p0 + j];
+            }
+          }
+          float v = (float)acc * (sx * wscale[co]);
+          if (bias != 0) v = v + bias[co];
+          if (bn_scale != 0) {
+            v = v * bn_scale[co];
+            v = v + bn_shift[co];
+          }
+          if (act == FQ_ACT_RELU || act == FQ_ACT_RELU6) v = v > 0.0f ? v : 0.0f;
+          if (act == FQ_ACT_RELU6) v = v < 6.0f ? v : 6.0f;
+          y[((s * c + co) * h + oh) * w + ow] = v;
+          const float a = v < 0.0f ? -v : v;
+          m = a > m ? a : m;
+        }
+    }
+    if (stat_out != 0) stat_out[s] = m;
+  }
+  return 0;
+}
+
 #ifdef __cplusplus
 }
 #endif

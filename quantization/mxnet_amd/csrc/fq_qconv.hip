@@ -597,6 +597,9 @@ int fq_qconv2d_forward(const float* x, const float* w, const void* wbuf, const f
   // (as a conditional fix-up - which a record of a [0, max] range with one zero in the tensor never asks for - the launch
   // returns at once: one workgroup per CU keeps that at ~2 us instead of the 4.6 us of 4096 workgroups; the recomputation
   // itself, when it does run, walks its outputs with that smaller grid)
+  // (the direct form alone keeps no per-sample statistic and marks that in stat_out[0]: the rest of a row that is the caller's
+  // fresh allocation must not be left as it was found)
+  if (!fast && stat_out != nullptr && !prezeroed) FQ_HIP(hipMemsetAsync(stat_out, 0, n * sizeof(float), st));
   const int64_t want = (out_numel + kBlock - 1) / kBlock;
   const int64_t cap = (int64_t)num_cu() * (fast ? 1 : 16);
   const int grid = (int)(want < cap ? want : cap);

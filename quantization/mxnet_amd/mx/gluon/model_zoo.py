@@ -12,7 +12,7 @@ from .block import HybridBlock
 from . import nn
 from .. import initializer as _init
 
-__all__ = ["get_model", "get_model_list", "MobileNet", "MobileNetV2", "ResNetV1", "CIFARResNetV1", "VGG"]
+__all__ = ["get_model", "get_model_list", "MobileNet", "MobileNetV2", "ResNetV1", "ResNext", "CIFARResNetV1", "VGG"]
 
 
 class RELU6(HybridBlock):
@@ -195,6 +195,66 @@ class ResNetV1(HybridBlock):
         return self.output(self.features(x))
 
 
+class ResNextBlock(BottleneckV1):
+    """gluoncv's resnext `Block` without squeeze-and-excitation: 1x1 to the group width, a GROUPED 3x3 that carries the stride,
+    1x1 to 4 x channels, each with BatchNorm, ReLU behind the first two; a 1x1 + BatchNorm shortcut where the shape changes.
+    Group width = cardinality * floor(channels * bottleneck_width / 64).  The forward is BottleneckV1's `(x + residual).relu()`."""
+
+    def __init__(self, channels, cardinality, bottleneck_width, stride, downsample=False, in_channels=0, **kwargs):
+        HybridBlock.__init__(self, **kwargs)
+        width = cardinality * int(channels * (bottleneck_width / 64.0))
+        self.body = nn.HybridSequential(prefix="")
+        self.body.add(nn.Conv2D(width, kernel_size=1, use_bias=False, in_channels=in_channels))
+        self.body.add(nn.BatchNorm(in_channels=width))
+        self.body.add(nn.Activation("relu"))
+        self.body.add(nn.Conv2D(width, kernel_size=3, strides=stride, padding=1, groups=cardinality, use_bias=False,
+                                in_channels=width))
+        self.body.add(nn.BatchNorm(in_channels=width))
+        self.body.add(nn.Activation("relu"))
+        self.body.add(nn.Conv2D(channels * 4, kernel_size=1, use_bias=False, in_channels=width))
+        self.body.add(nn.BatchNorm(in_channels=channels * 4))
+        if downsample:
+            self.downsample = nn.HybridSequential(prefix="")
+            self.downsample.add(nn.Conv2D(channels * 4, kernel_size=1, strides=stride, use_bias=False,
+                                          in_channels=in_channels))
+            self.downsample.add(nn.BatchNorm(in_channels=channels * 4))
+        else:
+            self.downsample = None
+
+
+class ResNext(HybridBlock):
+    """gluoncv.model_zoo.resnext.ResNext: 7x7 stem with max-pool, four stages of `ResNextBlock`s (64, 128, 256, 512 channels
+    before the x 4 expansion, stride 2 from the second stage on), global average pooling, Dense.  Parameters are named
+    structurally like the ResNets here; gluoncv is not installed where this was written, so that its checkpoints' names match
+    these could not be checked."""
+
+    def __init__(self, layers, cardinality, bottleneck_width, classes=1000, **kwargs):
+        super(ResNext, self).__init__(**kwargs)
+        with self.name_scope():
+            self.features = nn.HybridSequential(prefix="")
+            self.features.add(nn.Conv2D(64, 7, 2, 3, use_bias=False, in_channels=3))
+            self.features.add(nn.BatchNorm(in_channels=64))
+            self.features.add(nn.Activation("relu"))
+            self.features.add(nn.MaxPool2D(3, 2, 1))
+            in_channels = 64
+            for i, num_layer in enumerate(layers):
+                channels, stride = 64 << i, 1 if i == 0 else 2
+                stage = nn.HybridSequential(prefix="stage%d_" % (i + 1))
+                with stage.name_scope():
+                    stage.add(ResNextBlock(channels, cardinality, bottleneck_width, stride, True, in_channels=in_channels,
+                                           prefix=""))
+                    for _ in range(num_layer - 1):
+                        stage.add(ResNextBlock(channels, cardinality, bottleneck_width, 1, False, in_channels=channels * 4,
+                                               prefix=""))
+                self.features.add(stage)
+                in_channels = channels * 4
+            self.features.add(nn.GlobalAvgPool2D())
+            self.output = nn.Dense(classes, in_units=in_channels)
+
+    def forward(self, x):
+        return self.output(self.features(x))
+
+
 class CIFARBasicBlockV1(BasicBlockV1):
     pass
 
@@ -283,6 +343,11 @@ for _n, (_b, _l, _c) in _RESNET_SPEC.items():
     _MODELS["resnet%d_v1" % _n] = (lambda b, l, c: (lambda **kw: ResNetV1(b, l, c, **kw)))(_b, _l, _c)
 
 
+for _name, _l, _card, _bw in (("resnext50_32x4d", [3, 4, 6, 3], 32, 4), ("resnext101_32x4d", [3, 4, 23, 3], 32, 4),
+                              ("resnext101_64x4d", [3, 4, 23, 3], 64, 4)):
+    _MODELS[_name] = (lambda l, c, b: (lambda **kw: ResNext(l, c, b, **kw)))(_l, _card, _bw)
+
+
 for _n, (_l, _f) in _VGG_SPEC.items():
     _MODELS["vgg%d" % _n] = (lambda l, f: (lambda **kw: VGG(l, f, **kw)))(_l, _f)
     _MODELS["vgg%d_bn" % _n] = (lambda l, f: (lambda **kw: VGG(l, f, batch_norm=True, **kw)))(_l, _f)
@@ -339,7 +404,7 @@ def get_model(name, pretrained=False, classes=None, ctx=None, root=None, **kwarg
             raise TypeError("%s: __init__() got an unexpected keyword argument 'batch_norm'" % name)
         if not name.endswith("_bn"):
             kw["batch_norm"] = True
-    if last_gamma and not (name.startswith("resnet") or name.startswith("cifar_resnet")):
+    if last_gamma and not (name.startswith("resnet") or name.startswith("resnext") or name.startswith("cifar_resnet")):
         raise TypeError("%s: __init__() got an unexpected keyword argument 'last_gamma'" % name)
     if kwargs:
         raise TypeError("%s: __init__() got unexpected keyword arguments %s" % (name, sorted(kwargs)))

@@ -99,7 +99,7 @@ def device_info():
 
 
 KERNEL_IDS = {"stat": 0, "apply_online": 1, "apply_offline": 2, "weight": 3, "histogram": 4, "bn_act": 5,
-              "dwconv": 6, "pwconv": 7, "stem": 8, "pool": 9, "global_max": 10, "conv3x3": 11, "dense": 12}
+              "dwconv": 6, "pwconv": 7, "stem": 8, "pool": 9, "global_max": 10, "conv3x3": 11, "dense": 12, "gconv3x3": 13}
 
 
 # fq_debug_last_launch: family (FQ_LAUNCH_* of include/fakequant.h) -> (name, the names of its values in order)
@@ -111,6 +111,7 @@ LAUNCH_FAMILIES = {
     5: ("stream", ("KT", "thin", "RES", "O16", "I16", "NT", "dual")),
     6: ("stat", ("KT", "waves", "front", "table")),
     7: ("pair", ("KT", "CW", "S", "LZ", "FAST", "CODES", "NS", "rb")),
+    8: ("gconv3x3", ("WC", "PTW", "NB", "CG")),
 }
 
 
@@ -1318,6 +1319,74 @@ def conv3x3_i8(x, wcodes, wscale, wsum, bias=None, in_stat=None, in_thr=None, wi
     check_call(_lib_().fq_conv3x3_i8(_ptr(x), _ptr(wcodes), _ptr(wscale), _ptr(wsum), _ptr(bias), _ptr(y), n, cin, cout,
                                      h, w, _ptr(in_stat), _ptr(in_thr), int(width), int(flags), _ptr(cur_out),
                                      _ptr(bn_scale), _ptr(bn_shift), _ACTS[act] | zflag, _ptr(stat), _stream(x)))
+    return y, stat
+
+
+def gconv3x3_supported(cin, cout, groups, w=None):
+    """True when fq_gconv3x3_i8 takes a grouped 3x3 convolution (stride 1, padding 1) of these channel counts - cin == cout, a
+    multiple of 32, groups > 1 of 4, 8, 16 or 32 channels - and, when given, of planes `w` pixels wide."""
+    lib = _lib_()
+    if lib.fq_version() < 105 or (w is not None and int(w) > GCONV3X3_MAX_W):
+        return False
+    return bool(lib.fq_gconv3x3_i8_supported(int(cin), int(cout), int(groups)))
+
+
+GCONV3X3_MAX_W = 384              # FQ_GCONV3X3_MAX_W of include/fakequant.h: two regions of a pixel block must fit LDS
+
+
+def expand_g3x3(w, groups):
+    """A grouped 3x3 filter (C, C / groups, 3, 3) as the (C, 3, 3, 32) filter `gconv3x3_i8` multiplies: row co holds the cg = C /
+    groups values of tap (ky, kx) at slab position ((co % 32) / cg) * cg + j, zeros elsewhere."""
+    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or w.shape[0] != w.shape[1] * groups:
+        raise ValueError("expected a (C, C / %d, 3, 3) weight, got %s" % (groups, tuple(w.shape)))
+    c, cg = w.shape[0], w.shape[1]
+    if not gconv3x3_supported(c, c, groups):
+        raise ValueError("fq_gconv3x3_i8 does not take %d channels in %d groups" % (c, groups))
+    out = torch.zeros((c, 3, 3, 32), dtype=w.dtype, device=w.device)
+    pos = ((torch.arange(c, device=w.device) % 32) // cg * cg).reshape(c, 1) + torch.arange(cg, device=w.device).reshape(1, cg)
+    out.scatter_(3, pos.reshape(c, 1, 1, cg).expand(c, 3, 3, cg), w.permute(0, 2, 3, 1))
+    return out
+
+
+def weight_codes_g3x3(w, groups, rows_per_scale, width=8):
+    """Codes of a grouped 3x3 weight (C, C / groups, 3, 3) for `gconv3x3_i8`: those of `expand_g3x3(w, groups)`, with one scale
+    per `rows_per_scale` rows - C (layer), C / groups (group) or 1 (channel); the zeros change neither scales nor row sums.
+    Once per weight version, not on the hot path."""
+    _check(w, "w")
+    return weight_codes(expand_g3x3(w, groups), rows_per_scale, width)
+
+
+def _conv_outputs(shape, dev, want_stat, in_stat, cur_out):
+    """(y, stat or None, act flag of a pre-zeroed statistic row, cur_out) of a fused convolution: what the launch writes."""
+    stat, zflag = _stat_target(shape[0], dev, want_stat)
+    if in_stat is not None and cur_out is None:
+        cur_out = torch.empty(1, dtype=torch.float32, device=dev)
+    return torch.empty(shape, dtype=torch.float32, device=dev), stat, zflag, cur_out
+
+
+def gconv3x3_i8(x, wcodes, wscale, wsum, groups, bias=None, in_stat=None, in_thr=None, width=8, flags=0, cur_out=None,
+                bn_scale=None, bn_shift=None, act=None, want_stat=True):
+    """Grouped 3x3 convolution (stride 1, padding 1; `gconv3x3_supported`) on the integer codes (int8 MFMA, exact int32
+    accumulation; fq_gconv3x3_i8) with quantise-on-load and fused BatchNorm / activation / statistic.  x: (N, C, H, W) raw
+    activations; wcodes / wscale / wsum from `weight_codes_g3x3`.  Returns (y, stat or None)."""
+    _check(x, "x")
+    _check(wcodes, "wcodes", torch.int8)
+    _check(wscale, "wscale")
+    _check(wsum, "wsum", torch.int32)
+    for name, t in (("bias", bias), ("in_stat", in_stat), ("in_thr", in_thr), ("bn_scale", bn_scale),
+                    ("bn_shift", bn_shift), ("cur_out", cur_out)):
+        if t is not None:
+            _check(t, name)
+    if x.dim() != 4:
+        raise ValueError("expected (N, C, H, W) activations, got %s" % (tuple(x.shape),))
+    n, c, h, w = x.shape
+    if wscale.numel() != c or wcodes.dim() != 2 or wcodes.shape[1] != 320 or wcodes.shape[0] != (c + 63) // 64 * 64:
+        raise ValueError("weight codes of %s with %d scales do not belong to a grouped 3x3 filter of %d channels"
+                         % (tuple(wcodes.shape), wscale.numel(), c))
+    y, stat, zflag, cur_out = _conv_outputs((n, c, h, w), x.device, want_stat, in_stat, cur_out)
+    check_call(_lib_().fq_gconv3x3_i8(_ptr(x), _ptr(wcodes), _ptr(wscale), _ptr(wsum), _ptr(bias), _ptr(y), n, c, int(groups),
+                                      h, w, _ptr(in_stat), _ptr(in_thr), int(width), int(flags), _ptr(cur_out),
+                                      _ptr(bn_scale), _ptr(bn_shift), _ACTS[act] | zflag, _ptr(stat), _stream(x)))
     return y, stat
 
 

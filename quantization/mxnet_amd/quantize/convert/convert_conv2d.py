@@ -273,8 +273,9 @@ def front_store_taken(block, fz, x, plan):
 
 def _weight_rows_per_scale(block, args):
     cout = block._kwargs["num_filter"]
-    per_channel = args.quant_type == "channel" or (args.quant_type == "group" and block._kwargs["num_group"] == cout)
-    return 1 if per_channel else cout
+    if args.quant_type == "group":                     # one scale per group: 1 row (depthwise), all of them (groups == 1), or between
+        return cout // block._kwargs["num_group"]
+    return 1 if args.quant_type == "channel" else cout
 
 
 def _pointwise_weight_codes(block, args, weight_raw, weight_q):
@@ -300,6 +301,10 @@ def _pointwise_weight_codes(block, args, weight_raw, weight_q):
             block._fq_pw_cache = tuple(codes) + (key,)
         return codes
     make = ops.weight_codes_3x3 if three else ops.weight_codes
+    grouped = block._fq_pw_fused.get("kind") == "g3x3"
+    if grouped:
+        groups = block._kwargs["num_group"]
+        make = lambda w, rps, width: ops.weight_codes_g3x3(w, groups, rps, width)      # noqa: E731
     rederived = block.fixed_params == 1 and held is not None
     src = contiguous((weight_q if rederived else weight_raw)._t)
     live = None if rederived else block.__dict__.get("_fq_pw_live")
@@ -313,7 +318,7 @@ def _pointwise_weight_codes(block, args, weight_raw, weight_q):
     if block.fixed_params == 1:
         block.__dict__.pop("_fq_pw_live", None)
     if rederived:
-        ref = src.permute(0, 2, 3, 1).contiguous() if three else src
+        ref = src.permute(0, 2, 3, 1).contiguous() if three else (ops.expand_g3x3(src, groups) if grouped else src)
         if not ops.weight_codes_reproduce(ref, codes[0], codes[1]):
             block._fq_no_int8 = True
             block.__dict__.pop("_fq_pw_cache", None)
@@ -646,6 +651,9 @@ def pointwise_fused(block, F, x, weight_raw, weight_q, bias, plan, weights_quant
     scale, shift = fz["constants"]() if fz["bn"] is not None else (None, None)
     on_codes = bool(plan) and weights_quantised and args.in_width <= 8 and args.wt_width <= 8 \
         and not getattr(block, "_fq_no_int8", False)
+    if fz.get("kind") == "g3x3" and not (x._t.dim() == 4 and ops.gconv3x3_supported(
+            x._t.shape[1], block._kwargs["num_filter"], block._kwargs["num_group"], w=x._t.shape[3])):
+        on_codes = False                                 # (a plane wider than two regions in LDS: the library convolution)
     held = _pointwise_weight_codes(block, args, weight_raw, weight_q) if on_codes else None
     on_codes = held is not None
     front = getattr(x, "_fq_deferred", None)             # (only the record of a depthwise block in front reaches this function)
@@ -686,7 +694,10 @@ def pointwise_fused(block, F, x, weight_raw, weight_q, bias, plan, weights_quant
             x_arg = torch.empty(tuple(x._t.shape), dtype=torch.float32, device=x._t.device) if front.get("mode") != "store" else None
         else:
             x_arg = c16_in if c16_in is not None else contiguous(x._t)
-        if fz.get("kind") == "3x3":
+        if fz.get("kind") == "g3x3":
+            y, stat = ops.gconv3x3_i8(x_arg, codes, scales, rowsum, block._kwargs["num_group"],
+                                      None if bias is None else bias._t, bn_scale=scale, bn_shift=shift, act=fz["act"], **plan)
+        elif fz.get("kind") == "3x3":
             out_codes = None if fz.get("sliced") else handover_target(block)
             y, stat = ops.conv3x3_i8(x_arg, codes, scales, rowsum, None if bias is None else bias._t,
                                      bn_scale=scale, bn_shift=shift, act=fz["act"],
@@ -909,7 +920,9 @@ def _fake_quant_weight_now(block, args, weight):
         rows = block._kwargs['num_filter']
     elif args.quant_type == 'group':
         rows = block._kwargs['num_group']
-        if rows not in (1, w.shape[0]):
+        # (one scale per group of a grouped 3x3 convolution - the ResNeXt layers - is this package's own: the reference's
+        # broadcast below cannot express it.  fq_weight_fake_quant takes any row count.)
+        if rows not in (1, w.shape[0]) and block._kwargs['kernel'] != (3, 3):
             # the reference broadcasts a (G,1,1,1) scale against (Cout,Cin/g,kh,kw): MXNet raises here too
             raise ValueError("group-wise weight quantisation needs num_group in {1, num_filter} "
                              "(got num_group=%d, num_filter=%d): operands could not be broadcast" % (rows, w.shape[0]))

@@ -202,6 +202,9 @@ GAP_FUSE = _os.environ.get("FQ_GAP_FUSE", "1") != "0"
 # Folded shortcut (round 6, fq_pwconv_i8_shortcut): the shortcut convolution of a stage's first unit is computed inside the launch of
 # the unit's closing 1x1 - the shortcut tensor is never written (FQ_SHORTCUT_FUSE=0: two launches)
 SHORTCUT_FUSE = _os.environ.get("FQ_SHORTCUT_FUSE", "1") != "0"
+# FQ_GCONV=0: the grouped 3x3 layers of the ResNeXt units stay on the generic route - a fake-quant pass, the tensor library's fp32
+# grouped convolution, a BatchNorm + ReLU pass - instead of fq_gconv3x3_i8 (A/B)
+GCONV = _os.environ.get("FQ_GCONV", "1") != "0"
 UNIT_LINKS = _os.environ.get("FQ_HANDOVER_UNITS", "1") != "0"      # hand-over from a MobileNetV2 unit without shortcut to the next block (A/B)
 
 
@@ -248,6 +251,20 @@ def _is_dense3x3(b):
             and k["num_group"] == 1 and k["layout"] == "NCHW" and b.act is None and not a.fake_bn
             and cin in (64, 128, 256, 512) and k["num_filter"] >= 32
             and (not _wino_sliced(b) or (k["num_filter"] % 32 == 0 and WINO_SLICED)))
+
+
+def _is_grouped3x3(b):
+    """A converted GROUPED 3x3 convolution (stride 1, padding 1) whose integer form fq_gconv3x3_i8 takes: as many input as output
+    channels, a multiple of 32, in groups of 4, 8, 16 or 32 - the stride-1 3x3 layers of the ResNeXt units.  A Winograd-domain
+    quantised filter is not on one integer grid per channel and the form has no sliced variant: generic route."""
+    if type(b) is not nn.Conv2D or not hasattr(b, "quantize_args"):
+        return False
+    k = b._kwargs
+    a = b.quantize_args
+    cin = b.weight.shape[1] * k["num_group"] if b.weight.shape is not None and len(b.weight.shape) == 4 else 0
+    return (k["kernel"] == (3, 3) and k["pad"] == (1, 1) and k["dilate"] == (1, 1) and k["stride"] == (1, 1)
+            and 1 < k["num_group"] < k["num_filter"] and k["layout"] == "NCHW" and b.act is None and not a.fake_bn
+            and not _wino_sliced(b) and ops.gconv3x3_supported(cin, k["num_filter"], k["num_group"]))
 
 
 def _wino_sliced(b):
@@ -601,7 +618,8 @@ def fuse_inference(net, depthwise=True, pointwise_int8=True, stem=True, residual
         kids = list(container._children.values())
         for i, b in enumerate(kids):
             dense3 = _is_dense3x3(b)
-            if not (_is_pw1x1(b) or dense3) or hasattr(b, "_fq_pw_fused") or hasattr(b, "_fq_dw_fused"):
+            group3 = GCONV and _is_grouped3x3(b)
+            if not (_is_pw1x1(b) or dense3 or group3) or hasattr(b, "_fq_pw_fused") or hasattr(b, "_fq_dw_fused"):
                 continue
             bn = kids[i + 1] if i + 1 < len(kids) else None
             if not (type(bn) is nn.BatchNorm and not hasattr(bn, "_fq_fused") and bn._kwargs.get("axis", 1) == 1
@@ -611,7 +629,7 @@ def fuse_inference(net, depthwise=True, pointwise_int8=True, stem=True, residual
             act = _act_kind(nxt) if nxt is not None else None
             b._fq_pw_fused = {"bn": bn, "act": act or "none", "act_block": nxt if act else None,
                               "constants": _bn_constants_getter(bn) if bn is not None else None,
-                              "kind": "3x3" if dense3 else "1x1", "sliced": bool(dense3 and _wino_sliced(b))}
+                              "kind": "3x3" if dense3 else ("g3x3" if group3 else "1x1"), "sliced": bool(dense3 and _wino_sliced(b))}
             if bn is not None:
                 bn._fq_fused = {"taken_by_conv": True, "orig": bn.hybrid_forward, "act_block": None}
                 bn.hybrid_forward = types.MethodType(_identity_forward, bn)
@@ -631,10 +649,12 @@ def fuse_inference(net, depthwise=True, pointwise_int8=True, stem=True, residual
 
         for i, b in enumerate(kids):
             fz = getattr(b, "_fq_pw_fused", None) or getattr(b, "_fq_dw_fused", None)
-            if fz is None or fz.get("sliced") or not hasattr(b, "quantize_args"):
-                continue
+            if fz is None or fz.get("sliced") or fz.get("kind") == "g3x3" or not hasattr(b, "quantize_args"):
+                continue                                   # (the grouped 3x3 reads and writes fp32: no hand-over on either side)
             nxt = after(i, fz)
             if type(nxt) is not nn.Conv2D or not hasattr(nxt, "quantize_args"):
+                continue
+            if getattr(nxt, "_fq_pw_fused", None) is not None and nxt._fq_pw_fused.get("kind") == "g3x3":
                 continue
             if hasattr(b, "_fq_dw_fused"):
                 if getattr(nxt, "_fq_pw_fused", None) is not None and nxt._fq_pw_fused.get("kind") == "1x1":
