@@ -490,7 +490,9 @@ int fq_debug_fast_quotient(const float* c, int64_t n, const float* d, float* out
  *   FQ_LAUNCH_PAIR     fq_pwdw_fused:  KT, CW, S (stride), LZ, FAST (compile-time epilogue), CODES (code input), NS (statistic
  *                      mode), rb (rows per band)
  *   FQ_LAUNCH_GCONV3X3 fq_gconv3x3_i8 (libraries from fq_version() 105 on):  WC (slabs of 32 channels per workgroup), PTW (pixel
- *                      tiles per wavefront), NB (pixel blocks a workgroup walks), CG (channels per group)                  */
+ *                      tiles per wavefront), NB (pixel blocks a workgroup walks), CG (channels per group)
+ *   FQ_LAUNCH_GCONV3X3S2 fq_gconv3x3_s2_i8 (libraries from fq_version() 106 on):  WC, PT (pixel tiles of 32 OUTPUT pixels per
+ *                      block), NB, CG                                                                                       */
 #define FQ_LAUNCH_NONE 0
 #define FQ_LAUNCH_CONV3X3 1
 #define FQ_LAUNCH_SPLIT 2
@@ -500,6 +502,7 @@ int fq_debug_fast_quotient(const float* c, int64_t n, const float* d, float* out
 #define FQ_LAUNCH_STAT 6
 #define FQ_LAUNCH_PAIR 7
 #define FQ_LAUNCH_GCONV3X3 8
+#define FQ_LAUNCH_GCONV3X3S2 9
 #define FQ_LAUNCH_VALS 8
 int fq_debug_last_launch(int* kernel_id, int* vals, int nvals);
 int fq_pwdw_fused(const float* x, const int8_t* wcodes, const float* wscale, const int32_t* wsum, const float* pw_bias,
@@ -582,6 +585,18 @@ int fq_gconv3x3_i8(const float* x, const int8_t* wcodes, const float* wscale, co
                    float* y, int64_t n, int64_t c, int64_t groups, int64_t h, int64_t w, const float* in_stat,
                    const float* in_thr, int in_width, unsigned in_flags, float* out_current_max, const float* bn_scale,
                    const float* bn_shift, int act, float* stat_out, fqStream_t stream);
+/* ... with STRIDE 2 (padding 1; libraries from fq_version() 106 on) - the grouped 3x3 layers that open stages 2, 3 and 4 of the
+ * ResNeXt nets.  x: (n, c, h, w) fp32;  y: (n, c, ho, wo) fp32 with ho = (h - 1) / 2 + 1, wo = (w - 1) / 2 + 1, odd and even h
+ * and w down to a 1x1 plane; w <= FQ_GCONV3X3_S2_MAX_W (two region sets of four parity panels must fit LDS).  Shapes
+ * (fq_gconv3x3_s2_i8_supported: those of fq_gconv3x3_i8_supported), the weight buffer and every other argument are
+ * fq_gconv3x3_i8's; each output is bit for bit the stride-1 output at (2 oh, 2 ow), and stat_out[n] <- max|y[n]| covers the
+ * outputs that exist and nothing else.                                                                                      */
+#define FQ_GCONV3X3_S2_MAX_W 256
+int fq_gconv3x3_s2_i8_supported(int64_t cin, int64_t cout, int64_t groups);
+int fq_gconv3x3_s2_i8(const float* x, const int8_t* wcodes, const float* wscale, const int32_t* wsum, const float* bias,
+                      float* y, int64_t n, int64_t c, int64_t groups, int64_t h, int64_t w, const float* in_stat,
+                      const float* in_thr, int in_width, unsigned in_flags, float* out_current_max, const float* bn_scale,
+                      const float* bn_shift, int act, float* stat_out, fqStream_t stream);
 
 /* fq_conv3x3_i8 with C16 code tensors on either side or both (see fq_pwconv_i8_c16): the 3x3 convolution in the middle
  * of a ResNet bottleneck takes the codes its 1x1 predecessor wrote and writes the codes its 1x1 successor reads.            */

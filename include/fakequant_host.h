@@ -300,6 +300,65 @@ int fq_gconv3x3_i8_host(const float* x, const int8_t* wcodes, const float* wscal
   return 0;
 }
 
+/* ... with stride 2 (fq_gconv3x3_s2_i8), as plainly: output (oh, ow) sums the taps at input (2 oh + dy, 2 ow + dx) that exist;
+ * y: (n, c, (h - 1) / 2 + 1, (w - 1) / 2 + 1); the statistic covers these outputs only.  DEFINED here like the pair above.      */
+int fq_gconv3x3_s2_i8_supported_host(int64_t cin, int64_t cout, int64_t groups) {
+  return fq_gconv3x3_i8_supported_host(cin, cout, groups);
+}
+int fq_gconv3x3_s2_i8_host(const float* x, const int8_t* wcodes, const float* wscale, const int32_t* wsum, const float* bias,
+                           float* y, int64_t n, int64_t c, int64_t groups, int64_t h, int64_t w, const float* in_stat,
+                           const float* in_thr, int in_width, unsigned in_flags, float* out_current_max, const float* bn_scale,
+                           const float* bn_shift, int act, float* stat_out, fqStream_t stream) {
+  (void)wsum;
+  if (!x || !wcodes || !wscale || !y || !fq_gconv3x3_s2_i8_supported_host(c, c, groups) || (!in_stat && !in_thr)) return 1;
+  float mean = 0.0f;
+  if (in_stat != 0) {
+    int rc = fq_batch_mean_host(in_stat, n, &mean, stream);
+    if (rc != 0) return rc;
+    if (out_current_max != 0) out_current_max[0] = mean;
+  }
+  const float max_ = in_thr != 0 ? in_thr[0] : mean;
+  const int sgn = (in_flags & FQ_ACT_SIGNED) != 0;
+  const float levels = sgn ? (float)((1 << (in_width - 1)) - 1) : (float)((1 << in_width) - 1);
+  const float lo = (in_flags & FQ_ACT_LO_NEG_MAX) ? -max_ : 0.0f, sx = max_ / levels, den = sx + 1e-10f;
+  const int64_t cg = c / groups, ho = (h - 1) / 2 + 1, wo = (w - 1) / 2 + 1;
+  act &= ~FQ_STAT_PREZEROED;
+  for (int64_t s = 0; s < n; ++s) {
+    float m = 0.0f;
+    for (int64_t co = 0; co < c; ++co) {
+      const int64_t ci0 = co / cg * cg, p0 = ci0 % 32;                    /* the group's first channel, its slab position */
+      for (int64_t oh = 0; oh < ho; ++oh)
+        for (int64_t ow = 0; ow < wo; ++ow) {
+          int32_t acc = 0;
+          for (int t = 0; t < 9; ++t) {
+            const int64_t ih = 2 * oh + t / 3 - 1, iw = 2 * ow + t % 3 - 1;
+            if (ih < 0 || ih >= h || iw < 0 || iw >= w) continue;
+            for (int64_t j = 0; j < cg; ++j) {
+              float v = x[((s * c + ci0 + j) * h + ih) * w + iw];
+              v = v < lo ? lo : (v > max_ ? max_ : v);
+              if (v != v) v = lo;
+              const float q = v / den, r = (float)(int32_t)(q + (q < 0.0f ? -0.49999997f : 0.49999997f));
+              acc += (int32_t)r * (int32_t)wcodes[co * 320 + 32 * t + p0 + j];
+            }
+          }
+          float v = (float)acc * (sx * wscale[co]);
+          if (bias != 0) v = v + bias[co];
+          if (bn_scale != 0) {
+            v = v * bn_scale[co];
+            v = v + bn_shift[co];
+          }
+          if (act == FQ_ACT_RELU || act == FQ_ACT_RELU6) v = v > 0.0f ? v : 0.0f;
+          if (act == FQ_ACT_RELU6) v = v < 6.0f ? v : 6.0f;
+          y[((s * c + co) * ho + oh) * wo + ow] = v;
+          const float a = v < 0.0f ? -v : v;
+          m = a > m ? a : m;
+        }
+    }
+    if (stat_out != 0) stat_out[s] = m;
+  }
+  return 0;
+}
+
 #ifdef __cplusplus
 }
 #endif

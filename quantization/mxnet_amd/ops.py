@@ -112,6 +112,7 @@ LAUNCH_FAMILIES = {
     6: ("stat", ("KT", "waves", "front", "table")),
     7: ("pair", ("KT", "CW", "S", "LZ", "FAST", "CODES", "NS", "rb")),
     8: ("gconv3x3", ("WC", "PTW", "NB", "CG")),
+    9: ("gconv3x3s2", ("WC", "PT", "NB", "CG")),
 }
 
 
@@ -1322,16 +1323,22 @@ def conv3x3_i8(x, wcodes, wscale, wsum, bias=None, in_stat=None, in_thr=None, wi
     return y, stat
 
 
-def gconv3x3_supported(cin, cout, groups, w=None):
-    """True when fq_gconv3x3_i8 takes a grouped 3x3 convolution (stride 1, padding 1) of these channel counts - cin == cout, a
-    multiple of 32, groups > 1 of 4, 8, 16 or 32 channels - and, when given, of planes `w` pixels wide."""
+def gconv3x3_supported(cin, cout, groups, w=None, stride=1):
+    """True when fq_gconv3x3_i8 (stride 1) / fq_gconv3x3_s2_i8 (stride 2) takes a grouped 3x3 convolution (padding 1) of these
+    channel counts - cin == cout, a multiple of 32, groups > 1 of 4, 8, 16 or 32 channels - and, when given, of INPUT planes `w`
+    pixels wide."""
     lib = _lib_()
-    if lib.fq_version() < 105 or (w is not None and int(w) > GCONV3X3_MAX_W):
+    if stride == 2:
+        if lib.fq_version() < 106 or (w is not None and int(w) > GCONV3X3_S2_MAX_W):
+            return False
+        return bool(lib.fq_gconv3x3_s2_i8_supported(int(cin), int(cout), int(groups)))
+    if stride != 1 or lib.fq_version() < 105 or (w is not None and int(w) > GCONV3X3_MAX_W):
         return False
     return bool(lib.fq_gconv3x3_i8_supported(int(cin), int(cout), int(groups)))
 
 
 GCONV3X3_MAX_W = 384              # FQ_GCONV3X3_MAX_W of include/fakequant.h: two regions of a pixel block must fit LDS
+GCONV3X3_S2_MAX_W = 256           # FQ_GCONV3X3_S2_MAX_W: two sets of four parity panels must fit LDS
 
 
 def expand_g3x3(w, groups):
@@ -1365,10 +1372,11 @@ def _conv_outputs(shape, dev, want_stat, in_stat, cur_out):
 
 
 def gconv3x3_i8(x, wcodes, wscale, wsum, groups, bias=None, in_stat=None, in_thr=None, width=8, flags=0, cur_out=None,
-                bn_scale=None, bn_shift=None, act=None, want_stat=True):
-    """Grouped 3x3 convolution (stride 1, padding 1; `gconv3x3_supported`) on the integer codes (int8 MFMA, exact int32
-    accumulation; fq_gconv3x3_i8) with quantise-on-load and fused BatchNorm / activation / statistic.  x: (N, C, H, W) raw
-    activations; wcodes / wscale / wsum from `weight_codes_g3x3`.  Returns (y, stat or None)."""
+                bn_scale=None, bn_shift=None, act=None, want_stat=True, stride=1):
+    """Grouped 3x3 convolution (stride 1 or 2, padding 1; `gconv3x3_supported`) on the integer codes (int8 MFMA, exact int32
+    accumulation; fq_gconv3x3_i8, fq_gconv3x3_s2_i8) with quantise-on-load and fused BatchNorm / activation / statistic.
+    x: (N, C, H, W) raw activations; wcodes / wscale / wsum from `weight_codes_g3x3`, the same buffer for either stride.
+    Returns (y of (N, C, (H - 1) // stride + 1, (W - 1) // stride + 1), stat or None)."""
     _check(x, "x")
     _check(wcodes, "wcodes", torch.int8)
     _check(wscale, "wscale")
@@ -1383,10 +1391,14 @@ def gconv3x3_i8(x, wcodes, wscale, wsum, groups, bias=None, in_stat=None, in_thr
     if wscale.numel() != c or wcodes.dim() != 2 or wcodes.shape[1] != 320 or wcodes.shape[0] != (c + 63) // 64 * 64:
         raise ValueError("weight codes of %s with %d scales do not belong to a grouped 3x3 filter of %d channels"
                          % (tuple(wcodes.shape), wscale.numel(), c))
-    y, stat, zflag, cur_out = _conv_outputs((n, c, h, w), x.device, want_stat, in_stat, cur_out)
-    check_call(_lib_().fq_gconv3x3_i8(_ptr(x), _ptr(wcodes), _ptr(wscale), _ptr(wsum), _ptr(bias), _ptr(y), n, c, int(groups),
-                                      h, w, _ptr(in_stat), _ptr(in_thr), int(width), int(flags), _ptr(cur_out),
-                                      _ptr(bn_scale), _ptr(bn_shift), _ACTS[act] | zflag, _ptr(stat), _stream(x)))
+    if stride not in (1, 2):
+        raise FakeQuantError("fq_gconv3x3_i8 / fq_gconv3x3_s2_i8: stride 1 or 2, got %r" % (stride,))
+    y, stat, zflag, cur_out = _conv_outputs((n, c, (h - 1) // stride + 1, (w - 1) // stride + 1), x.device, want_stat, in_stat,
+                                            cur_out)
+    entry = _lib_().fq_gconv3x3_i8 if stride == 1 else _lib_().fq_gconv3x3_s2_i8
+    check_call(entry(_ptr(x), _ptr(wcodes), _ptr(wscale), _ptr(wsum), _ptr(bias), _ptr(y), n, c, int(groups), h, w,
+                     _ptr(in_stat), _ptr(in_thr), int(width), int(flags), _ptr(cur_out), _ptr(bn_scale), _ptr(bn_shift),
+                     _ACTS[act] | zflag, _ptr(stat), _stream(x)))
     return y, stat
 
 

@@ -652,7 +652,7 @@ def pointwise_fused(block, F, x, weight_raw, weight_q, bias, plan, weights_quant
     on_codes = bool(plan) and weights_quantised and args.in_width <= 8 and args.wt_width <= 8 \
         and not getattr(block, "_fq_no_int8", False)
     if fz.get("kind") == "g3x3" and not (x._t.dim() == 4 and ops.gconv3x3_supported(
-            x._t.shape[1], block._kwargs["num_filter"], block._kwargs["num_group"], w=x._t.shape[3])):
+            x._t.shape[1], block._kwargs["num_filter"], block._kwargs["num_group"], w=x._t.shape[3], stride=fz.get("stride", 1))):
         on_codes = False                                 # (a plane wider than two regions in LDS: the library convolution)
     held = _pointwise_weight_codes(block, args, weight_raw, weight_q) if on_codes else None
     on_codes = held is not None
@@ -696,7 +696,8 @@ def pointwise_fused(block, F, x, weight_raw, weight_q, bias, plan, weights_quant
             x_arg = c16_in if c16_in is not None else contiguous(x._t)
         if fz.get("kind") == "g3x3":
             y, stat = ops.gconv3x3_i8(x_arg, codes, scales, rowsum, block._kwargs["num_group"],
-                                      None if bias is None else bias._t, bn_scale=scale, bn_shift=shift, act=fz["act"], **plan)
+                                      None if bias is None else bias._t, bn_scale=scale, bn_shift=shift, act=fz["act"],
+                                      stride=fz.get("stride", 1), **plan)
         elif fz.get("kind") == "3x3":
             out_codes = None if fz.get("sliced") else handover_target(block)
             y, stat = ops.conv3x3_i8(x_arg, codes, scales, rowsum, None if bias is None else bias._t,

@@ -205,6 +205,9 @@ SHORTCUT_FUSE = _os.environ.get("FQ_SHORTCUT_FUSE", "1") != "0"
 # FQ_GCONV=0: the grouped 3x3 layers of the ResNeXt units stay on the generic route - a fake-quant pass, the tensor library's fp32
 # grouped convolution, a BatchNorm + ReLU pass - instead of fq_gconv3x3_i8 (A/B)
 GCONV = _os.environ.get("FQ_GCONV", "1") != "0"
+# FQ_GCONV_S2=0: the STRIDE-2 grouped 3x3 layers alone - the ones that open stages 2, 3 and 4 of a ResNeXt - stay on the generic
+# route instead of fq_gconv3x3_s2_i8 (A/B); FQ_GCONV=0 turns both strides off
+GCONV_S2 = _os.environ.get("FQ_GCONV_S2", "1") != "0"
 UNIT_LINKS = _os.environ.get("FQ_HANDOVER_UNITS", "1") != "0"      # hand-over from a MobileNetV2 unit without shortcut to the next block (A/B)
 
 
@@ -265,6 +268,19 @@ def _is_grouped3x3(b):
     return (k["kernel"] == (3, 3) and k["pad"] == (1, 1) and k["dilate"] == (1, 1) and k["stride"] == (1, 1)
             and 1 < k["num_group"] < k["num_filter"] and k["layout"] == "NCHW" and b.act is None and not a.fake_bn
             and not _wino_sliced(b) and ops.gconv3x3_supported(cin, k["num_filter"], k["num_group"]))
+
+
+def _is_grouped3x3_s2(b):
+    """`_is_grouped3x3` for stride (2, 2): the grouped 3x3 layer of the first unit of a ResNeXt stage, whose integer form
+    fq_gconv3x3_s2_i8 takes.  Same channel counts, same weight buffer, same refusals."""
+    if type(b) is not nn.Conv2D or not hasattr(b, "quantize_args"):
+        return False
+    k = b._kwargs
+    a = b.quantize_args
+    cin = b.weight.shape[1] * k["num_group"] if b.weight.shape is not None and len(b.weight.shape) == 4 else 0
+    return (k["kernel"] == (3, 3) and k["pad"] == (1, 1) and k["dilate"] == (1, 1) and k["stride"] == (2, 2)
+            and 1 < k["num_group"] < k["num_filter"] and k["layout"] == "NCHW" and b.act is None and not a.fake_bn
+            and not _wino_sliced(b) and ops.gconv3x3_supported(cin, k["num_filter"], k["num_group"], stride=2))
 
 
 def _wino_sliced(b):
@@ -618,7 +634,8 @@ def fuse_inference(net, depthwise=True, pointwise_int8=True, stem=True, residual
         kids = list(container._children.values())
         for i, b in enumerate(kids):
             dense3 = _is_dense3x3(b)
-            group3 = GCONV and _is_grouped3x3(b)
+            group3s2 = GCONV and GCONV_S2 and _is_grouped3x3_s2(b)
+            group3 = (GCONV and _is_grouped3x3(b)) or group3s2
             if not (_is_pw1x1(b) or dense3 or group3) or hasattr(b, "_fq_pw_fused") or hasattr(b, "_fq_dw_fused"):
                 continue
             bn = kids[i + 1] if i + 1 < len(kids) else None
@@ -630,6 +647,8 @@ def fuse_inference(net, depthwise=True, pointwise_int8=True, stem=True, residual
             b._fq_pw_fused = {"bn": bn, "act": act or "none", "act_block": nxt if act else None,
                               "constants": _bn_constants_getter(bn) if bn is not None else None,
                               "kind": "3x3" if dense3 else ("g3x3" if group3 else "1x1"), "sliced": bool(dense3 and _wino_sliced(b))}
+            if group3s2:
+                b._fq_pw_fused["stride"] = 2                 # (fq_gconv3x3_s2_i8; every other rule of kind "g3x3" holds)
             if bn is not None:
                 bn._fq_fused = {"taken_by_conv": True, "orig": bn.hybrid_forward, "act_block": None}
                 bn.hybrid_forward = types.MethodType(_identity_forward, bn)
