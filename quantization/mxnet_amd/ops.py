@@ -113,6 +113,7 @@ LAUNCH_FAMILIES = {
     7: ("pair", ("KT", "CW", "S", "LZ", "FAST", "CODES", "NS", "rb")),
     8: ("gconv3x3", ("WC", "PTW", "NB", "CG")),
     9: ("gconv3x3s2", ("WC", "PT", "NB", "CG")),
+    10: ("gconv3x3c16", ("WC", "PTW", "NB", "CG", "IN16", "OUT16")),
 }
 
 
@@ -1339,6 +1340,7 @@ def gconv3x3_supported(cin, cout, groups, w=None, stride=1):
 
 GCONV3X3_MAX_W = 384              # FQ_GCONV3X3_MAX_W of include/fakequant.h: two regions of a pixel block must fit LDS
 GCONV3X3_S2_MAX_W = 256           # FQ_GCONV3X3_S2_MAX_W: two sets of four parity panels must fit LDS
+GCONV3X3_C16_MAX_W = 384          # FQ_GCONV3X3_C16_MAX_W: fq_gconv3x3_i8_c16 keeps fq_gconv3x3_i8's two panels
 
 
 def expand_g3x3(w, groups):
@@ -1363,21 +1365,38 @@ def weight_codes_g3x3(w, groups, rows_per_scale, width=8):
     return weight_codes(expand_g3x3(w, groups), rows_per_scale, width)
 
 
-def _conv_outputs(shape, dev, want_stat, in_stat, cur_out):
-    """(y, stat or None, act flag of a pre-zeroed statistic row, cur_out) of a fused convolution: what the launch writes."""
+def _conv_outputs(shape, dev, want_stat, in_stat, cur_out, out_codes=None):
+    """(y, stat or None, act flag of a pre-zeroed statistic row, cur_out) of a fused convolution: what the launch writes.
+    `out_codes`: y is the `Codes16` of that hand-over."""
     stat, zflag = _stat_target(shape[0], dev, want_stat)
     if in_stat is not None and cur_out is None:
         cur_out = torch.empty(1, dtype=torch.float32, device=dev)
-    return torch.empty(shape, dtype=torch.float32, device=dev), stat, zflag, cur_out
+    if out_codes is not None:
+        y = Codes16.empty(shape, dev, _check(out_codes["thr"], "out_codes['thr']"), out_codes.get("width", 8), out_codes.get("flags", 0))
+    else:
+        y = torch.empty(shape, dtype=torch.float32, device=dev)
+    return y, stat, zflag, cur_out
 
 
 def gconv3x3_i8(x, wcodes, wscale, wsum, groups, bias=None, in_stat=None, in_thr=None, width=8, flags=0, cur_out=None,
-                bn_scale=None, bn_shift=None, act=None, want_stat=True, stride=1):
+                bn_scale=None, bn_shift=None, act=None, want_stat=True, stride=1, out_codes=None):
     """Grouped 3x3 convolution (stride 1 or 2, padding 1; `gconv3x3_supported`) on the integer codes (int8 MFMA, exact int32
     accumulation; fq_gconv3x3_i8, fq_gconv3x3_s2_i8) with quantise-on-load and fused BatchNorm / activation / statistic.
     x: (N, C, H, W) raw activations; wcodes / wscale / wsum from `weight_codes_g3x3`, the same buffer for either stride.
+    Offline hand-over as in `conv3x3_i8`, stride 1 only: `x` may be a `Codes16`, `out_codes=dict(thr=..., width=8, flags=0)` makes
+    `y` one (fq_gconv3x3_i8_c16).
     Returns (y of (N, C, (H - 1) // stride + 1, (W - 1) // stride + 1), stat or None)."""
-    _check(x, "x")
+    in16 = isinstance(x, Codes16)
+    if in16:
+        if in_thr is None or not x.matches(in_thr, width, flags):
+            raise FakeQuantError("fq_gconv3x3_i8_c16: the C16 input was quantised with another threshold / width / signedness "
+                                 "than this call names")
+        xc, x = x, x.t
+        _check(x, "x", torch.int8)
+        xshape = xc.shape
+    else:
+        _check(x, "x")
+        xshape = tuple(x.shape)
     _check(wcodes, "wcodes", torch.int8)
     _check(wscale, "wscale")
     _check(wsum, "wsum", torch.int32)
@@ -1385,16 +1404,26 @@ def gconv3x3_i8(x, wcodes, wscale, wsum, groups, bias=None, in_stat=None, in_thr
                     ("bn_shift", bn_shift), ("cur_out", cur_out)):
         if t is not None:
             _check(t, name)
-    if x.dim() != 4:
-        raise ValueError("expected (N, C, H, W) activations, got %s" % (tuple(x.shape),))
-    n, c, h, w = x.shape
+    if len(xshape) != 4:
+        raise ValueError("expected (N, C, H, W) activations, got %s" % (xshape,))
+    n, c, h, w = xshape
     if wscale.numel() != c or wcodes.dim() != 2 or wcodes.shape[1] != 320 or wcodes.shape[0] != (c + 63) // 64 * 64:
         raise ValueError("weight codes of %s with %d scales do not belong to a grouped 3x3 filter of %d channels"
                          % (tuple(wcodes.shape), wscale.numel(), c))
     if stride not in (1, 2):
         raise FakeQuantError("fq_gconv3x3_i8 / fq_gconv3x3_s2_i8: stride 1 or 2, got %r" % (stride,))
+    if (in16 or out_codes is not None) and stride != 1:
+        raise FakeQuantError("fq_gconv3x3_s2_i8 takes and writes fp32 tensors: C16 code tensors with stride 1 only")
     y, stat, zflag, cur_out = _conv_outputs((n, c, (h - 1) // stride + 1, (w - 1) // stride + 1), x.device, want_stat, in_stat,
-                                            cur_out)
+                                            cur_out, out_codes)
+    if in16 or out_codes is not None:
+        out16 = out_codes is not None
+        check_call(_lib_().fq_gconv3x3_i8_c16(_ptr(x), 1 if in16 else 0, _ptr(wcodes), _ptr(wscale), _ptr(wsum), _ptr(bias),
+                                              _ptr(y.t if out16 else y), n, c, int(groups), h, w, _ptr(in_stat), _ptr(in_thr),
+                                              int(width), int(flags), _ptr(cur_out), _ptr(bn_scale), _ptr(bn_shift),
+                                              _ACTS[act] | zflag, _ptr(stat), _ptr(y.thr if out16 else None),
+                                              int(y.width if out16 else 8), int(y.flags if out16 else 0), _stream(wcodes)))
+        return y, stat
     entry = _lib_().fq_gconv3x3_i8 if stride == 1 else _lib_().fq_gconv3x3_s2_i8
     check_call(entry(_ptr(x), _ptr(wcodes), _ptr(wscale), _ptr(wsum), _ptr(bias), _ptr(y), n, c, int(groups), h, w,
                      _ptr(in_stat), _ptr(in_thr), int(width), int(flags), _ptr(cur_out), _ptr(bn_scale), _ptr(bn_shift),

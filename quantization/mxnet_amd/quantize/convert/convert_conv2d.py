@@ -346,15 +346,33 @@ def _hooked(b):
     return b is not None and bool(getattr(b, "_forward_hooks", None) or getattr(b, "_forward_pre_hooks", None))
 
 
-def handover_target(block, fz=None):
-    """The consumer this fused convolution may hand integer codes to (quantize/fuse.py links `next`), when the consumer will
+def _grouped_link_runs(block, fz, nxt, out_w):
+    """A `g_next` link (quantize/fuse.py: into or out of a stride-1 grouped 3x3) is taken only when the consumer WILL read the
+    codes in this forward.  Into the grouped block: `pointwise_fused`'s `on_codes` conditions for it - `_consumer_takes_codes` has
+    asked for all but the shape - i.e. `gconv3x3_supported` with the width of the plane this producer writes.  Out of it: the
+    closing 1x1 reads codes through the split form alone, with or without the unit's residual operand and the trunk's code copy
+    (fq_pwconv_i8_c16 / _dual): the input channel counts that form is built for."""
+    if fz.get("kind") == "g3x3":
+        return ops.pwconv_strided_supported(block._kwargs["num_filter"])
+    k = nxt._kwargs
+    return out_w is not None and ops.gconv3x3_supported(block._kwargs["num_filter"], k["num_filter"], k["num_group"], w=out_w) \
+        and int(out_w) <= ops.GCONV3X3_C16_MAX_W
+
+
+def handover_target(block, fz=None, out_w=None):
+    """The consumer this fused convolution may hand integer codes to (quantize/fuse.py links `next`, or `g_next` into and out of
+    a stride-1 grouped 3x3: `out_w` is then the width of the producer's output plane), when the consumer will
     quantise with its STORED threshold in this very forward - offline input quantisation (convert_conv2d.py:58 takes
     `input_max`) - and runs on the integer codes itself.  A depthwise consumer (fq_dwconv3x3_c16 reads AND writes codes)
     counts only while it can hand over to its own consumer.  Returns the keyword `out_codes` of ops.pwconv_i8 /
-    conv3x3_i8 / dwconv3x3_c16, or None."""
+    conv3x3_i8 / gconv3x3_i8 / dwconv3x3_c16, or None."""
     from .. import fuse as _fuse
     fz = fz if fz is not None else block._fq_pw_fused          # (the first convolution passes its own record)
     nxt = fz.get("next")
+    if nxt is None and _fuse.GCONV_C16 and fz.get("g_next") is not None:
+        nxt = fz["g_next"]
+        if not _grouped_link_runs(block, fz, nxt, out_w):
+            return None
     if nxt is None or not _fuse.HANDOVER or autograd.is_recording() or not _consumer_takes_codes(nxt):
         return None
     # a user hook on the producer, on the consumer or on a block bypassed between them (folded BatchNorm, bypassed
@@ -651,9 +669,11 @@ def pointwise_fused(block, F, x, weight_raw, weight_q, bias, plan, weights_quant
     scale, shift = fz["constants"]() if fz["bn"] is not None else (None, None)
     on_codes = bool(plan) and weights_quantised and args.in_width <= 8 and args.wt_width <= 8 \
         and not getattr(block, "_fq_no_int8", False)
-    if fz.get("kind") == "g3x3" and not (x._t.dim() == 4 and ops.gconv3x3_supported(
-            x._t.shape[1], block._kwargs["num_filter"], block._kwargs["num_group"], w=x._t.shape[3], stride=fz.get("stride", 1))):
-        on_codes = False                                 # (a plane wider than two regions in LDS: the library convolution)
+    if fz.get("kind") == "g3x3":
+        gs = _handed_over(x).shape if _handed_over(x) is not None else tuple(x._t.shape)      # (codes: the tensor they stand for)
+        if not (len(gs) == 4 and ops.gconv3x3_supported(gs[1], block._kwargs["num_filter"], block._kwargs["num_group"], w=gs[3],
+                                                        stride=fz.get("stride", 1))):
+            on_codes = False                             # (a plane wider than two regions in LDS: the library convolution)
     held = _pointwise_weight_codes(block, args, weight_raw, weight_q) if on_codes else None
     on_codes = held is not None
     front = getattr(x, "_fq_deferred", None)             # (only the record of a depthwise block in front reaches this function)
@@ -695,9 +715,11 @@ def pointwise_fused(block, F, x, weight_raw, weight_q, bias, plan, weights_quant
         else:
             x_arg = c16_in if c16_in is not None else contiguous(x._t)
         if fz.get("kind") == "g3x3":
+            # (stride 1 under stored thresholds: the opening 1x1's codes in, the closing 1x1's codes out - fq_gconv3x3_i8_c16)
+            out_codes = handover_target(block) if fz.get("stride", 1) == 1 else None
             y, stat = ops.gconv3x3_i8(x_arg, codes, scales, rowsum, block._kwargs["num_group"],
                                       None if bias is None else bias._t, bn_scale=scale, bn_shift=shift, act=fz["act"],
-                                      stride=fz.get("stride", 1), **plan)
+                                      stride=fz.get("stride", 1), **({} if out_codes is None else dict(out_codes=out_codes)), **plan)
         elif fz.get("kind") == "3x3":
             out_codes = None if fz.get("sliced") else handover_target(block)
             y, stat = ops.conv3x3_i8(x_arg, codes, scales, rowsum, None if bias is None else bias._t,
@@ -766,7 +788,7 @@ def pointwise_fused(block, F, x, weight_raw, weight_q, bias, plan, weights_quant
                 xs = c16_in.shape if c16_in is not None else tuple(x._t.shape)
                 s_ = stride_
                 fz["c16_pays"] = len(xs) == 4 and ((xs[2] - 1) // s_ + 1) * ((xs[3] - 1) // s_ + 1) >= _DW_C16_MIN_PIXELS
-                out_codes = handover_target(block)
+                out_codes = handover_target(block, out_w=(xs[3] - 1) // s_ + 1 if len(xs) == 4 else None)
                 if out_codes is not None and fz.get("via") is not None:
                     # across two MobileNetV2 units (fuse.visit_unit_links): only while the consumer, which will READ codes, can
                     # write codes as well (the rule above, for ITS input) - otherwise its depthwise layer falls back to fp32

@@ -208,6 +208,9 @@ GCONV = _os.environ.get("FQ_GCONV", "1") != "0"
 # FQ_GCONV_S2=0: the STRIDE-2 grouped 3x3 layers alone - the ones that open stages 2, 3 and 4 of a ResNeXt - stay on the generic
 # route instead of fq_gconv3x3_s2_i8 (A/B); FQ_GCONV=0 turns both strides off
 GCONV_S2 = _os.environ.get("FQ_GCONV_S2", "1") != "0"
+# FQ_GCONV_C16=0: no int8 hand-over into or out of the stride-1 grouped 3x3 layers (fq_gconv3x3_i8_c16): they read and write fp32
+# under stored thresholds as well, fq_gconv3x3_i8 (A/B)
+GCONV_C16 = _os.environ.get("FQ_GCONV_C16", "1") != "0"
 UNIT_LINKS = _os.environ.get("FQ_HANDOVER_UNITS", "1") != "0"      # hand-over from a MobileNetV2 unit without shortcut to the next block (A/B)
 
 
@@ -668,12 +671,20 @@ def fuse_inference(net, depthwise=True, pointwise_int8=True, stem=True, residual
 
         for i, b in enumerate(kids):
             fz = getattr(b, "_fq_pw_fused", None) or getattr(b, "_fq_dw_fused", None)
-            if fz is None or fz.get("sliced") or fz.get("kind") == "g3x3" or not hasattr(b, "quantize_args"):
-                continue                                   # (the grouped 3x3 reads and writes fp32: no hand-over on either side)
+            if fz is None or fz.get("sliced") or not hasattr(b, "quantize_args"):
+                continue
             nxt = after(i, fz)
             if type(nxt) is not nn.Conv2D or not hasattr(nxt, "quantize_args"):
                 continue
-            if getattr(nxt, "_fq_pw_fused", None) is not None and nxt._fq_pw_fused.get("kind") == "g3x3":
+            # the grouped 3x3 keeps `next` free on either side (its stride-2 form reads and writes fp32); the stride-1 form between
+            # two fused 1x1 convolutions hands over under a key of its own (fq_gconv3x3_i8_c16; convert_conv2d.handover_target)
+            nz = getattr(nxt, "_fq_pw_fused", None)
+            if fz.get("kind") == "g3x3" or (nz is not None and nz.get("kind") == "g3x3"):
+                g3 = fz if fz.get("kind") == "g3x3" else nz
+                other = nz if g3 is fz else fz
+                if GCONV_C16 and g3.get("stride", 1) == 1 and other is not None and other.get("kind") == "1x1" \
+                        and not hasattr(b, "_fq_dw_fused"):
+                    fz["g_next"] = nxt
                 continue
             if hasattr(b, "_fq_dw_fused"):
                 if getattr(nxt, "_fq_pw_fused", None) is not None and nxt._fq_pw_fused.get("kind") == "1x1":
