@@ -494,7 +494,9 @@ int fq_debug_fast_quotient(const float* c, int64_t n, const float* d, float* out
  *   FQ_LAUNCH_GCONV3X3S2 fq_gconv3x3_s2_i8 (libraries from fq_version() 106 on):  WC, PT (pixel tiles of 32 OUTPUT pixels per
  *                      block), NB, CG
  *   FQ_LAUNCH_GCONV3X3_C16 fq_gconv3x3_i8_c16 (libraries from fq_version() 107 on):  WC, PTW, NB, CG as FQ_LAUNCH_GCONV3X3, IN16,
- *                      OUT16 (C16 codes in / out)                                                                           */
+ *                      OUT16 (C16 codes in / out)
+ *   FQ_LAUNCH_GCONV3X3S2_C16 fq_gconv3x3_s2_i8_c16 (libraries from fq_version() 108 on):  WC, PT, NB, CG as FQ_LAUNCH_GCONV3X3S2,
+ *                      IN16, OUT16, NW (wavefronts per workgroup)                                                           */
 #define FQ_LAUNCH_NONE 0
 #define FQ_LAUNCH_CONV3X3 1
 #define FQ_LAUNCH_SPLIT 2
@@ -506,6 +508,7 @@ int fq_debug_fast_quotient(const float* c, int64_t n, const float* d, float* out
 #define FQ_LAUNCH_GCONV3X3 8
 #define FQ_LAUNCH_GCONV3X3S2 9
 #define FQ_LAUNCH_GCONV3X3_C16 10
+#define FQ_LAUNCH_GCONV3X3S2_C16 11
 #define FQ_LAUNCH_VALS 8
 int fq_debug_last_launch(int* kernel_id, int* vals, int nvals);
 int fq_pwdw_fused(const float* x, const int8_t* wcodes, const float* wscale, const int32_t* wsum, const float* pw_bias,
@@ -612,6 +615,20 @@ int fq_gconv3x3_i8_c16(const void* x, int x_is_c16, const int8_t* wcodes, const 
                        const float* in_stat, const float* in_thr, int in_width, unsigned in_flags, float* out_current_max,
                        const float* bn_scale, const float* bn_shift, int act, float* stat_out, const float* out_thr,
                        int out_width, unsigned out_flags, fqStream_t stream);
+
+/* fq_gconv3x3_s2_i8 with C16 code tensors on either side or both (libraries from fq_version() 108 on): the stride-2 grouped 3x3
+ * that opens stages 2, 3 and 4 of a ResNeXt takes the codes its 1x1 predecessor wrote and writes the codes its 1x1 successor reads,
+ * where fq_gconv3x3_i8_c16 is stride 1 only.  Shapes, weight buffer and every other argument are fq_gconv3x3_s2_i8's, x_is_c16 /
+ * out_thr / out_width / out_flags fq_gconv3x3_i8_c16's: x is (N, C, H, W) fp32 or its [n][C/16][H][W][16] codes, y (N, C, Ho, Wo)
+ * fp32 or [n][C/16][Ho][Wo][16] codes; at least one side is a C16 tensor; w <= FQ_GCONV3X3_S2_C16_MAX_W (the two sets of four
+ * parity panels are fq_gconv3x3_s2_i8's).  The values are those of fq_gconv3x3_s2_i8 followed by the consumer's quantiser, bit
+ * for bit (tests/test_gpu_gconv3x3_s2_c16.py).                                                                               */
+#define FQ_GCONV3X3_S2_C16_MAX_W 256
+int fq_gconv3x3_s2_i8_c16(const void* x, int x_is_c16, const int8_t* wcodes, const float* wscale, const int32_t* wsum,
+                          const float* bias, void* y, int64_t n, int64_t c, int64_t groups, int64_t h, int64_t w,
+                          const float* in_stat, const float* in_thr, int in_width, unsigned in_flags, float* out_current_max,
+                          const float* bn_scale, const float* bn_shift, int act, float* stat_out, const float* out_thr,
+                          int out_width, unsigned out_flags, fqStream_t stream);
 
 /* fq_conv3x3_i8 with C16 code tensors on either side or both (see fq_pwconv_i8_c16): the 3x3 convolution in the middle
  * of a ResNet bottleneck takes the codes its 1x1 predecessor wrote and writes the codes its 1x1 successor reads.            */

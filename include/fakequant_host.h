@@ -359,47 +359,70 @@ int fq_gconv3x3_s2_i8_host(const float* x, const int8_t* wcodes, const float* ws
   return 0;
 }
 
-/* ... between C16 code tensors (fq_gconv3x3_i8_c16), composed of the twin above: a C16 input is read back as the fp32 values its
- * codes stand for (code * sx, which quantise to the same codes), the fp32 result is quantised with the consumer's out_thr into the
- * C16 layout of fakequant.h.  DEFINED here like the pair above (C++ only: the one unit that includes this header is).          */
+/* The two ends of a composed C16 twin.  A C16 tensor ([n][C/16][plane][16], fakequant.h) read back as the fp32 values its codes stand
+ * for (code * sx, which quantise to the same codes), and an fp32 tensor quantised with a consumer's stored threshold into that layout. */
+static void fqh_from_c16(const void* x, float* xf, int64_t n, int64_t c, int64_t hw, const float* thr, int width, unsigned flags) {
+  const int sgn = (flags & FQ_ACT_SIGNED) != 0;
+  const float sx = thr[0] / (sgn ? (float)((1 << (width - 1)) - 1) : (float)((1 << width) - 1));
+  const unsigned char* xb = (const unsigned char*)x;
+  for (int64_t s = 0; s < n; ++s)
+    for (int64_t ch = 0; ch < c; ++ch)
+      for (int64_t p = 0; p < hw; ++p) {
+        const int b = xb[((s * (c / 16) + ch / 16) * hw + p) * 16 + ch % 16] ^ 0x80;      /* (code + 128 - zoff) mod 256 */
+        xf[(s * c + ch) * hw + p] = (float)(sgn ? (int)(signed char)(unsigned char)(b - 128) : b) * sx;
+      }
+}
+static void fqh_to_c16(const float* yf, void* y, int64_t n, int64_t c, int64_t hw, const float* thr, int width, unsigned flags) {
+  const int sgn = (flags & FQ_ACT_SIGNED) != 0;
+  const float max_ = thr[0], levels = sgn ? (float)((1 << (width - 1)) - 1) : (float)((1 << width) - 1);
+  const float lo = (flags & FQ_ACT_LO_NEG_MAX) ? -max_ : 0.0f, den = max_ / levels + 1e-10f;
+  unsigned char* yb = (unsigned char*)y;
+  for (int64_t s = 0; s < n; ++s)
+    for (int64_t ch = 0; ch < c; ++ch)
+      for (int64_t p = 0; p < hw; ++p) {
+        float v = yf[(s * c + ch) * hw + p];
+        v = v < lo ? lo : (v > max_ ? max_ : v);
+        if (v != v) v = lo;
+        const float q = v / den;
+        const int code = (int32_t)(q + (q < 0.0f ? -0.49999997f : 0.49999997f));
+        yb[((s * (c / 16) + ch / 16) * hw + p) * 16 + ch % 16] = (unsigned char)(((code + (sgn ? 128 : 0)) & 255) ^ 0x80);
+      }
+}
+
+/* ... between C16 code tensors (fq_gconv3x3_i8_c16, fq_gconv3x3_s2_i8_c16), composed of the two twins above and the two ends.
+ * DEFINED here like the pair above (C++ only: the one unit that includes this header is).                                      */
 int fq_gconv3x3_i8_c16_host(const void* x, int x_is_c16, const int8_t* wcodes, const float* wscale, const int32_t* wsum,
                             const float* bias, void* y, int64_t n, int64_t c, int64_t groups, int64_t h, int64_t w,
                             const float* in_stat, const float* in_thr, int in_width, unsigned in_flags, float* out_current_max,
                             const float* bn_scale, const float* bn_shift, int act, float* stat_out, const float* out_thr,
                             int out_width, unsigned out_flags, fqStream_t stream) {
   if (!x || !y || (!x_is_c16 && !out_thr) || (x_is_c16 && !in_thr) || c % 16 != 0) return 1;
-  const int64_t hw = h * w, cb = c / 16, numel = n * c * hw;
+  const int64_t hw = h * w, numel = n * c * hw;
   float* xf = x_is_c16 ? new float[numel] : 0;
   float* yf = out_thr ? new float[numel] : 0;
-  if (x_is_c16) {
-    const int sgn = (in_flags & FQ_ACT_SIGNED) != 0;
-    const float sx = in_thr[0] / (sgn ? (float)((1 << (in_width - 1)) - 1) : (float)((1 << in_width) - 1));
-    const unsigned char* xb = (const unsigned char*)x;
-    for (int64_t s = 0; s < n; ++s)
-      for (int64_t ch = 0; ch < c; ++ch)
-        for (int64_t p = 0; p < hw; ++p) {
-          const int b = xb[((s * cb + ch / 16) * hw + p) * 16 + ch % 16] ^ 0x80;      /* (code + 128 - zoff) mod 256 */
-          xf[(s * c + ch) * hw + p] = (float)(sgn ? (int)(signed char)(unsigned char)(b - 128) : b) * sx;
-        }
-  }
+  if (x_is_c16) fqh_from_c16(x, xf, n, c, hw, in_thr, in_width, in_flags);
   int rc = fq_gconv3x3_i8_host(x_is_c16 ? xf : (const float*)x, wcodes, wscale, wsum, bias, out_thr ? yf : (float*)y, n, c, groups,
                                h, w, in_stat, in_thr, in_width, in_flags, out_current_max, bn_scale, bn_shift, act, stat_out, stream);
-  if (rc == 0 && out_thr) {
-    const int sgn = (out_flags & FQ_ACT_SIGNED) != 0;
-    const float max_ = out_thr[0], levels = sgn ? (float)((1 << (out_width - 1)) - 1) : (float)((1 << out_width) - 1);
-    const float lo = (out_flags & FQ_ACT_LO_NEG_MAX) ? -max_ : 0.0f, den = max_ / levels + 1e-10f;
-    unsigned char* yb = (unsigned char*)y;
-    for (int64_t s = 0; s < n; ++s)
-      for (int64_t ch = 0; ch < c; ++ch)
-        for (int64_t p = 0; p < hw; ++p) {
-          float v = yf[(s * c + ch) * hw + p];
-          v = v < lo ? lo : (v > max_ ? max_ : v);
-          if (v != v) v = lo;
-          const float q = v / den;
-          const int code = (int32_t)(q + (q < 0.0f ? -0.49999997f : 0.49999997f));
-          yb[((s * cb + ch / 16) * hw + p) * 16 + ch % 16] = (unsigned char)(((code + (sgn ? 128 : 0)) & 255) ^ 0x80);
-        }
-  }
+  if (rc == 0 && out_thr) fqh_to_c16(yf, y, n, c, hw, out_thr, out_width, out_flags);
+  delete[] xf;
+  delete[] yf;
+  return rc;
+}
+
+int fq_gconv3x3_s2_i8_c16_host(const void* x, int x_is_c16, const int8_t* wcodes, const float* wscale, const int32_t* wsum,
+                               const float* bias, void* y, int64_t n, int64_t c, int64_t groups, int64_t h, int64_t w,
+                               const float* in_stat, const float* in_thr, int in_width, unsigned in_flags, float* out_current_max,
+                               const float* bn_scale, const float* bn_shift, int act, float* stat_out, const float* out_thr,
+                               int out_width, unsigned out_flags, fqStream_t stream) {
+  if (!x || !y || (!x_is_c16 && !out_thr) || (x_is_c16 && !in_thr) || c % 16 != 0) return 1;
+  const int64_t hwi = h * w, hwo = ((h - 1) / 2 + 1) * ((w - 1) / 2 + 1);
+  float* xf = x_is_c16 ? new float[n * c * hwi] : 0;
+  float* yf = out_thr ? new float[n * c * hwo] : 0;
+  if (x_is_c16) fqh_from_c16(x, xf, n, c, hwi, in_thr, in_width, in_flags);
+  int rc = fq_gconv3x3_s2_i8_host(x_is_c16 ? xf : (const float*)x, wcodes, wscale, wsum, bias, out_thr ? yf : (float*)y, n, c,
+                                  groups, h, w, in_stat, in_thr, in_width, in_flags, out_current_max, bn_scale, bn_shift, act,
+                                  stat_out, stream);
+  if (rc == 0 && out_thr) fqh_to_c16(yf, y, n, c, hwo, out_thr, out_width, out_flags);
   delete[] xf;
   delete[] yf;
   return rc;

@@ -33,10 +33,11 @@ FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=
 # (a packed fp32 instruction costs about 1.7 plain ones on gfx950, profiles/r5_pk_probe.txt): 72 instead of 48 instructions.
 # fq_pw_stat: its front mode's tap chains were compiled with the flag while the kernel lived in fq_pwdw, and keep it.
 # fq_gconv3x3_s2: no packed fp32 instructions at all - its epilogue and quantiser are scalar fp32 by design, and the unit is
-# compiled so that the backend cannot pair them behind its back; fq_gconv3x3_16: the same epilogue and quantisers, the same flag
+# compiled so that the backend cannot pair them behind its back; fq_gconv3x3_16, fq_gconv3x3_s2_16: the same epilogue and
+# quantisers, the same flag
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 UNIT_FLAGS = {"fq_pwdw": ["-fno-slp-vectorize"], "fq_pw_stat": ["-fno-slp-vectorize"], "fq_gconv3x3_s2": _NO_PK_F32,
-              "fq_gconv3x3_16": _NO_PK_F32}
+              "fq_gconv3x3_16": _NO_PK_F32, "fq_gconv3x3_s2_16": _NO_PK_F32}
 
 
 def hipcc():

@@ -19,7 +19,7 @@
 //   fq_conv3x3.hip     K2n dense 3x3 on int8 codes (implicit GEMM over tap and channel); fq_conv3x3_16.hip: its instantiations
 //                      with C16 code tensors on either side (the kernel: fq_conv3x3_kernel.h)
 //   fq_gconv3x3.hip    K2g grouped 3x3 on int8 codes (the ResNeXt units); fq_gconv3x3_s2.hip K2g2: stride 2; fq_gconv3x3_16.hip
-//                      K2gc: stride 1 between C16 code tensors
+//                      K2gc: stride 1 between C16 code tensors; fq_gconv3x3_s2_16.hip K2g2c: stride 2 between them
 //   fq_pw_stream.hip   K2h pointwise on int8 codes, weights resident in LDS (largest planes)
 //   fq_pw_sample.hip   K2r pointwise, one block of 96..128 pixels x 256 / 512 channels per workgroup, output-stationary
 //   fq_pw_split.hip    K2m pointwise, one (pixel tile, channel group) per workgroup: every other layer from 28x28 planes down;

@@ -114,6 +114,7 @@ LAUNCH_FAMILIES = {
     8: ("gconv3x3", ("WC", "PTW", "NB", "CG")),
     9: ("gconv3x3s2", ("WC", "PT", "NB", "CG")),
     10: ("gconv3x3c16", ("WC", "PTW", "NB", "CG", "IN16", "OUT16")),
+    11: ("gconv3x3s2c16", ("WC", "PT", "NB", "CG", "IN16", "OUT16", "NW")),
 }
 
 
@@ -1341,6 +1342,7 @@ def gconv3x3_supported(cin, cout, groups, w=None, stride=1):
 GCONV3X3_MAX_W = 384              # FQ_GCONV3X3_MAX_W of include/fakequant.h: two regions of a pixel block must fit LDS
 GCONV3X3_S2_MAX_W = 256           # FQ_GCONV3X3_S2_MAX_W: two sets of four parity panels must fit LDS
 GCONV3X3_C16_MAX_W = 384          # FQ_GCONV3X3_C16_MAX_W: fq_gconv3x3_i8_c16 keeps fq_gconv3x3_i8's two panels
+GCONV3X3_S2_C16_MAX_W = 256       # FQ_GCONV3X3_S2_C16_MAX_W: fq_gconv3x3_s2_i8_c16 keeps fq_gconv3x3_s2_i8's two sets of panels
 
 
 def expand_g3x3(w, groups):
@@ -1384,13 +1386,34 @@ def gconv3x3_i8(x, wcodes, wscale, wsum, groups, bias=None, in_stat=None, in_thr
     accumulation; fq_gconv3x3_i8, fq_gconv3x3_s2_i8) with quantise-on-load and fused BatchNorm / activation / statistic.
     x: (N, C, H, W) raw activations; wcodes / wscale / wsum from `weight_codes_g3x3`, the same buffer for either stride.
     Offline hand-over as in `conv3x3_i8`, stride 1 only: `x` may be a `Codes16`, `out_codes=dict(thr=..., width=8, flags=0)` makes
-    `y` one (fq_gconv3x3_i8_c16).
+    `y` one (fq_gconv3x3_i8_c16).  Stride 2 between code tensors is an op of its own, `gconv3x3_s2_c16`.
     Returns (y of (N, C, (H - 1) // stride + 1, (W - 1) // stride + 1), stat or None)."""
+    if (isinstance(x, Codes16) or out_codes is not None) and stride == 2:
+        raise FakeQuantError("fq_gconv3x3_s2_i8 takes and writes fp32 tensors: C16 code tensors with stride 1 only "
+                             "(stride 2: ops.gconv3x3_s2_c16, fq_gconv3x3_s2_i8_c16)")
+    return _gconv3x3(x, wcodes, wscale, wsum, groups, bias, in_stat, in_thr, width, flags, cur_out, bn_scale, bn_shift, act,
+                     want_stat, stride, out_codes)
+
+
+def gconv3x3_s2_c16(x, wcodes, wscale, wsum, groups, bias=None, in_stat=None, in_thr=None, width=8, flags=0, cur_out=None,
+                    bn_scale=None, bn_shift=None, act=None, want_stat=True, out_codes=None):
+    """`gconv3x3_i8(stride=2)` with a C16 code tensor on either side or both (fq_gconv3x3_s2_i8_c16): `x` is a `Codes16` or fp32,
+    `out_codes=dict(thr=..., width=8, flags=0)` makes `y` a `Codes16`; at least one of the two.  Planes up to
+    `GCONV3X3_S2_C16_MAX_W` wide.  Returns (y of (N, C, (H - 1) // 2 + 1, (W - 1) // 2 + 1), stat or None)."""
+    if not isinstance(x, Codes16) and out_codes is None:
+        raise FakeQuantError("fq_gconv3x3_s2_i8_c16: neither side is a C16 tensor (use gconv3x3_i8 with stride=2)")
+    return _gconv3x3(x, wcodes, wscale, wsum, groups, bias, in_stat, in_thr, width, flags, cur_out, bn_scale, bn_shift, act,
+                     want_stat, 2, out_codes)
+
+
+def _gconv3x3(x, wcodes, wscale, wsum, groups, bias, in_stat, in_thr, width, flags, cur_out, bn_scale, bn_shift, act, want_stat,
+              stride, out_codes):
+    """The checks and the call of the two ops above: the four entry points by stride and by whether a side is a `Codes16`."""
     in16 = isinstance(x, Codes16)
     if in16:
         if in_thr is None or not x.matches(in_thr, width, flags):
-            raise FakeQuantError("fq_gconv3x3_i8_c16: the C16 input was quantised with another threshold / width / signedness "
-                                 "than this call names")
+            raise FakeQuantError("fq_gconv3x3_i8_c16 / fq_gconv3x3_s2_i8_c16: the C16 input was quantised with another threshold "
+                                 "/ width / signedness than this call names")
         xc, x = x, x.t
         _check(x, "x", torch.int8)
         xshape = xc.shape
@@ -1412,17 +1435,15 @@ def gconv3x3_i8(x, wcodes, wscale, wsum, groups, bias=None, in_stat=None, in_thr
                          % (tuple(wcodes.shape), wscale.numel(), c))
     if stride not in (1, 2):
         raise FakeQuantError("fq_gconv3x3_i8 / fq_gconv3x3_s2_i8: stride 1 or 2, got %r" % (stride,))
-    if (in16 or out_codes is not None) and stride != 1:
-        raise FakeQuantError("fq_gconv3x3_s2_i8 takes and writes fp32 tensors: C16 code tensors with stride 1 only")
     y, stat, zflag, cur_out = _conv_outputs((n, c, (h - 1) // stride + 1, (w - 1) // stride + 1), x.device, want_stat, in_stat,
                                             cur_out, out_codes)
     if in16 or out_codes is not None:
         out16 = out_codes is not None
-        check_call(_lib_().fq_gconv3x3_i8_c16(_ptr(x), 1 if in16 else 0, _ptr(wcodes), _ptr(wscale), _ptr(wsum), _ptr(bias),
-                                              _ptr(y.t if out16 else y), n, c, int(groups), h, w, _ptr(in_stat), _ptr(in_thr),
-                                              int(width), int(flags), _ptr(cur_out), _ptr(bn_scale), _ptr(bn_shift),
-                                              _ACTS[act] | zflag, _ptr(stat), _ptr(y.thr if out16 else None),
-                                              int(y.width if out16 else 8), int(y.flags if out16 else 0), _stream(wcodes)))
+        entry = _lib_().fq_gconv3x3_i8_c16 if stride == 1 else _lib_().fq_gconv3x3_s2_i8_c16
+        check_call(entry(_ptr(x), 1 if in16 else 0, _ptr(wcodes), _ptr(wscale), _ptr(wsum), _ptr(bias), _ptr(y.t if out16 else y),
+                         n, c, int(groups), h, w, _ptr(in_stat), _ptr(in_thr), int(width), int(flags), _ptr(cur_out),
+                         _ptr(bn_scale), _ptr(bn_shift), _ACTS[act] | zflag, _ptr(stat), _ptr(y.thr if out16 else None),
+                         int(y.width if out16 else 8), int(y.flags if out16 else 0), _stream(wcodes)))
         return y, stat
     entry = _lib_().fq_gconv3x3_i8 if stride == 1 else _lib_().fq_gconv3x3_s2_i8
     check_call(entry(_ptr(x), _ptr(wcodes), _ptr(wscale), _ptr(wsum), _ptr(bias), _ptr(y), n, c, int(groups), h, w,

@@ -346,33 +346,38 @@ def _hooked(b):
     return b is not None and bool(getattr(b, "_forward_hooks", None) or getattr(b, "_forward_pre_hooks", None))
 
 
-def _grouped_link_runs(block, fz, nxt, out_w):
-    """A `g_next` link (quantize/fuse.py: into or out of a stride-1 grouped 3x3) is taken only when the consumer WILL read the
-    codes in this forward.  Into the grouped block: `pointwise_fused`'s `on_codes` conditions for it - `_consumer_takes_codes` has
-    asked for all but the shape - i.e. `gconv3x3_supported` with the width of the plane this producer writes.  Out of it: the
-    closing 1x1 reads codes through the split form alone, with or without the unit's residual operand and the trunk's code copy
-    (fq_pwconv_i8_c16 / _dual): the input channel counts that form is built for."""
+def _grouped_link_runs(block, fz, nxt, out_w, stride):
+    """A `g_next` / `g2_next` link (quantize/fuse.py: into or out of a grouped 3x3 of stride 1 / 2) is taken only when the consumer
+    WILL read the codes in this forward.  Into the grouped block: `pointwise_fused`'s `on_codes` conditions for it -
+    `_consumer_takes_codes` has asked for all but the shape - i.e. `gconv3x3_supported` with the width of the plane this producer
+    writes, within what the C16 kernel of that stride holds in LDS.  Out of it: the closing 1x1 reads codes through the split form
+    alone, with or without the unit's residual operand, the trunk's code copy (fq_pwconv_i8_c16 / _dual) or - the first unit of a
+    stage - the folded shortcut convolution, which takes codes under conditions of its own and is otherwise computed first and added
+    as a tensor: the input channel counts the split form is built for.  (Where this says no behind a stride-2 block, that block
+    still reads codes and writes fp32.)"""
     if fz.get("kind") == "g3x3":
         return ops.pwconv_strided_supported(block._kwargs["num_filter"])
     k = nxt._kwargs
-    return out_w is not None and ops.gconv3x3_supported(block._kwargs["num_filter"], k["num_filter"], k["num_group"], w=out_w) \
-        and int(out_w) <= ops.GCONV3X3_C16_MAX_W
+    return out_w is not None and ops.gconv3x3_supported(block._kwargs["num_filter"], k["num_filter"], k["num_group"], w=out_w,
+                                                        stride=stride) \
+        and int(out_w) <= (ops.GCONV3X3_C16_MAX_W if stride == 1 else ops.GCONV3X3_S2_C16_MAX_W)
 
 
 def handover_target(block, fz=None, out_w=None):
-    """The consumer this fused convolution may hand integer codes to (quantize/fuse.py links `next`, or `g_next` into and out of
-    a stride-1 grouped 3x3: `out_w` is then the width of the producer's output plane), when the consumer will
+    """The consumer this fused convolution may hand integer codes to (quantize/fuse.py links `next`, or `g_next` / `g2_next` into
+    and out of a grouped 3x3 of stride 1 / 2: `out_w` is then the width of the producer's output plane), when the consumer will
     quantise with its STORED threshold in this very forward - offline input quantisation (convert_conv2d.py:58 takes
     `input_max`) - and runs on the integer codes itself.  A depthwise consumer (fq_dwconv3x3_c16 reads AND writes codes)
     counts only while it can hand over to its own consumer.  Returns the keyword `out_codes` of ops.pwconv_i8 /
-    conv3x3_i8 / gconv3x3_i8 / dwconv3x3_c16, or None."""
+    conv3x3_i8 / gconv3x3_i8 / gconv3x3_s2_c16 / dwconv3x3_c16, or None."""
     from .. import fuse as _fuse
     fz = fz if fz is not None else block._fq_pw_fused          # (the first convolution passes its own record)
     nxt = fz.get("next")
-    if nxt is None and _fuse.GCONV_C16 and fz.get("g_next") is not None:
-        nxt = fz["g_next"]
-        if not _grouped_link_runs(block, fz, nxt, out_w):
-            return None
+    for key, on, stride in (("g_next", _fuse.GCONV_C16, 1), ("g2_next", _fuse.GCONV_S2_C16, 2)):
+        if nxt is None and on and fz.get(key) is not None:
+            nxt = fz[key]
+            if not _grouped_link_runs(block, fz, nxt, out_w, stride):
+                return None
     if nxt is None or not _fuse.HANDOVER or autograd.is_recording() or not _consumer_takes_codes(nxt):
         return None
     # a user hook on the producer, on the consumer or on a block bypassed between them (folded BatchNorm, bypassed
@@ -715,11 +720,16 @@ def pointwise_fused(block, F, x, weight_raw, weight_q, bias, plan, weights_quant
         else:
             x_arg = c16_in if c16_in is not None else contiguous(x._t)
         if fz.get("kind") == "g3x3":
-            # (stride 1 under stored thresholds: the opening 1x1's codes in, the closing 1x1's codes out - fq_gconv3x3_i8_c16)
-            out_codes = handover_target(block) if fz.get("stride", 1) == 1 else None
-            y, stat = ops.gconv3x3_i8(x_arg, codes, scales, rowsum, block._kwargs["num_group"],
-                                      None if bias is None else bias._t, bn_scale=scale, bn_shift=shift, act=fz["act"],
-                                      stride=fz.get("stride", 1), **({} if out_codes is None else dict(out_codes=out_codes)), **plan)
+            # (under stored thresholds: the opening 1x1's codes in, the closing 1x1's codes out - fq_gconv3x3_i8_c16, and with
+            # stride 2 the op of its own, which wants codes on at least one side)
+            out_codes = handover_target(block)
+            gkw = dict(bn_scale=scale, bn_shift=shift, act=fz["act"], **({} if out_codes is None else dict(out_codes=out_codes)))
+            if fz.get("stride", 1) == 2 and (c16_in is not None or out_codes is not None):
+                y, stat = ops.gconv3x3_s2_c16(x_arg, codes, scales, rowsum, block._kwargs["num_group"],
+                                              None if bias is None else bias._t, **gkw, **plan)
+            else:
+                y, stat = ops.gconv3x3_i8(x_arg, codes, scales, rowsum, block._kwargs["num_group"],
+                                          None if bias is None else bias._t, stride=fz.get("stride", 1), **gkw, **plan)
         elif fz.get("kind") == "3x3":
             out_codes = None if fz.get("sliced") else handover_target(block)
             y, stat = ops.conv3x3_i8(x_arg, codes, scales, rowsum, None if bias is None else bias._t,

@@ -211,6 +211,9 @@ GCONV_S2 = _os.environ.get("FQ_GCONV_S2", "1") != "0"
 # FQ_GCONV_C16=0: no int8 hand-over into or out of the stride-1 grouped 3x3 layers (fq_gconv3x3_i8_c16): they read and write fp32
 # under stored thresholds as well, fq_gconv3x3_i8 (A/B)
 GCONV_C16 = _os.environ.get("FQ_GCONV_C16", "1") != "0"
+# FQ_GCONV_S2_C16=0: the same for the three stride-2 grouped 3x3 layers (fq_gconv3x3_s2_i8_c16): fp32 around them,
+# fq_gconv3x3_s2_i8 (A/B)
+GCONV_S2_C16 = _os.environ.get("FQ_GCONV_S2_C16", "1") != "0"
 UNIT_LINKS = _os.environ.get("FQ_HANDOVER_UNITS", "1") != "0"      # hand-over from a MobileNetV2 unit without shortcut to the next block (A/B)
 
 
@@ -676,15 +679,18 @@ def fuse_inference(net, depthwise=True, pointwise_int8=True, stem=True, residual
             nxt = after(i, fz)
             if type(nxt) is not nn.Conv2D or not hasattr(nxt, "quantize_args"):
                 continue
-            # the grouped 3x3 keeps `next` free on either side (its stride-2 form reads and writes fp32); the stride-1 form between
-            # two fused 1x1 convolutions hands over under a key of its own (fq_gconv3x3_i8_c16; convert_conv2d.handover_target)
+            # the grouped 3x3 keeps `next` free on either side; between two fused 1x1 convolutions it hands over under a key of its
+            # own, `g_next` with stride 1 (fq_gconv3x3_i8_c16) and `g2_next` with stride 2 (fq_gconv3x3_s2_i8_c16;
+            # convert_conv2d.handover_target follows both)
             nz = getattr(nxt, "_fq_pw_fused", None)
             if fz.get("kind") == "g3x3" or (nz is not None and nz.get("kind") == "g3x3"):
                 g3 = fz if fz.get("kind") == "g3x3" else nz
                 other = nz if g3 is fz else fz
-                if GCONV_C16 and g3.get("stride", 1) == 1 and other is not None and other.get("kind") == "1x1" \
-                        and not hasattr(b, "_fq_dw_fused"):
-                    fz["g_next"] = nxt
+                if other is not None and other.get("kind") == "1x1" and not hasattr(b, "_fq_dw_fused"):
+                    if GCONV_C16 and g3.get("stride", 1) == 1:
+                        fz["g_next"] = nxt
+                    elif GCONV_S2_C16 and g3.get("stride", 1) == 2:
+                        fz["g2_next"] = nxt
                 continue
             if hasattr(b, "_fq_dw_fused"):
                 if getattr(nxt, "_fq_pw_fused", None) is not None and nxt._fq_pw_fused.get("kind") == "1x1":
