@@ -72,7 +72,8 @@ int fq_device_info(char* arch, int arch_len, int* compute_units, int* wavefront)
 #define FQ_KERNEL_CONV3X3 11      /* conv3x3_i8_kernel             : 4 B/in elem + 4 B/out elem                     */
 #define FQ_KERNEL_DENSE 12        /* pwconv_rows_kernel (the classifier on the codes: planes of one pixel; latency-bound)  */
 #define FQ_KERNEL_GCONV3X3 13     /* gconv3x3_i8_kernel            : 4 B/in elem + 4 B/out elem                     */
-#define FQ_KERNEL_COUNT 14
+#define FQ_KERNEL_CONV3X3_NARROW 14 /* conv3x3_narrow_kernel        : 4 B/in elem + 4 B/out elem (moved = algorithmic)  */
+#define FQ_KERNEL_COUNT 15
 int fq_profile_enable(int on);
 int fq_profile_reset(void);
 int fq_profile_read(int kernel_id, double* total_ms, int64_t* launches, double* total_bytes);
@@ -496,7 +497,9 @@ int fq_debug_fast_quotient(const float* c, int64_t n, const float* d, float* out
  *   FQ_LAUNCH_GCONV3X3_C16 fq_gconv3x3_i8_c16 (libraries from fq_version() 107 on):  WC, PTW, NB, CG as FQ_LAUNCH_GCONV3X3, IN16,
  *                      OUT16 (C16 codes in / out)
  *   FQ_LAUNCH_GCONV3X3S2_C16 fq_gconv3x3_s2_i8_c16 (libraries from fq_version() 108 on):  WC, PT, NB, CG as FQ_LAUNCH_GCONV3X3S2,
- *                      IN16, OUT16, NW (wavefronts per workgroup)                                                           */
+ *                      IN16, OUT16, NW (wavefronts per workgroup)
+ *   FQ_LAUNCH_CONV3X3_NARROW fq_conv3x3_i8_narrow (libraries from fq_version() 109 on):  CIN (16 or 32), WC (channel tiles of 32 per
+ *                      workgroup), PTW (pixel tiles per wavefront), NB (pixel blocks a workgroup walks)                     */
 #define FQ_LAUNCH_NONE 0
 #define FQ_LAUNCH_CONV3X3 1
 #define FQ_LAUNCH_SPLIT 2
@@ -509,6 +512,7 @@ int fq_debug_fast_quotient(const float* c, int64_t n, const float* d, float* out
 #define FQ_LAUNCH_GCONV3X3S2 9
 #define FQ_LAUNCH_GCONV3X3_C16 10
 #define FQ_LAUNCH_GCONV3X3S2_C16 11
+#define FQ_LAUNCH_CONV3X3_NARROW 12
 #define FQ_LAUNCH_VALS 8
 int fq_debug_last_launch(int* kernel_id, int* vals, int nvals);
 int fq_pwdw_fused(const float* x, const int8_t* wcodes, const float* wscale, const int32_t* wsum, const float* pw_bias,
@@ -575,6 +579,19 @@ int fq_conv3x3_i8(const float* x, const int8_t* wcodes, const float* wscale, con
                   float* y, int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w, const float* in_stat,
                   const float* in_thr, int in_width, unsigned in_flags, float* out_current_max, const float* bn_scale,
                   const float* bn_shift, int act, float* stat_out, fqStream_t stream);
+
+/* fq_conv3x3_i8 for NARROW layers (libraries from fq_version() 109 on): cin in {16, 32}, any cout >= 1 - the 3x3 layers of the
+ * first two stages of the CIFAR ResNets (16 channels at 32x32, 32 at 16x16), which fq_conv3x3_i8 refuses.  Stride 1, padding 1,
+ * no groups / dilation, fp32 NCHW on both sides; same contract in every other respect: quantise on load from in_stat (online),
+ * in_thr (offline) or both, widths 2 to 8, signed and unsigned codes, exact int32 sums, one fp32 multiply by sx * wscale[co],
+ * bias / folded BatchNorm / activation / per-sample statistic on store, FQ_STAT_PREZEROED, out_current_max.
+ * wcodes / wscale / wsum: what fq_weight_codes writes for the weights permuted to (cout, 3, 3, cin), unchanged: rows = cout,
+ * row_len = 9 * cin (144 / 288), row_pad = 192 / 320, rows_pad = cout rounded up to 64; the all-zero padding of a row is not
+ * multiplied.  Output channels past cout of the last tile of 32 are masked.  Every other cin is refused.                      */
+int fq_conv3x3_i8_narrow(const float* x, const int8_t* wcodes, const float* wscale, const int32_t* wsum, const float* bias,
+                         float* y, int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w, const float* in_stat,
+                         const float* in_thr, int in_width, unsigned in_flags, float* out_current_max, const float* bn_scale,
+                         const float* bn_shift, int act, float* stat_out, fqStream_t stream);
 
 /* GROUPED 3x3 convolution (stride 1, padding 1, no dilation) on the integer codes - the 3x3 layers of the ResNeXt bottlenecks
  * (libraries from fq_version() 105 on).  cin == cout == c, c % 32 == 0, groups > 1 and c / groups in {4, 8, 16, 32}

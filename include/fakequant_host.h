@@ -428,6 +428,61 @@ int fq_gconv3x3_s2_i8_c16_host(const void* x, int x_is_c16, const int8_t* wcodes
   return rc;
 }
 
+/* The dense 3x3 convolution on the codes for 16 and 32 input channels (fq_conv3x3_i8_narrow), restated plainly on the DEVICE's
+ * weight buffer: rows of row_pad = 192 / 320 bytes, tap t's cin codes at [cin t, cin t + cin).  A tap outside the image
+ * contributes x = 0, whose code is 0 in either signedness.  DEFINED here like the grouped twins above.                        */
+int fq_conv3x3_i8_narrow_host(const float* x, const int8_t* wcodes, const float* wscale, const int32_t* wsum, const float* bias,
+                              float* y, int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w, const float* in_stat,
+                              const float* in_thr, int in_width, unsigned in_flags, float* out_current_max,
+                              const float* bn_scale, const float* bn_shift, int act, float* stat_out, fqStream_t stream) {
+  (void)wsum;
+  if (!x || !wcodes || !wscale || !y || (cin != 16 && cin != 32) || cout < 1 || (!in_stat && !in_thr)) return 1;
+  float mean = 0.0f;
+  if (in_stat != 0) {
+    int rc = fq_batch_mean_host(in_stat, n, &mean, stream);
+    if (rc != 0) return rc;
+    if (out_current_max != 0) out_current_max[0] = mean;
+  }
+  const float max_ = in_thr != 0 ? in_thr[0] : mean;
+  const int sgn = (in_flags & FQ_ACT_SIGNED) != 0;
+  const float levels = sgn ? (float)((1 << (in_width - 1)) - 1) : (float)((1 << in_width) - 1);
+  const float lo = (in_flags & FQ_ACT_LO_NEG_MAX) ? -max_ : 0.0f, sx = max_ / levels, den = sx + 1e-10f;
+  const int64_t row_pad = (9 * cin + 63) / 64 * 64;
+  act &= ~FQ_STAT_PREZEROED;
+  for (int64_t s = 0; s < n; ++s) {
+    float m = 0.0f;
+    for (int64_t co = 0; co < cout; ++co)
+      for (int64_t oh = 0; oh < h; ++oh)
+        for (int64_t ow = 0; ow < w; ++ow) {
+          int32_t acc = 0;
+          for (int t = 0; t < 9; ++t) {
+            const int64_t ih = oh + t / 3 - 1, iw = ow + t % 3 - 1;
+            if (ih < 0 || ih >= h || iw < 0 || iw >= w) continue;
+            for (int64_t ci = 0; ci < cin; ++ci) {
+              float v = x[((s * cin + ci) * h + ih) * w + iw];
+              v = v < lo ? lo : (v > max_ ? max_ : v);
+              if (v != v) v = lo;
+              const float q = v / den, r = (float)(int32_t)(q + (q < 0.0f ? -0.49999997f : 0.49999997f));
+              acc += (int32_t)r * (int32_t)wcodes[co * row_pad + cin * t + ci];
+            }
+          }
+          float v = (float)acc * (sx * wscale[co]);
+          if (bias != 0) v = v + bias[co];
+          if (bn_scale != 0) {
+            v = v * bn_scale[co];
+            v = v + bn_shift[co];
+          }
+          if (act == FQ_ACT_RELU || act == FQ_ACT_RELU6) v = v > 0.0f ? v : 0.0f;
+          if (act == FQ_ACT_RELU6) v = v < 6.0f ? v : 6.0f;
+          y[((s * cout + co) * h + oh) * w + ow] = v;
+          const float a = v < 0.0f ? -v : v;
+          m = a > m ? a : m;
+        }
+    if (stat_out != 0) stat_out[s] = m;
+  }
+  return 0;
+}
+
 #ifdef __cplusplus
 }
 #endif

@@ -115,6 +115,8 @@ EXPORTS = {
                                  _vp, _vp, _int, _vp, _vp, _int, _uint, _vp]),
     "fq_conv3x3_i8_sliced": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _int, _uint, _vp,
                                     _vp, _vp, _int, _vp, _vp]),
+    "fq_conv3x3_i8_narrow": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _int, _uint, _vp, _vp,
+                                    _vp, _int, _vp, _vp]),                           # (fq_conv3x3_i8's arguments)
     "fq_gconv3x3_i8_supported": (_int, [_i64, _i64, _i64]),
     # x, wcodes, wscale, wsum, bias, y, n, c, groups, h, w, in_stat, in_thr, in_width, in_flags, cur, bn_scale, bn_shift, act,
     # stat_out, stream
@@ -162,7 +164,7 @@ EXPORTS = {
 # entry points that came after fq_version() 102, with the version that has them: an older library may lack these, and only these
 SINCE = {"fq_pwconv_i8_front_supported": 103, "fq_pwconv_i8_front": 103, "fq_debug_last_launch": 104,
          "fq_gconv3x3_i8_supported": 105, "fq_gconv3x3_i8": 105, "fq_gconv3x3_s2_i8_supported": 106, "fq_gconv3x3_s2_i8": 106,
-         "fq_gconv3x3_i8_c16": 107, "fq_gconv3x3_s2_i8_c16": 108}
+         "fq_gconv3x3_i8_c16": 107, "fq_gconv3x3_s2_i8_c16": 108, "fq_conv3x3_i8_narrow": 109}
 
 FQ_ACT_SIGNED, FQ_ACT_LO_NEG_MAX, FQ_ACT_NO_ABS, FQ_ACT_NO_EPS = 1, 2, 4, 8
 FQ_CODES_INT8, FQ_CODES_UINT8, FQ_CODES_RANGE, FQ_CODES_SCALE = 0, 1, 2, 3

@@ -18,6 +18,7 @@
 //   fq_stem_pool.hip   K2u first convolution 7x7 s2 + BatchNorm + activation + MaxPool 3x3 s2 in one kernel
 //   fq_conv3x3.hip     K2n dense 3x3 on int8 codes (implicit GEMM over tap and channel); fq_conv3x3_16.hip: its instantiations
 //                      with C16 code tensors on either side (the kernel: fq_conv3x3_kernel.h)
+//   fq_conv3x3_narrow.hip K2w dense 3x3 on int8 codes for 16 and 32 input channels (the first two stages of the CIFAR ResNets)
 //   fq_gconv3x3.hip    K2g grouped 3x3 on int8 codes (the ResNeXt units); fq_gconv3x3_s2.hip K2g2: stride 2; fq_gconv3x3_16.hip
 //                      K2gc: stride 1 between C16 code tensors; fq_gconv3x3_s2_16.hip K2g2c: stride 2 between them
 //   fq_pw_stream.hip   K2h pointwise on int8 codes, weights resident in LDS (largest planes)

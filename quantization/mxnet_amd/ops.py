@@ -99,7 +99,9 @@ def device_info():
 
 
 KERNEL_IDS = {"stat": 0, "apply_online": 1, "apply_offline": 2, "weight": 3, "histogram": 4, "bn_act": 5,
-              "dwconv": 6, "pwconv": 7, "stem": 8, "pool": 9, "global_max": 10, "conv3x3": 11, "dense": 12, "gconv3x3": 13}
+              "dwconv": 6, "pwconv": 7, "stem": 8, "pool": 9, "global_max": 10, "conv3x3": 11, "dense": 12, "gconv3x3": 13,
+              "conv3x3_narrow": 14}
+_KERNEL_SINCE = {"conv3x3_narrow": 109}       # ids an older library (FQ_LIB_PATH, A/B) does not know
 
 
 # fq_debug_last_launch: family (FQ_LAUNCH_* of include/fakequant.h) -> (name, the names of its values in order)
@@ -115,6 +117,7 @@ LAUNCH_FAMILIES = {
     9: ("gconv3x3s2", ("WC", "PT", "NB", "CG")),
     10: ("gconv3x3c16", ("WC", "PTW", "NB", "CG", "IN16", "OUT16")),
     11: ("gconv3x3s2c16", ("WC", "PT", "NB", "CG", "IN16", "OUT16", "NW")),
+    12: ("conv3x3narrow", ("CIN", "WC", "PTW", "NB")),
 }
 
 
@@ -145,6 +148,8 @@ def profile_read():
     a C16 code tensor)}} since the last reset (synchronises)."""
     out = {}
     for name, kid in KERNEL_IDS.items():
+        if _lib_().fq_version() < _KERNEL_SINCE.get(name, 0):
+            continue
         ms, n, b = ctypes.c_double(0), ctypes.c_int64(0), ctypes.c_double(0)
         check_call(_lib_().fq_profile_read(kid, ctypes.byref(ms), ctypes.byref(n), ctypes.byref(b)))
         mv = ctypes.c_double(0)
@@ -1265,7 +1270,8 @@ def conv3x3_i8(x, wcodes, wscale, wsum, bias=None, in_stat=None, in_thr=None, wi
     quantise-on-load and fused BatchNorm / activation / statistic.  x: (N, Cin, H, W) raw activations; wcodes / wscale / wsum
     from `weight_codes_3x3` - or from `weight_slices_3x3` (three int8 slices of a filter that is not on one integer grid:
     Winograd-domain quantised weights; fq_conv3x3_i8_sliced).  Offline hand-over as in `pwconv_i8`: `x` may be a `Codes16`,
-    `out_codes=dict(thr=..., width=8, flags=0)` makes `y` one (fq_conv3x3_i8_c16).  Returns (y, stat or None)."""
+    `out_codes=dict(thr=..., width=8, flags=0)` makes `y` one (fq_conv3x3_i8_c16).  Cin of 16 or 32 (`conv3x3_narrow_supported`)
+    between fp32 tensors goes to fq_conv3x3_i8_narrow.  Returns (y, stat or None)."""
     in16 = isinstance(x, Codes16)
     if in16:
         if in_thr is None or not x.matches(in_thr, width, flags):
@@ -1292,8 +1298,8 @@ def conv3x3_i8(x, wcodes, wscale, wsum, bias=None, in_stat=None, in_thr=None, wi
         rows_pad = (cout + 63) // 64 * 64
         if wcodes.shape[1] != 2 * rows_pad * 9 * cin or (9 * cin) % 64:
             raise ValueError("weight slices do not match Cin = %d, Cout = %d" % (cin, cout))
-    elif wcodes.shape[1] != 9 * cin:
-        raise ValueError("weight codes have rows of %d, expected 9 * Cin = %d" % (wcodes.shape[1], 9 * cin))
+    elif wcodes.shape[1] != (9 * cin + 63) // 64 * 64:
+        raise ValueError("weight codes have rows of %d, expected 9 * Cin = %d (padded to 64)" % (wcodes.shape[1], 9 * cin))
     stat, zflag = _stat_target(n, dev, want_stat)
     if in_stat is not None and cur_out is None:
         cur_out = torch.empty(1, dtype=torch.float32, device=dev)
@@ -1319,10 +1325,21 @@ def conv3x3_i8(x, wcodes, wscale, wsum, bias=None, in_stat=None, in_thr=None, wi
                                                 _ptr(cur_out), _ptr(bn_scale), _ptr(bn_shift), _ACTS[act] | zflag,
                                                 _ptr(stat), _stream(x)))
         return y, stat
-    check_call(_lib_().fq_conv3x3_i8(_ptr(x), _ptr(wcodes), _ptr(wscale), _ptr(wsum), _ptr(bias), _ptr(y), n, cin, cout,
-                                     h, w, _ptr(in_stat), _ptr(in_thr), int(width), int(flags), _ptr(cur_out),
-                                     _ptr(bn_scale), _ptr(bn_shift), _ACTS[act] | zflag, _ptr(stat), _stream(x)))
+    entry = _lib_().fq_conv3x3_i8
+    if conv3x3_narrow_supported(cin, cout):
+        if _lib_().fq_version() < 109:
+            raise FakeQuantError("fq_conv3x3_i8_narrow needs a library of fq_version() 109 or later")
+        entry = _lib_().fq_conv3x3_i8_narrow
+    check_call(entry(_ptr(x), _ptr(wcodes), _ptr(wscale), _ptr(wsum), _ptr(bias), _ptr(y), n, cin, cout, h, w, _ptr(in_stat),
+                     _ptr(in_thr), int(width), int(flags), _ptr(cur_out), _ptr(bn_scale), _ptr(bn_shift), _ACTS[act] | zflag,
+                     _ptr(stat), _stream(x)))
     return y, stat
+
+
+def conv3x3_narrow_supported(cin, cout):
+    """True when `conv3x3_i8` takes a dense 3x3 convolution (stride 1, padding 1) of these channel counts through
+    fq_conv3x3_i8_narrow: 16 or 32 input channels, any number of output channels.  Shapes only: nothing is asked of the library."""
+    return int(cin) in (16, 32) and int(cout) >= 1
 
 
 def gconv3x3_supported(cin, cout, groups, w=None, stride=1):

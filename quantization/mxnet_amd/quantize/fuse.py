@@ -214,6 +214,9 @@ GCONV_C16 = _os.environ.get("FQ_GCONV_C16", "1") != "0"
 # FQ_GCONV_S2_C16=0: the same for the three stride-2 grouped 3x3 layers (fq_gconv3x3_s2_i8_c16): fp32 around them,
 # fq_gconv3x3_s2_i8 (A/B)
 GCONV_S2_C16 = _os.environ.get("FQ_GCONV_S2_C16", "1") != "0"
+# FQ_C3_NARROW=0: the dense 3x3 layers with 16 or 32 input channels - the first two stages of the CIFAR ResNets - stay on the
+# generic route instead of fq_conv3x3_i8_narrow (A/B)
+C3_NARROW = _os.environ.get("FQ_C3_NARROW", "1") != "0"
 UNIT_LINKS = _os.environ.get("FQ_HANDOVER_UNITS", "1") != "0"      # hand-over from a MobileNetV2 unit without shortcut to the next block (A/B)
 
 
@@ -250,7 +253,7 @@ def _is_dense3x3(b):
     """A converted dense 3x3 convolution (stride 1, padding 1) whose integer form fq_conv3x3_i8 takes: the 3x3 layers of the
     ResNet units.  Under Winograd-domain weight quantisation the spatial filter is not an integer multiple of one scale per
     channel: it then goes through the three-slice form (fq_weight_slices + fq_conv3x3_i8_sliced; `_wino_sliced`), which
-    needs whole 32-channel tiles."""
+    needs whole 32-channel tiles.  16 or 32 input channels (`_is_narrow3x3`: fq_conv3x3_i8_narrow) have no sliced form."""
     if type(b) is not nn.Conv2D or not hasattr(b, "quantize_args"):
         return False
     k = b._kwargs
@@ -258,8 +261,17 @@ def _is_dense3x3(b):
     cin = b.weight.shape[1] if b.weight.shape is not None and len(b.weight.shape) == 4 else 0
     return (k["kernel"] == (3, 3) and k["pad"] == (1, 1) and k["dilate"] == (1, 1) and k["stride"] == (1, 1)
             and k["num_group"] == 1 and k["layout"] == "NCHW" and b.act is None and not a.fake_bn
-            and cin in (64, 128, 256, 512) and k["num_filter"] >= 32
-            and (not _wino_sliced(b) or (k["num_filter"] % 32 == 0 and WINO_SLICED)))
+            and ((cin in (64, 128, 256, 512) and k["num_filter"] >= 32
+                  and (not _wino_sliced(b) or (k["num_filter"] % 32 == 0 and WINO_SLICED)))
+                 or _is_narrow3x3(b)))
+
+
+def _is_narrow3x3(b):
+    """The channel counts of `_is_dense3x3` that go to fq_conv3x3_i8_narrow: 16 or 32 input channels, any output channels, the
+    filter on one integer grid per scale.  Such a block reads and writes fp32 under stored thresholds as well: no hand-over link
+    is set into or out of it."""
+    cin = b.weight.shape[1] if b.weight.shape is not None and len(b.weight.shape) == 4 else 0
+    return C3_NARROW and cin in (16, 32) and ops.conv3x3_narrow_supported(cin, b._kwargs["num_filter"]) and not _wino_sliced(b)
 
 
 def _is_grouped3x3(b):
@@ -653,6 +665,8 @@ def fuse_inference(net, depthwise=True, pointwise_int8=True, stem=True, residual
             b._fq_pw_fused = {"bn": bn, "act": act or "none", "act_block": nxt if act else None,
                               "constants": _bn_constants_getter(bn) if bn is not None else None,
                               "kind": "3x3" if dense3 else ("g3x3" if group3 else "1x1"), "sliced": bool(dense3 and _wino_sliced(b))}
+            if dense3 and _is_narrow3x3(b):
+                b._fq_pw_fused["narrow"] = True              # (fq_conv3x3_i8_narrow: fp32 on both sides, see the links below)
             if group3s2:
                 b._fq_pw_fused["stride"] = 2                 # (fq_gconv3x3_s2_i8; every other rule of kind "g3x3" holds)
             if bn is not None:
@@ -683,6 +697,8 @@ def fuse_inference(net, depthwise=True, pointwise_int8=True, stem=True, residual
             # own, `g_next` with stride 1 (fq_gconv3x3_i8_c16) and `g2_next` with stride 2 (fq_gconv3x3_s2_i8_c16;
             # convert_conv2d.handover_target follows both)
             nz = getattr(nxt, "_fq_pw_fused", None)
+            if fz.get("narrow") or (nz is not None and nz.get("narrow")):
+                continue                                     # (no code tensor on either side of fq_conv3x3_i8_narrow)
             if fz.get("kind") == "g3x3" or (nz is not None and nz.get("kind") == "g3x3"):
                 g3 = fz if fz.get("kind") == "g3x3" else nz
                 other = nz if g3 is fz else fz
