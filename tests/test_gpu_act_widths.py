@@ -44,6 +44,7 @@ QUIRK = collections.OrderedDict((("quirk4", 4),))
 IN_OUT = collections.OrderedDict((("in2-out2", (2, 2)), ("in4-out4", (4, 4)), ("in8-out4", (8, 4)), ("in4-out8", (4, 8))))
 IN_MID = collections.OrderedDict((("in4-mid4", (4, 4)), ("in8-mid4", (8, 4)), ("in4-mid8", (4, 8))))
 OPERANDS = collections.OrderedDict((("x4-x2_4", (4, 4)), ("x8-x2_4", (8, 4))))
+GROUPED_QUANTS = ("u8_bn_relu_u8", "s8_bias_s8")   # the grouped C16 cells: unsigned on both sides, signed on both sides
 
 CASES = collections.OrderedDict()
 
@@ -73,6 +74,13 @@ for kind, settings in (("u", UNSIGNED), ("s", SIGNED), ("q", QUIRK)):
              [case(P.test_conv3x3_i8_vs_oracle, STORED, case=c, mode=mode, width=wd) for c in ((2, 64, 64, 9, 11), (5, 64, 96, 3, 3))] +
              [case(P.test_conv3x3_i8_sliced_vs_oracle, STORED, case=c, mode="offline_s8_bias" if sg else "online_u8_bn_relu_wino",
                    width=wd) for c in ((2, 64, 64, 9, 11), (5, 64, 96, 3, 3))])
+        # fq_conv3x3_i8_narrow: two taps and one tap per K slab
+        _add("dense3x3", name, [case(V._narrow, STORED, case=c, mode="offline_s8_channel_w4_bias" if sg else "online_u8_bn_relu", width=wd)
+                                for c in V.C3N_SHAPES[:2]])
+        # the grouped forms between fp32 tensors, either stride, a shape per channels-per-group value
+        _add("grouped3x3", name,
+             [case(d, STORED, case=c, mode="offline_s8_channel_w4" if sg else "online_u8_bn_relu", width=wd)
+              for d, shapes in ((V.G1.test_gconv3x3_i8, V.G1_SHAPES[:4]), (V.G2._run, V.G2_SHAPES[:4])) for c in shapes])
         _add("depthwise3x3", name, [case(P._dwconv_case, STORED, shape=s, stride=st, mode="offline_signed" if sg else "bn_relu_online",
                                          width=wd) for s in V.DW_SHAPES for st in (1, 2)])
         if not sg:                                 # (the classifier's input is a ReLU's: unsigned codes, clipped at 0)
@@ -98,7 +106,12 @@ for name, (wd, owd) in IN_OUT.items():
          [case(C16.test_dense3x3_with_codes_on_both_sides, STORED, case=(2, 64, 64, 9, 11), signed=sg, width=wd, out_width=owd)
           for sg in (False, True)] +
          [case(C16.test_depthwise_between_two_code_tensors, STORED, case=c, signed=sg, width=wd, out_width=owd)
-          for c in ((3, 24, 9, 11, 1), (4, 40, 5, 6, 2)) for sg in (False, True)])
+          for c in ((3, 24, 9, 11, 1), (4, 40, 5, 6, 2)) for sg in (False, True)] +
+         # the grouped forms between code tensors, either stride, one slab and two, unsigned and signed on both sides (a launch
+         # that writes fp32 has no output width: it runs where its input width is not 8)
+         [case(d, STORED, case=c, io=io, quant=q, width=wd, out_width=owd)
+          for d, shapes in ((V.G1C.test_gconv3x3_i8_c16, V.G1_SHAPES[:2]), (V.G2C.test_gconv3x3_s2_c16, V.G2_SHAPES[:2]))
+          for c in shapes for io in V.G1C.IO for q in GROUPED_QUANTS if io.endswith("codes") or wd != 8])
 
 # the recompute pair (`mid_width`, `x_codes_out`), the folded front layer (`front_width`: its depthwise quantiser is the pair's
 # first, the 1x1 behind it the second) and the chained pair (`mid_codes_out`)
@@ -137,7 +150,7 @@ def test_family_at_width_under_regime(dev, ops, monkeypatch, family, setting, re
         if regime not in c.regimes:
             continue
         kw = dict(c.kwargs, regime=regime)
-        if c.driver is V._chain:
+        if c.driver in V.TAKES_MONKEYPATCH:
             kw["monkeypatch"] = monkeypatch
         try:
             c.driver(dev=dev, ops=ops, **kw)
@@ -149,7 +162,7 @@ def test_family_at_width_under_regime(dev, ops, monkeypatch, family, setting, re
 
 def test_codes_carry_their_width_and_a_launch_that_names_another_is_refused(dev, ops):
     """What `Codes16` records and `matches` compares: a producer told `out_codes["width"] = 4` hands over a tensor that says 4,
-    its consumers at width 4 - 1x1, dense 3x3, depthwise 3x3 - compute what they compute from the fp32
+    its consumers at width 4 - 1x1, dense 3x3, depthwise 3x3, grouped 3x3 of either stride - compute what they compute from the fp32
     tensor under that threshold, and every one of them refuses the same tensor under the same threshold at width 8 or 2 before
     anything is launched (the codes would be read against the wrong scale)."""
     import numpy as np
@@ -184,6 +197,17 @@ def test_codes_carry_their_width_and_a_launch_that_names_another_is_refused(dev,
     dw_f = ops.dwconv3x3(y, dww, in_thr=thr2, width=4, flags=0, act="relu")[0]
     wantc = O.ste_codes(N(dw_f), O.act_scale(np.float32(1.7), False, 8), np.float32(1.7), np.float32(0))
     P._eq(N(dw_c.t), O.to_c16(wantc.astype(np.int64), 128), "depthwise on four-bit codes")
+    # the grouped 3x3 consumers, either stride (they refuse with the library's error class, as they refuse a shape)
+    from quantization.mxnet_amd._lib import FakeQuantError
+    g3 = ops.weight_codes_g3x3(T((rng.standard_normal((c, 8, 3, 3)) * 0.1).astype(np.float32), dev), 8, 8)
+    gkw = dict(in_thr=thr2, flags=0, act="relu")
+    for stride, on_codes in ((1, ops.gconv3x3_i8), (2, ops.gconv3x3_s2_c16)):
+        g, gs = on_codes(yc, *g3, 8, width=4, **gkw)
+        r, rs = ops.gconv3x3_i8(y, *g3, 8, width=4, stride=stride, **gkw)
+        assert torch.equal(g, r) and torch.equal(gs, rs), "grouped 3x3, stride %d" % stride
+        for width in (8, 2):
+            with pytest.raises(FakeQuantError, match="width"):
+                on_codes(yc, *g3, 8, width=width, **gkw)
     for width in (8, 2):
         with pytest.raises(ValueError, match="width"):
             ops.pwconv_i8(yc, *pw, in_thr=thr2, width=width, flags=0)

@@ -5,6 +5,7 @@ import pytest
 import torch
 
 import poison
+import regimes as R
 from oracle import fq_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -48,9 +49,37 @@ def _dense(wt, groups):
     return wd
 
 
-@pytest.mark.parametrize("case", CASES, ids=["%dx%dg%d@%dx%d" % c for c in CASES])
-@pytest.mark.parametrize("mode", MODES)
-def test_gconv3x3_i8(dev, ops, case, mode):
+def _input_side(regime, rthr, x, stored, both=False):
+    """(launch keywords as host arrays, the threshold the launch quantises with).  `rthr` is what `R.apply` returned: the driver's
+    stored threshold, the regime's own in its place, the batch mean a regime without one leaves stored - or None, the launch works
+    online.  Routed as `_regime_threshold` of tests/test_gpu_parity.py routes it: a regime's own threshold turns an online launch
+    into a stored one - but for `boundaries`, which plants its threshold as every sample's maximum: that launch stays online and
+    divides by the same d.  `both`: a stored launch that is handed the statistic too (it only feeds cur_out)."""
+    stat = O.absmax_per_sample(x)
+    if rthr is not None and (stored or regime != "boundaries"):
+        kw = dict(in_thr=np.float32([rthr]))
+        if both:
+            kw["in_stat"] = stat
+        return kw, np.float32(rthr)
+    in_max = O.batch_mean(stat)
+    assert rthr is None or in_max == rthr
+    return dict(in_stat=stat), in_max
+
+
+def _up(kw, dev, T):
+    return {k: (T(v, dev) if isinstance(v, np.ndarray) else v) for k, v in kw.items()}
+
+
+def _fp64(xq, wq, groups, stride, bias=None):
+    """plain and high-precision: the fp64 grouped convolution of the two fake-quantised tensors"""
+    ref = torch.nn.functional.conv2d(torch.from_numpy(xq.astype(np.float64)), torch.from_numpy(wq.astype(np.float64)),
+                                     stride=stride, padding=1, groups=groups).numpy()
+    return ref if bias is None else ref + bias.astype(np.float64).reshape(1, -1, 1, 1)
+
+
+def _make(case, mode, regime=None, width=8, stride=1):
+    """What needs no device, for either stride: the data as drawn, turned into `regime` (tests/regimes.py) and checked against its
+    condition, the launch keywords as host arrays and both references at `width`."""
     n, c, groups, h, w = case
     cg = c // groups
     rng = np.random.default_rng(sum(case) + 11)
@@ -61,49 +90,56 @@ def test_gconv3x3_i8(dev, ops, case, mode):
     wt = (rng.standard_normal((c, cg, 3, 3)) * rng.uniform(0.05, 1.0, (c, 1, 1, 1))).astype(np.float32)
     wt_width = 4 if "w4" in mode else 8
     rps = 1 if "channel" in mode else (cg if "group" in mode else c)
-    codes, scales, rowsum = ops.weight_codes_g3x3(T(wt, dev), groups, rps, wt_width)
-    kw, okw = {}, {}
-    if mode.startswith("online"):
-        stat = O.absmax_per_sample(x)
-        kw.update(in_stat=T(stat, dev), width=8, flags=ops.act_flags(signed=signed))
-        okw.update(in_max=O.batch_mean(stat), signed=signed, width=8)
-    else:
-        thr = np.float32(2.3)
-        kw.update(in_thr=T(np.float32([thr]), dev), width=8, flags=ops.act_flags(signed=True))
-        okw.update(in_max=thr, signed=True, width=8)
+    stored = mode.startswith("offline")
+    assert signed or not stored                              # (the modes under a stored threshold are the signed ones)
+    x, wt, rthr = R.apply(regime, x, signed, wt, rps, np.float32(2.3) if stored else None, width=width)
+    kw, in_max = _input_side(regime, rthr, x, stored)
+    R.check(regime, x, in_max, signed, w=wt, rps=rps, wt_width=wt_width, taps=9, width=width)
+    okw = dict(in_max=in_max, signed=signed, width=width)
     if "bn_relu" in mode:
         sc = rng.uniform(0.3, 1.5, c).astype(np.float32)
         sh = rng.standard_normal(c).astype(np.float32)
-        kw.update(bn_scale=T(sc, dev), bn_shift=T(sh, dev), act="relu")
+        kw.update(bn_scale=sc, bn_shift=sh, act="relu")
         okw.update(bn_scale=sc, bn_shift=sh, act="relu")
     if "bias" in mode:
         b = rng.standard_normal(c).astype(np.float32)
-        kw.update(bias=T(b, dev))
+        kw.update(bias=b)
         okw.update(bias=b)
+    k = dict(case=case, cg=cg, signed=signed, x=x, wt=wt, rps=rps, wt_width=wt_width, width=width, kw=kw, okw=okw, ref=None)
+    # the project's bar: the dense oracle on the zero-expanded filter (zeros change no scale), bit for bit; a stride subsamples it
+    k["want"] = np.ascontiguousarray(O.conv3x3_i8(x, _dense(wt, groups), rps, wt_width, **okw)[:, :, ::stride, ::stride])
+    assert np.isfinite(k["want"]).all()
+    if "bn_relu" not in mode:
+        # (fp32 vs fp64 summation noise: the bound is scale-free, it holds under every regime and at every width)
+        wc, ws = O.weight_codes(wt, rps, wt_width)
+        wq = (wc.astype(np.float32) * ws[:, None]).astype(np.float32).reshape(wt.shape)
+        xq = O.ste_forward(x, O.act_scale(in_max, signed, width), in_max, -in_max if signed else 0.0)
+        k["ref"] = _fp64(xq, wq, groups, stride, okw.get("bias"))
+    return k
+
+
+@pytest.mark.parametrize("case", CASES, ids=["%dx%dg%d@%dx%d" % c for c in CASES])
+@pytest.mark.parametrize("mode", MODES)
+def test_gconv3x3_i8(dev, ops, case, mode, regime=None, width=8):
+    """`regime`: a value regime of tests/regimes.py, applied to the data as drawn (tests/test_gpu_value_regimes.py).
+    `width`: the activation width of the launch and of both references (tests/test_gpu_act_widths.py)."""
+    k = _make(case, mode, regime, width)
+    groups = case[2]
+    codes, scales, rowsum = ops.weight_codes_g3x3(T(k["wt"], dev), groups, k["rps"], k["wt_width"])
     cur = torch.zeros(1, device=dev)
-    y, stat_out = ops.gconv3x3_i8(T(x, dev), codes, scales, rowsum, groups, cur_out=cur, **kw)
+    y, stat_out = ops.gconv3x3_i8(T(k["x"], dev), codes, scales, rowsum, groups, cur_out=cur, width=width,
+                                  flags=ops.act_flags(signed=k["signed"]), **_up(k["kw"], dev, T))
     launch = ops.last_launch()
     got = y.cpu().numpy()
-    assert launch[0] == "gconv3x3" and launch[4] == cg, launch
+    assert launch[0] == "gconv3x3" and launch[4] == k["cg"], launch
     if case == CASES[-1]:
         assert launch[3] >= 2, "this case is here for a band of several blocks: %s" % (launch,)
-    # the project's bar: the dense oracle on the zero-expanded filter (zeros change no scale), bit for bit
-    want = O.conv3x3_i8(x, _dense(wt, groups), rps, wt_width, **okw)
-    np.testing.assert_array_equal(got, want)
+    np.testing.assert_array_equal(got, k["want"])
     np.testing.assert_array_equal(stat_out.cpu().numpy(), O.absmax_per_sample(got))
-    if "in_stat" in kw:
-        np.testing.assert_array_equal(cur.cpu().numpy(), np.float32([okw["in_max"]]))
-    if "bn_relu" in mode:
-        return
-    # plain and high-precision: the fp64 grouped convolution of the two fake-quantised tensors (fp32 vs fp64 summation noise)
-    wc, ws = O.weight_codes(wt, rps, wt_width)
-    wq = (wc.astype(np.float32) * ws[:, None]).astype(np.float32).reshape(wt.shape)
-    xq = O.ste_forward(x, O.act_scale(okw["in_max"], okw["signed"], 8), okw["in_max"], -okw["in_max"] if okw["signed"] else 0.0)
-    ref = torch.nn.functional.conv2d(torch.from_numpy(xq.astype(np.float64)), torch.from_numpy(wq.astype(np.float64)),
-                                     padding=1, groups=groups).numpy()
-    if "bias" in mode:
-        ref = ref + okw["bias"].reshape(1, -1, 1, 1)
-    np.testing.assert_allclose(got, ref, rtol=2e-5, atol=2e-5 * np.abs(ref).max())
+    if "in_stat" in k["kw"]:
+        np.testing.assert_array_equal(cur.cpu().numpy(), np.float32([k["okw"]["in_max"]]))
+    if k["ref"] is not None:
+        np.testing.assert_allclose(got, k["ref"], rtol=2e-5, atol=2e-5 * np.abs(k["ref"]).max())
 
 
 @pytest.mark.parametrize("pattern", poison.PATTERNS, ids=["0x%02X" % p for p in poison.PATTERNS])

@@ -6,7 +6,7 @@ import torch
 
 import poison
 from oracle import fq_oracle as O
-from test_gpu_gconv3x3 import MODES, T, _dense, dev, ops  # noqa: F401  (the stride-1 file's modes, fixtures and helpers)
+from test_gpu_gconv3x3 import MODES, T, _make, _up, dev, ops  # noqa: F401  (the stride-1 file's modes, fixtures and helpers)
 
 pytestmark = pytest.mark.gpu
 
@@ -24,54 +24,25 @@ CASES = [  # (n, C, groups, h, w)
     (2, 64, 8, 28, 28)]      # two slabs: a band of several blocks of 64 pixels
 
 
-def _run(dev, ops, case, mode, want_pt=None):
+def _run(dev, ops, case, mode, want_pt=None, regime=None, width=8):
+    """`regime`, `width`: as in the stride-1 file, whose device-free half makes the data and both references for this stride too."""
     n, c, groups, h, w = case
-    cg, signed, rng = c // groups, "s8" in mode, np.random.default_rng(sum(case) + 11)
-    x = (rng.standard_normal((n, c, h, w)) * 2).astype(np.float32)
-    x = x if signed else np.maximum(x, 0)
-    wt = (rng.standard_normal((c, cg, 3, 3)) * rng.uniform(0.05, 1.0, (c, 1, 1, 1))).astype(np.float32)
-    wt_width, rps = 4 if "w4" in mode else 8, 1 if "channel" in mode else (cg if "group" in mode else c)
-    codes, scales, rowsum = ops.weight_codes_g3x3(T(wt, dev), groups, rps, wt_width)
-    kw, okw = {}, {}
-    if mode.startswith("online"):
-        stat = O.absmax_per_sample(x)
-        kw.update(in_stat=T(stat, dev), width=8, flags=ops.act_flags(signed=signed))
-        okw.update(in_max=O.batch_mean(stat), signed=signed, width=8)
-    else:
-        thr = np.float32(2.3)
-        kw.update(in_thr=T(np.float32([thr]), dev), width=8, flags=ops.act_flags(signed=True))
-        okw.update(in_max=thr, signed=True, width=8)
-    if "bn_relu" in mode:
-        sc, sh = rng.uniform(0.3, 1.5, c).astype(np.float32), rng.standard_normal(c).astype(np.float32)
-        kw.update(bn_scale=T(sc, dev), bn_shift=T(sh, dev), act="relu")
-        okw.update(bn_scale=sc, bn_shift=sh, act="relu")
-    if "bias" in mode:
-        b = rng.standard_normal(c).astype(np.float32)
-        kw.update(bias=T(b, dev))
-        okw.update(bias=b)
+    k = _make(case, mode, regime, width, stride=2)
+    codes, scales, rowsum = ops.weight_codes_g3x3(T(k["wt"], dev), groups, k["rps"], k["wt_width"])
     cur = torch.zeros(1, device=dev)
-    y, stat_out = ops.gconv3x3_i8(T(x, dev), codes, scales, rowsum, groups, cur_out=cur, stride=2, **kw)
+    y, stat_out = ops.gconv3x3_i8(T(k["x"], dev), codes, scales, rowsum, groups, cur_out=cur, stride=2, width=width,
+                                  flags=ops.act_flags(signed=k["signed"]), **_up(k["kw"], dev, T))
     launch, got = ops.last_launch(), y.cpu().numpy()              # (family, WC, PT, NB, CG)
-    assert launch[0] == "gconv3x3s2" and launch[4] == cg, launch
+    assert launch[0] == "gconv3x3s2" and launch[4] == k["cg"], launch
     assert launch[1:3] == ((1, 4) if c == 32 else (2, want_pt or 2)), launch      # one slab: WC 1, four pixel tiles
     if h == 28:
         assert launch[3] >= 2 and n * 196 > 32 * launch[2], "this case is here for a band of several blocks: %s" % (launch,)
-    want = O.conv3x3_i8(x, _dense(wt, groups), rps, wt_width, **okw)[:, :, ::2, ::2]
-    np.testing.assert_array_equal(got, want)
+    np.testing.assert_array_equal(got, k["want"])
     np.testing.assert_array_equal(stat_out.cpu().numpy(), O.absmax_per_sample(got))
-    if "in_stat" in kw:
-        np.testing.assert_array_equal(cur.cpu().numpy(), np.float32([okw["in_max"]]))
-    if "bn_relu" in mode:
-        return
-    # plain and high-precision: the fp64 strided grouped convolution of the two fake-quantised tensors
-    wc, ws = O.weight_codes(wt, rps, wt_width)
-    wq = (wc.astype(np.float32) * ws[:, None]).astype(np.float32).reshape(wt.shape)
-    xq = O.ste_forward(x, O.act_scale(okw["in_max"], okw["signed"], 8), okw["in_max"], -okw["in_max"] if okw["signed"] else 0.0)
-    ref = torch.nn.functional.conv2d(torch.from_numpy(xq.astype(np.float64)), torch.from_numpy(wq.astype(np.float64)),
-                                     stride=2, padding=1, groups=groups).numpy()
-    if "bias" in mode:
-        ref = ref + okw["bias"].reshape(1, -1, 1, 1)
-    np.testing.assert_allclose(got, ref, rtol=2e-5, atol=2e-5 * np.abs(ref).max())
+    if "in_stat" in k["kw"]:
+        np.testing.assert_array_equal(cur.cpu().numpy(), np.float32([k["okw"]["in_max"]]))
+    if k["ref"] is not None:        # plain and high-precision: the fp64 strided grouped convolution of the two fake-quantised tensors
+        np.testing.assert_allclose(got, k["ref"], rtol=2e-5, atol=2e-5 * np.abs(k["ref"]).max())
 
 
 @pytest.mark.parametrize("case", CASES, ids=["%dx%dg%d@%dx%d" % c for c in CASES])

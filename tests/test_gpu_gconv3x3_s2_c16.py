@@ -1,92 +1,35 @@
 """fq_gconv3x3_s2_i8_c16: the stride-2 grouped 3x3 convolution with C16 code tensors on either side - bit for bit the subsampled
 dense oracle on the zero-expanded filter followed by the consumer's quantiser, and within one code step of an fp64 strided grouped
 convolution."""
-import functools
-
 import numpy as np
 import pytest
 import torch
 
 import poison
+import test_gpu_gconv3x3_c16 as S1
 from oracle import fq_oracle as O
-from test_gpu_gconv3x3 import T, _dense, dev, ops  # noqa: F401  (fixtures and helpers of the fp32 form)
+from test_gpu_gconv3x3 import T, dev, ops  # noqa: F401  (fixtures and helpers of the fp32 form)
 from test_gpu_gconv3x3_c16 import IN_THR, IO, QUANT     # the stride-1 file's io forms and quantiser cells
 from test_gpu_gconv3x3_s2 import CASES                  # the eleven shapes of the fp32 stride-2 form
 
 pytestmark = pytest.mark.gpu
 
 
-@functools.lru_cache(maxsize=None)
-def _expected(case, quant):
-    """Inputs and both references of one (shape, quantiser) cell, computed once for its three io forms."""
-    n, c, groups, h, w = case
-    cg = c // groups
-    signed, epi, out_width, out_signed = QUANT[quant]
-    rng = np.random.default_rng(sum(case) + 29)
-    x = (rng.standard_normal((n, c, h, w)) * 2).astype(np.float32)
-    if not signed:
-        x = np.maximum(x, 0)
-    wt = (rng.standard_normal((c, cg, 3, 3)) * rng.uniform(0.05, 1.0, (c, 1, 1, 1))).astype(np.float32)
-    rps = 1 if signed else cg
-    e = dict(x=x, wt=wt, rps=rps, okw=dict(in_max=IN_THR, signed=signed, width=8))
-    if epi == "bn_relu":
-        e["sc"], e["sh"] = rng.uniform(0.3, 1.5, c).astype(np.float32), rng.standard_normal(c).astype(np.float32)
-        e["okw"].update(bn_scale=e["sc"], bn_shift=e["sh"], act="relu")
-    else:
-        e["b"] = rng.standard_normal(c).astype(np.float32)
-        e["okw"].update(bias=e["b"])
-    e["cx"] = O.ste_codes(x, O.act_scale(IN_THR, signed, 8), IN_THR, -IN_THR if signed else np.float32(0))
-    # the project's bar: the dense oracle on the zero-expanded filter, subsampled, then the consumer's quantiser
-    want = e["want"] = np.ascontiguousarray(O.conv3x3_i8(x, _dense(wt, groups), rps, 8, **e["okw"])[:, :, ::2, ::2])
-    thr2 = e["thr2"] = np.float32(0.6) * np.abs(want).max()
-    lo2 = -thr2 if out_signed else np.float32(0)
-    s2 = O.act_scale(thr2, out_signed, out_width)
-    e["want_codes"] = O.ste_codes(want, s2, thr2, lo2)
-    # plain and high-precision: the fp64 strided grouped convolution of the two fake-quantised tensors, the epilogue in fp64
-    wc, ws = O.weight_codes(wt, rps, 8)
-    wq = (wc.astype(np.float32) * ws[:, None]).astype(np.float32).reshape(wt.shape)
-    xq = (e["cx"] * O.act_scale(IN_THR, signed, 8)).astype(np.float32)
-    ref = torch.nn.functional.conv2d(torch.from_numpy(xq.astype(np.float64)), torch.from_numpy(wq.astype(np.float64)),
-                                     stride=2, padding=1, groups=groups).numpy()
-    if epi == "bn_relu":
-        ref = np.maximum(ref * e["sc"].astype(np.float64).reshape(1, -1, 1, 1) + e["sh"].astype(np.float64).reshape(1, -1, 1, 1), 0)
-    else:
-        ref = ref + e["b"].astype(np.float64).reshape(1, -1, 1, 1)
-    e["ref"] = ref
-    q = np.clip(ref, float(lo2), float(thr2)) / (float(s2) + 1e-10)
-    e["ref_codes"] = np.sign(q) * np.floor(np.abs(q) + 0.5)
-    return e
-
-
-def _codes_within_cap(codes, ref_codes):
-    """The condition on a code output: no code more than one step off the fp64 reference's, at most 1 in 1000 off at all."""
-    diff = np.abs(codes - ref_codes)
-    print("codes off the fp64 reference: %d of %d, largest step %d" % ((diff != 0).sum(), diff.size, diff.max()))
-    return diff.max() <= 1 and (diff != 0).sum() * 1000 <= diff.size
+def _expected(case, quant, regime=None, width=8, out_width=None):
+    """Inputs and both references of one (shape, quantiser, regime, widths) cell, computed once for its three io forms: the
+    stride-1 file's, with this file's seed, subsampled."""
+    return S1._expected(case, quant, regime, width, out_width, stride=2)
 
 
 @pytest.mark.parametrize("case", CASES, ids=["%dx%dg%d@%dx%d" % c for c in CASES])
 @pytest.mark.parametrize("io", IO)
 @pytest.mark.parametrize("quant", list(QUANT))
-def test_gconv3x3_s2_c16(dev, ops, case, io, quant):
+def test_gconv3x3_s2_c16(dev, ops, case, io, quant, regime=None, width=8, out_width=None):
+    """`regime`, `width`, `out_width`: as in the stride-1 file."""
     n, c, groups, h, w = case
-    signed, epi, out_width, out_signed = QUANT[quant]
-    e = _expected(case, quant)
-    in16, out16 = io.startswith("codes"), io.endswith("codes")
+    e = _expected(case, quant, regime, width, out_width)
     codes, scales, rowsum = ops.weight_codes_g3x3(T(e["wt"], dev), groups, e["rps"], 8)
-    thr_t = T(np.float32([IN_THR]), dev)
-    flags = ops.act_flags(signed=signed)
-    kw = dict(in_thr=thr_t, width=8, flags=flags)
-    if signed:                                           # (offline with the statistic: it only feeds cur_out)
-        kw.update(in_stat=T(O.absmax_per_sample(e["x"]), dev))
-    if epi == "bn_relu":
-        kw.update(bn_scale=T(e["sc"], dev), bn_shift=T(e["sh"], dev), act="relu")
-    else:
-        kw.update(bias=T(e["b"], dev))
-    if out16:
-        kw.update(out_codes=dict(thr=T(np.float32([e["thr2"]]), dev), width=out_width, flags=ops.act_flags(signed=out_signed)))
-    xa = ops.Codes16(T(O.to_c16(e["cx"].astype(np.int64), 0 if signed else 128), dev), e["x"].shape, thr_t, 8, flags) if in16 \
-        else T(e["x"], dev)
+    xa, kw, in16, out16 = S1._launch_args(e, quant, io, dev, ops, T)
     cur = torch.zeros(1, device=dev)
     y, stat_out = ops.gconv3x3_s2_c16(xa, codes, scales, rowsum, groups, cur_out=cur, **kw)
     launch = ops.last_launch()                           # (family, WC, PT, NB, CG, IN16, OUT16, NW)
@@ -94,19 +37,7 @@ def test_gconv3x3_s2_c16(dev, ops, case, io, quant):
     assert launch[1:3] == ((1, 4) if c == 32 else (2, 2)), launch
     if h == 28:
         assert launch[3] >= 2 and n * 196 > 32 * launch[2], "this case is here for a band of several blocks: %s" % (launch,)
-    np.testing.assert_array_equal(stat_out.cpu().numpy(), O.absmax_per_sample(e["want"]))
-    if signed:
-        np.testing.assert_array_equal(cur.cpu().numpy(), np.float32([O.batch_mean(O.absmax_per_sample(e["x"]))]))
-    if not out16:
-        got = y.cpu().numpy()
-        np.testing.assert_array_equal(got, e["want"])
-        np.testing.assert_allclose(got, e["ref"], rtol=2e-5, atol=2e-5 * np.abs(e["ref"]).max())
-        return
-    assert isinstance(y, ops.Codes16) and y.shape == e["want"].shape and y.width == out_width
-    zoff = 0 if out_signed else 128
-    got = y.t.cpu().numpy()
-    assert np.array_equal(got, O.to_c16(e["want_codes"].astype(np.int64), zoff)), "codes of the grouped output"
-    assert _codes_within_cap(O.from_c16(got, c, *e["want"].shape[2:], zoff), e["ref_codes"])
+    S1._compare(e, quant, regime, y, stat_out, cur, out16, ops)
 
 
 def test_gconv3x3_s2_c16_larger_blocks(dev, ops, monkeypatch):

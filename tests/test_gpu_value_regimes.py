@@ -18,8 +18,13 @@ import torch
 
 import regimes as R
 import test_gpu_c16 as C16
+import test_gpu_conv3x3_narrow as NARROW
 import test_gpu_front_dw as FRONT
 import test_gpu_gap as GAP
+import test_gpu_gconv3x3 as G1
+import test_gpu_gconv3x3_c16 as G1C
+import test_gpu_gconv3x3_s2 as G2
+import test_gpu_gconv3x3_s2_c16 as G2C
 import test_gpu_pair_chain as CHAIN
 import test_gpu_parity as P
 import test_gpu_poison as POISON
@@ -98,6 +103,11 @@ def _chain(dev, ops, monkeypatch, case, signed, regime, width=8, mid_width=8):
     want, host = CHAIN._stored(k, dev, ops), CHAIN._host_mid_codes(k, ops, dev)
     got = CHAIN._chained(k, dev, ops)
     CHAIN._compare(got, want, host, regime=regime)
+
+
+def _narrow(dev, ops, monkeypatch, case, mode, regime, width=8):
+    """fq_conv3x3_i8_narrow (tests/test_gpu_conv3x3_narrow.py), the fp64 convolution wherever no BatchNorm follows."""
+    NARROW._run(dev, ops, case, mode, monkeypatch, fp64="bn" not in mode, regime=regime, width=width)
 
 
 def _gemm_extremes(dev, ops, n, l, k, cout, zoff):
@@ -212,6 +222,12 @@ PW_LARGE = [("two_kernels", (2, 960, 320, 7, 7), ("online_u8_layer",)),
 DW_SHAPES = [(2, 8, 7, 7), (3, 16, 14, 14), (2, 32, 28, 28), (1, 3, 9, 11), (5, 4, 7, 3), (1, 2, 30, 70)]
 PAIR_CASES = [(2, 32, 64, 40, 36, 1), (2, 32, 32, 30, 32, 2)]
 C3_SHAPES = [(5, 64, 96, 3, 3), (9, 256, 32, 4, 4), (2, 64, 64, 9, 11)]        # (the first two reach the large sums: u8 / s8)
+C3N_SHAPES = [(2, 16, 16, 5, 7), (3, 32, 32, 9, 11), (5, 16, 40, 3, 3), (4, 32, 8, 1, 1), (2, 16, 16, 32, 32)]
+C3N_MODES = ("online_u8_bn_relu", "offline_s8_channel_w4_bias", "online_s8_plain")
+# (n, C, groups, h, w): channels per group 4, 8 (blocks that span samples), 16 (a ragged slab count), 32, and the second panel
+G1_SHAPES = [(2, 32, 8, 5, 6), (3, 64, 8, 7, 7), (2, 96, 6, 9, 11), (1, 128, 4, 14, 14), (2, 32, 8, 28, 28)]
+G2_SHAPES = [(2, 32, 8, 5, 7), (3, 64, 8, 6, 8), (2, 96, 6, 9, 11), (1, 128, 4, 14, 14), (2, 32, 8, 28, 28)]
+G_MODES = ("online_u8_bn_relu", "offline_s8_channel_w4", "online_s8_bias")
 
 CASES = collections.OrderedDict()
 
@@ -253,7 +269,22 @@ CASES["dense3x3"] = (
     [case(P.test_conv3x3_i8_sliced_vs_oracle, IN, case=c, mode=m)
      for c in C3_SHAPES for m in ("online_u8_bn_relu_wino", "offline_s8_bias")] +
     [case(C16.test_dense3x3_with_codes_on_both_sides, IN + OUT, case=c, signed=sg)
-     for c in C3_SHAPES[::2] for sg in (False, True)])
+     for c in C3_SHAPES[::2] for sg in (False, True)] +
+    # fq_conv3x3_i8_narrow: both tap arrangements, a block that spans samples under a partial channel tile, one-pixel planes,
+    # the second panel
+    [case(_narrow, IN, case=c, mode=m) for c in C3N_SHAPES for m in C3N_MODES] +
+    [case(_narrow, IN, case=C3N_SHAPES[0], mode="both_u8_bn")])
+
+# the four grouped forms.  K <= 9 * 32 = 288 and 288 * 255 * 127 < 2^24: `saturated` pins clipping and the re-centring of unsigned
+# codes here, not the int32 -> fp32 conversion.  All three sides of `fq_nonneg`: unsigned, signed with lo = -max, signed under W4
+# per channel; the regimes with a threshold of their own turn an online mode into a stored one (`boundaries` stays online).
+# An output-side regime says nothing about a launch that writes fp32: it goes to the two io forms that write codes.
+CASES["grouped3x3"] = (
+    [case(G1.test_gconv3x3_i8, IN, case=c, mode=m) for c in G1_SHAPES for m in G_MODES] +
+    [case(G2._run, IN, case=c, mode=m) for c in G2_SHAPES for m in G_MODES] +
+    [case(d, IN + (OUT if io.endswith("codes") else ()), case=c, io=io, quant=q)
+     for d, shapes in ((G1C.test_gconv3x3_i8_c16, G1_SHAPES), (G2C.test_gconv3x3_s2_c16, G2_SHAPES))
+     for c in shapes for io in G1C.IO for q in ("u8_bn_relu_u8", "s8_bias_s8")])
 
 CASES["depthwise3x3"] = (
     [case(P._dwconv_case, IN, shape=s, stride=st, mode=m)
@@ -288,6 +319,18 @@ CASES["qconv2d"] = [case(_qconv_range, ("tiny", "huge"))]
 
 # drivers that take the regime by that name; the others (`_gemm_extremes`) ARE their regime
 _TAKES_REGIME = lambda c: c.driver is not _gemm_extremes      # noqa: E731
+TAKES_MONKEYPATCH = (_chain, _narrow)
+
+# the grouped and the narrow drivers: driver -> its half that needs no device (data, regime, condition, references), for the CPU
+# tables of tests/test_value_regimes_host.py and tests/test_act_widths_host.py
+DEVICE_FREE = {
+    _narrow: lambda case, mode, regime=None, width=8: NARROW._make(case, mode, regime, width),
+    G1.test_gconv3x3_i8: lambda case, mode, regime=None, width=8: G1._make(case, mode, regime, width),
+    G2._run: lambda case, mode, regime=None, width=8: G1._make(case, mode, regime, width, stride=2),
+    G1C.test_gconv3x3_i8_c16: lambda case, io, quant, regime=None, width=8, out_width=None:
+        G1C._expected(case, quant, regime, width, out_width),
+    G2C.test_gconv3x3_s2_c16: lambda case, io, quant, regime=None, width=8, out_width=None:
+        G2C._expected(case, quant, regime, width, out_width)}
 
 
 def regimes_of(family):
@@ -334,7 +377,7 @@ def test_family_under_regime(dev, ops, monkeypatch, family, regime):
         kw = dict(c.kwargs)
         if _TAKES_REGIME(c):
             kw["regime"] = regime
-        if c.driver is _chain:
+        if c.driver in TAKES_MONKEYPATCH:
             kw["monkeypatch"] = monkeypatch
         try:
             c.driver(dev=dev, ops=ops, **kw)

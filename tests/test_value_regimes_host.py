@@ -30,6 +30,7 @@ MAX_MACS = 3e7                                    # the numpy einsum of the larg
 APPLIES = {
     "pointwise1x1": R.INPUT + R.OUTPUT,
     "dense3x3": R.INPUT + R.OUTPUT,
+    "grouped3x3": R.INPUT + R.OUTPUT,
     "depthwise3x3": R.INPUT + R.OUTPUT,
     "recompute_pair": R.INPUT,
     "head": R.INPUT,
@@ -111,6 +112,12 @@ def test_family_under_regime_on_the_references(family, regime):
                 FRONT._make(c.kwargs["case"], c.kwargs["mode"], regime=regime)
             elif c.driver is V._chain:
                 CHAIN._make(c.kwargs["case"], c.kwargs["signed"], regime=regime)
+            elif c.driver in V.DEVICE_FREE:
+                # (the grouped and the narrow forms: the regime's condition on their data, and a finite output of the oracle)
+                try:
+                    V.DEVICE_FREE[c.driver](regime=regime, **c.kwargs)
+                except AssertionError as e:
+                    raise AssertionError("regime %s, %s: %s" % (regime, V._describe(c), e)) from e
             elif c.driver in HOST_DRIVERS and _macs(c) <= MAX_MACS:
                 try:
                     c.driver(dev=dev, ops=ops, regime=regime, **c.kwargs)
@@ -195,3 +202,20 @@ def test_every_family_has_a_case_under_every_regime_that_applies_to_it():
                    for cs in V.CASES.values() for c in cs), driver.__name__
     # the pair's fused kernel (at most 256 input channels) and the streaming form (K <= 256) cannot
     assert not R.reaches_large_sums(256, False)
+    # ... nor the grouped and the narrow 3x3 forms: K <= 9 * 32
+    assert not R.reaches_large_sums(288, False)
+    # the grouped forms and the narrow kernel meet all three sides of fq_nonneg, a bias and BatchNorm + ReLU; an all-zero sample
+    # lies inside a pixel block that spans samples
+    for driver in (V.G1.test_gconv3x3_i8, V.G2._run, V._narrow):
+        cs = [c for cs in V.CASES.values() for c in cs if c.driver is driver]
+        assert {"online_u8_bn_relu", "online_s8_bias" if driver is not V._narrow else "online_s8_plain"} <= {c.kwargs["mode"] for c in cs}
+        assert any("s8_channel_w4" in c.kwargs["mode"] for c in cs) and any("bias" in c.kwargs["mode"] for c in cs)
+        assert all("saturated" in c.regimes and "boundaries" in c.regimes for c in cs)
+    spans = {V._narrow: (5, 16, 40, 3, 3), V.G1.test_gconv3x3_i8: (3, 64, 8, 7, 7), V.G1C.test_gconv3x3_i8_c16: (3, 64, 8, 7, 7)}
+    for driver, shape in spans.items():
+        assert any(c.driver is driver and c.kwargs["case"] == shape and "zero_sample" in c.regimes
+                   for cs in V.CASES.values() for c in cs), driver.__name__
+    for driver in (V.G1C.test_gconv3x3_i8_c16, V.G2C.test_gconv3x3_s2_c16):
+        ios = {(c.kwargs["io"], r) for c in V.CASES["grouped3x3"] if c.driver is driver for r in c.regimes}
+        assert {(io, r) for io in V.G1C.IO for r in R.INPUT} <= ios
+        assert {(io, r) for io in V.G1C.IO[::2] for r in R.OUTPUT} <= ios
