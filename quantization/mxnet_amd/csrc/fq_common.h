@@ -21,6 +21,8 @@
 //   fq_conv3x3_narrow.hip K2w dense 3x3 on int8 codes for 16 and 32 input channels (the first two stages of the CIFAR ResNets)
 //   fq_gconv3x3.hip    K2g grouped 3x3 on int8 codes (the ResNeXt units); fq_gconv3x3_s2.hip K2g2: stride 2; fq_gconv3x3_16.hip
 //                      K2gc: stride 1 between C16 code tensors; fq_gconv3x3_s2_16.hip K2g2c: stride 2 between them
+//   fq_gconv.h         (header) what those four share: geometry, LDS budget, work items, regions, A fragments, constant tables,
+//                      quantiser, call struct and launcher; the entry points' argument checks, plan and statistic zeroing
 //   fq_pw_stream.hip   K2h pointwise on int8 codes, weights resident in LDS (largest planes)
 //   fq_pw_sample.hip   K2r pointwise, one block of 96..128 pixels x 256 / 512 channels per workgroup, output-stationary
 //   fq_pw_split.hip    K2m pointwise, one (pixel tile, channel group) per workgroup: every other layer from 28x28 planes down;

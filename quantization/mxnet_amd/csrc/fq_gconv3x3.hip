@@ -1,7 +1,7 @@
 // libfakequant — K2g grouped 3x3 convolution (stride 1, pad 1, 4 .. 32 channels per group) on int8 codes: the 3x3 layers of the
-// ResNeXt bottlenecks (see fq_common.h for the list of translation units and the design rules)
-#include "fq_mma.h"
-#include "fq_common.h"
+// ResNeXt bottlenecks (see fq_common.h for the list of translation units and the design rules; what the four grouped kernels
+// share - geometry, work items, regions, A fragments, quantiser, launch, the entry points' checks and plan: fq_gconv.h)
+#include "fq_gconv.h"
 
 namespace {
 
@@ -24,34 +24,21 @@ namespace {
 //     through nine validity bits per lane and pixel tile; epilogue with lane = pixel: all as in the dense form.
 // Budget per wavefront: 36 (A) + 16 * PTW (accumulators) + 32 (two units in flight) + 8 (B) VGPRs; LDS 2 * RT * 32 * (32 WC + 16)
 // bytes - 40 KiB at W = 56 with WC = 2 - plus 20 * 32 * WC bytes of per-channel constants.
-struct GCGeom {
-  int C, H, W, HW;
-  int NSLAB, CS;             // slabs of 32 channels; slab groups = ceil(NSLAB / WC)
-  int NB;                    // pixel blocks per band
-  int RT, ROW;               // region tiles of 32 pixels; bytes per region pixel in a panel
-  int zoff;
-  int64_t cols, nblocks, items;   // n * HW; pixel blocks of 128; bands * CS
-};
-
 constexpr int kGcPT = 4;                         // pixel tiles of 32 per block
 constexpr int kGcNW = 4;
 
 template <int WC>
 __global__ __launch_bounds__(kGcNW * 64, 2) void gconv3x3_i8_kernel(
     const float* __restrict__ x, const int8_t* __restrict__ wfrag, const float* __restrict__ wscale,
-    const int* __restrict__ wsum, const float* __restrict__ bias, float* __restrict__ y, GCGeom g,
+    const int* __restrict__ wsum, const float* __restrict__ bias, float* __restrict__ y, GcGeom g,
     const float* __restrict__ in_stat, int n, const float* __restrict__ in_thr, float levels, int lo_neg_max, float eps,
     float* __restrict__ cur_max_out, const float* __restrict__ bn_scale, const float* __restrict__ bn_shift, int act,
     float* __restrict__ stat_out) {
-  constexpr int NW = kGcNW, WP = NW / WC, PTW = kGcPT / WP, NCH = WC * 32, KTS = 10;
+  constexpr int NW = kGcNW, WP = NW / WC, PTW = kGcPT / WP, NCH = WC * 32, BPX = 32 * kGcPT;
   extern __shared__ __attribute__((aligned(16))) unsigned char gc_smem[];
   __shared__ unsigned k_stat[kStatSlots];
   const unsigned panel_bytes = (unsigned)g.RT * 32u * (unsigned)g.ROW;
-  float* c_sxw = reinterpret_cast<float*>(gc_smem + 2u * panel_bytes);
-  float* c_bsc = c_sxw + NCH;
-  float* c_bsh = c_bsc + NCH;
-  float* c_bias = c_bsh + NCH;
-  int* c_zs = reinterpret_cast<int*>(c_bias + NCH);
+  const GcTables ct = gc_tables<NCH>(gc_smem + 2u * panel_bytes);
 
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -59,33 +46,18 @@ __global__ __launch_bounds__(kGcNW * 64, 2) void gconv3x3_i8_kernel(
   const unsigned HW = (unsigned)g.HW, W = (unsigned)g.W, cols = (unsigned)g.cols;
   const unsigned plane4 = HW * 4u;
   const bool has_bn = bn_scale != nullptr, has_stat = stat_out != nullptr;
-  unsigned item;
+  unsigned item, blk0, blk1, s_band;
+  int slab0, ch0;
   if (!mma_xcd_item(g.items, item)) return;
-  const unsigned band = item / (unsigned)g.CS, sg = item - band * (unsigned)g.CS;
-  const int slab0 = (int)sg * WC;                                       // first slab of the workgroup
-  const int ch0 = slab0 * 32;
-  const unsigned blk0 = band * (unsigned)g.NB;
-  const unsigned blk1 = blk0 + (unsigned)g.NB < (unsigned)g.nblocks ? blk0 + (unsigned)g.NB : (unsigned)g.nblocks;
-  const unsigned s_band = blk0 * (32u * kGcPT) / HW;                    // first sample the band's OUTPUT touches
+  gc_work_item<WC, BPX>(g, HW, item, slab0, ch0, blk0, blk1, s_band);
   const int64_t samp = (int64_t)g.C * HW * 4;
   const int64_t n_samp = (int64_t)(cols / HW);
 
   // ---- a block's region -> a panel: units of (region tile of 32 pixels, slab), wave-strided; lane = pixel, 16 channels ------
   const int NU = g.RT * WC;
-  struct Region {
-    fq_rsrc xr;
-    int jr0;
-    unsigned n_base;
-  };
-  auto region_of = [&](unsigned blk) __attribute__((always_inline)) {
-    Region r;
-    r.jr0 = (int)(blk * (32u * kGcPT)) - (int)W - 1;                    // first pixel of the region (may be < 0)
-    r.n_base = (unsigned)(r.jr0 < 0 ? 0 : r.jr0) / HW;                  // first sample the region touches
-    r.xr = make_rsrc(reinterpret_cast<const char*>(x) + r.n_base * samp, (n_samp - r.n_base) * samp);
-    return r;
-  };
+  auto region_of = [&](unsigned blk) __attribute__((always_inline)) { return gc_region_of(x, blk, BPX, W, HW, samp, n_samp); };
   auto unit_ok = [&](int u) __attribute__((always_inline)) { return u < NU && slab0 + u % WC < g.NSLAB; };
-  auto issue = [&](const Region& r, int u, float (&v)[16]) __attribute__((always_inline)) {
+  auto issue = [&](const GcRegion& r, int u, float (&v)[16]) __attribute__((always_inline)) {
     const int rt = u / WC, s = u - rt * WC;
     int jr = r.jr0 + rt * 32 + pl;
     jr = jr < 0 ? 0 : (jr < (int)cols ? jr : (int)cols - 1);            // outside the tensor: any valid pixel (masked later)
@@ -97,7 +69,7 @@ __global__ __launch_bounds__(kGcNW * 64, 2) void gconv3x3_i8_kernel(
   float bufa[16], bufb[16];
   const ThresholdReq treq = threshold_request(in_stat, n, in_thr, item == 0);   // first in the memory queue (fq_common.h)
   FQ_PIN();
-  Region rg = region_of(blk0);
+  GcRegion rg = region_of(blk0);
   if (unit_ok(wave)) issue(rg, wave, bufa);                             // in flight during the set-up
   FQ_PIN();
   const float max_ = threshold_finish(treq, in_stat, n, in_thr, cur_max_out, item == 0);
@@ -105,29 +77,12 @@ __global__ __launch_bounds__(kGcNW * 64, 2) void gconv3x3_i8_kernel(
   const int zoff = g.zoff;
   const float sx = q.scale;
   mma_stat_init(k_stat);
-  for (int i = threadIdx.x; i < NCH; i += NW * 64) {
-    const bool ok = ch0 + i < g.C;
-    const int ic = ok ? ch0 + i : 0;
-    c_sxw[i] = ok ? sx * wscale[ic] : 0.0f;
-    c_zs[i] = ok ? zoff * wsum[ic] : 0;
-    c_bias[i] = ok && bias != nullptr ? bias[ic] : 0.0f;
-    c_bsc[i] = has_bn && ok ? bn_scale[ic] : (ok ? 1.0f : 0.0f);
-    c_bsh[i] = has_bn && ok ? bn_shift[ic] : 0.0f;
-  }
+  gc_fill_tables<NCH, NW * 64>(ct, ch0, g.C, sx, zoff, wscale, wsum, bias, bn_scale, bn_shift, has_bn);
   const int ubias = 128 - zoff;
   const unsigned nn_xor = fq_nonneg_xor(ubias);
   const bool nonneg = fq_nonneg(q);
-  // (non-negative quotients - unsigned activations - take the 5-instruction quantiser of fq_common.h)
   auto quant_to_panel = [&](unsigned char* panel, int u, const float (&v)[16]) __attribute__((always_inline)) {
-    v4i f;
-    if (nonneg) {
-#pragma unroll
-      for (int d = 0; d < 4; ++d) f[d] = fq_pack4<true>(v[4 * d + 0], v[4 * d + 1], v[4 * d + 2], v[4 * d + 3], q, ubias, nn_xor);
-    } else {
-#pragma unroll
-      for (int d = 0; d < 4; ++d) f[d] = fq_pack4<false>(v[4 * d + 0], v[4 * d + 1], v[4 * d + 2], v[4 * d + 3], q, ubias, nn_xor);
-    }
-    asm volatile("" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]));
+    const v4i f = gc_quant16(v, nonneg, q, ubias, nn_xor);
     const int rt = u / WC, s = u - rt * WC;
     *reinterpret_cast<v4i*>(panel + (size_t)(rt * 32 + pl) * g.ROW + s * 32 + 16 * h) = f;
   };
@@ -148,10 +103,8 @@ __global__ __launch_bounds__(kGcNW * 64, 2) void gconv3x3_i8_kernel(
   const int slab = slab0 + wc;
   const bool mine = slab < g.NSLAB;                                     // (a slab group wider than the layer: this wavefront
                                                                         // only helps to quantise)
-  const fq_rsrc wr = make_rsrc(wfrag + (((int64_t)slab * KTS) << 10), mine ? 9 * 1024 : 0);
   v4i afrag[9];
-#pragma unroll
-  for (int tap = 0; tap < 9; ++tap) afrag[tap] = buf_ld_v4i(wr, (unsigned)lane * 16u, (unsigned)(tap << 10));
+  gc_load_afrag(wfrag, slab, mine, lane, afrag);
   const int zb = stored_zero4(ubias);                                   // four codes "0" in the stored representation
   const float* fbias = bias;
   FQ_PIN();
@@ -162,10 +115,10 @@ __global__ __launch_bounds__(kGcNW * 64, 2) void gconv3x3_i8_kernel(
     const unsigned char* panel = gc_smem + cur * panel_bytes;
     unsigned char* other = gc_smem + (cur ^ 1u) * panel_bytes;
     const bool has_next = blk + 1 < blk1;
-    const unsigned j0 = blk * (32u * kGcPT);
+    const unsigned j0 = blk * (unsigned)BPX;
     const int jr0 = (int)j0 - (int)W - 1;
     const unsigned s_base = j0 / HW;                                    // first sample this block's output touches
-    Region nx = rg;
+    GcRegion nx = rg;
     if (has_next) nx = region_of(blk + 1);
     // per pixel tile: the lane's pixel, its nine tap-validity bits, its panel row
     unsigned smp[PTW], pp[PTW], tapmask[PTW], rbase[PTW];
@@ -199,16 +152,8 @@ __global__ __launch_bounds__(kGcNW * 64, 2) void gconv3x3_i8_kernel(
       if (mine) {
         const int shift = ((tap / 3 - 1) * (int)W + (tap % 3 - 1)) * g.ROW;   // wave-uniform
 #pragma unroll
-        for (int t = 0; t < PTW; ++t) {
-          const v4i raw = *reinterpret_cast<const v4i*>(panel + (unsigned)((int)rbase[t] + shift));
-          const bool tv = (tapmask[t] >> tap) & 1u;
-          v4i b;
-          b[0] = tv ? raw[0] : zb;
-          b[1] = tv ? raw[1] : zb;
-          b[2] = tv ? raw[2] : zb;
-          b[3] = tv ? raw[3] : zb;
-          acc[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(afrag[tap], b, acc[t], 0, 0, 0);
-        }
+        for (int t = 0; t < PTW; ++t)
+          gc_mma_tap(panel + (unsigned)((int)rbase[t] + shift), (tapmask[t] >> tap) & 1u, zb, afrag[tap], acc[t]);
       }
       FQ_PIN();
       if (has_next) {
@@ -245,12 +190,12 @@ __global__ __launch_bounds__(kGcNW * 64, 2) void gconv3x3_i8_kernel(
 #pragma unroll
         for (int gq = 0; gq < 4; ++gq) {
           const int c0 = cb + 8 * gq;
-          const v4i zs = *reinterpret_cast<const v4i*>(c_zs + c0);
-          const f4 sxw = *reinterpret_cast<const f4*>(c_sxw + c0);
-          const f4 bsc = *reinterpret_cast<const f4*>(c_bsc + c0);
-          const f4 bsh = *reinterpret_cast<const f4*>(c_bsh + c0);
+          const v4i zs = *reinterpret_cast<const v4i*>(ct.zs + c0);
+          const f4 sxw = *reinterpret_cast<const f4*>(ct.sxw + c0);
+          const f4 bsc = *reinterpret_cast<const f4*>(ct.bsc + c0);
+          const f4 bsh = *reinterpret_cast<const f4*>(ct.bsh + c0);
           f4 bch = (f4){0.f, 0.f, 0.f, 0.f};
-          if (BIAS_M == 1 || (BIAS_M < 0 && fbias != nullptr)) bch = *reinterpret_cast<const f4*>(c_bias + c0);
+          if (BIAS_M == 1 || (BIAS_M < 0 && fbias != nullptr)) bch = *reinterpret_cast<const f4*>(ct.bias + c0);
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             float v = (float)(acc[t][4 * gq + r] + zs[r]) * sxw[r];
@@ -274,20 +219,12 @@ __global__ __launch_bounds__(kGcNW * 64, 2) void gconv3x3_i8_kernel(
   }
 }
 
+constexpr GcEntry kGcEntry = {"fq_gconv3x3_i8", "fq_conv3x3_i8", 1, FQ_GCONV3X3_MAX_W, false};
+
 template <int WC>
-int gconv3x3_go(const float* x, const int8_t* wfrag, const float* wscale, const int32_t* wsum, const float* bias, float* y,
-                const GCGeom& g, int64_t grid, size_t lds, hipStream_t st, const float* in_stat, int n, const float* in_thr,
-                float levels, int lo_neg, float* out_current_max, const float* bn_scale, const float* bn_shift, int act,
-                float* stat_out, int cg) {
-  static const bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&gconv3x3_i8_kernel<WC>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) == hipSuccess;
-  FQ_REQUIRE(attr_ok, "fq_gconv3x3_i8: cannot raise the dynamic LDS limit");
-  hipLaunchKernelGGL((gconv3x3_i8_kernel<WC>), dim3((unsigned)grid), dim3(kGcNW * 64), lds, st, x, wfrag, wscale,
-                     (const int*)wsum, bias, y, g, in_stat, n, in_thr, levels, lo_neg, kEps, out_current_max, bn_scale,
-                     bn_shift, act, stat_out);
-  note_launch(FQ_KERNEL_GCONV3X3, FQ_LAUNCH_GCONV3X3, {WC, kGcPT / (kGcNW / WC), g.NB, cg});
-  FQ_LAUNCH_CHECK();
-  return FQ_OK;
+int gconv3x3_go(const GcCall& a, const GcGeom& g, int64_t grid, size_t lds, hipStream_t st) {
+  return gc_launch<&gconv3x3_i8_kernel<WC>>(kGcEntry.name, kGcNW * 64, FQ_LAUNCH_GCONV3X3, {WC, kGcPT / (kGcNW / WC), g.NB, a.cg}, a, g,
+                                            grid, lds, st);
 }
 
 }  // namespace
@@ -296,72 +233,26 @@ using namespace fqi;
 
 extern "C" {
 
-int fq_gconv3x3_i8_supported(int64_t cin, int64_t cout, int64_t groups) {
-  if (cin != cout || cin <= 0 || cin % 32 != 0 || groups <= 1 || cin % groups != 0) return 0;
-  const int64_t cg = cin / groups;
-  return (cg == 4 || cg == 8 || cg == 16 || cg == 32) ? 1 : 0;
-}
+int fq_gconv3x3_i8_supported(int64_t cin, int64_t cout, int64_t groups) { return gc_supported(cin, cout, groups); }
 
 int fq_gconv3x3_i8(const float* x, const int8_t* wcodes, const float* wscale, const int32_t* wsum, const float* bias,
                    float* y, int64_t n, int64_t c, int64_t groups, int64_t h, int64_t w, const float* in_stat,
                    const float* in_thr, int in_width, unsigned in_flags, float* out_current_max, const float* bn_scale,
                    const float* bn_shift, int act, float* stat_out, fqStream_t stream) {
-  FQ_REQUIRE(x && wcodes && wscale && wsum && y, "fq_gconv3x3_i8: null pointer");
-  FQ_REQUIRE(n > 0 && c > 0 && h > 0 && w > 0 && n * h * w < (1ll << 31) - 4096, "fq_gconv3x3_i8: bad shape");
-  FQ_REQUIRE(fq_gconv3x3_i8_supported(c, c, groups), "fq_gconv3x3_i8: %lld channels in %lld groups: the channel count must be "
-             "a multiple of 32 and a group 4, 8, 16 or 32 channels wide (groups == 1: fq_conv3x3_i8)", (long long)c,
-             (long long)groups);
-  FQ_REQUIRE(w <= FQ_GCONV3X3_MAX_W, "fq_gconv3x3_i8: planes up to %d pixels wide (got %lld)", FQ_GCONV3X3_MAX_W, (long long)w);
-  FQ_REQUIRE(in_stat != nullptr || in_thr != nullptr, "fq_gconv3x3_i8: give in_stat (online), in_thr (offline) or both "
-             "(offline, the statistic only feeds out_current_max)");
-  FQ_REQUIRE(in_thr != nullptr || out_current_max != nullptr, "fq_gconv3x3_i8: online mode needs out_current_max");
-  FQ_REQUIRE(in_width >= 2 && in_width <= 8, "fq_gconv3x3_i8: input width %d does not fit int8 codes", in_width);
-  FQ_REQUIRE(!(in_flags & (FQ_ACT_NO_ABS | FQ_ACT_NO_EPS)), "fq_gconv3x3_i8: unsupported activation flags");
-  FQ_REQUIRE((bn_scale == nullptr) == (bn_shift == nullptr), "fq_gconv3x3_i8: bn_scale and bn_shift go together");
-  const bool prezeroed = (act & FQ_STAT_PREZEROED) != 0;
-  act &= ~FQ_STAT_PREZEROED;
-  FQ_REQUIRE(act >= FQ_ACT_NONE && act <= FQ_ACT_RELU6, "fq_gconv3x3_i8: unknown activation %d", act);
-  FQ_REQUIRE(aligned16(wcodes) && aligned16(x), "fq_gconv3x3_i8: x and wcodes must be 16-byte aligned");
-  const int64_t hw = h * w, cols = n * hw;
-  const int blockpx = 32 * kGcPT;
-  // 32-bit lane offsets count from the first sample a block's region (input) or the block itself (output) touches
-  FQ_REQUIRE(((blockpx + 2 * w + 2) / hw + 2) * c * hw * 4 < (1ll << 31),
-             "fq_gconv3x3_i8: a pixel block and its halo must stay within 2 GiB of their first sample");
+  GcCall a = {x, nullptr, wscale, wsum, bias, y, in_stat, 0, in_thr, 0.0f, 0, out_current_max, bn_scale, bn_shift, act, stat_out,
+              nullptr, 0};
+  bool prezeroed;
+  if (int rc = gc_check(kGcEntry, a, wcodes, n, c, groups, h, w, in_width, in_flags, prezeroed)) return rc;
+  GcGeom g;
+  int64_t grid;
+  size_t lds;
+  // the band: four blocks per workgroup while that leaves two workgroups per compute unit, else two (FQ_GC_NB: tuning, read per call)
+  if (int rc = gc_plan(kGcEntry, a, wcodes, n, c, h, w, in_flags, kGcPT, 4, env_int("FQ_GC_NB", 0), 4, 4, g, grid, lds)) return rc;
   hipStream_t st = (hipStream_t)stream;
-  const int64_t row_pad = 320, rows_pad = (c + 63) / 64 * 64;            // fq_weight_codes' buffer of the (C, 3, 3, 32) filter
-  const int8_t* wfrag = wcodes + rows_pad * row_pad;                    // its fragment-major copy
-  const int nslab = (int)(c / 32);
-  const int wc = nslab >= 2 ? 2 : 1;
-  GCGeom g;
-  g.C = (int)c; g.H = (int)h; g.W = (int)w; g.HW = (int)hw;
-  g.NSLAB = nslab; g.CS = (nslab + wc - 1) / wc;
-  g.cols = cols; g.nblocks = (cols + blockpx - 1) / blockpx;
-  // the band: four blocks per workgroup while that leaves two workgroups per compute unit, else two - never one: a band of
-  // one block has nothing to load under its multiplies (FQ_GC_NB: tuning, read per call)
-  int nb = 4;
-  if (((g.nblocks + nb - 1) / nb) * g.CS < 2 * (int64_t)num_cu()) nb = 2;
-  const int tune = env_int("FQ_GC_NB", 0);
-  if (tune >= 1 && tune <= 64) nb = tune;
-  g.NB = nb;
-  g.items = ((g.nblocks + nb - 1) / nb) * g.CS;
-  const int rp = blockpx + 2 * (int)w + 2;
-  g.RT = (rp + 31) / 32; g.ROW = 32 * wc + 16;
-  g.zoff = (in_flags & FQ_ACT_SIGNED) ? 0 : 128;
-  const int64_t grid = (g.items + 7) / 8 * 8;
-  FQ_REQUIRE(grid < (1ll << 31), "fq_gconv3x3_i8: too many pixel blocks");
-  const size_t lds = 2 * (size_t)g.RT * 32 * g.ROW + (size_t)(32 * wc) * 5 * sizeof(float);
-  FQ_REQUIRE(lds <= 150 * 1024, "fq_gconv3x3_i8: two regions of %d pixels x %d channels do not fit LDS (planes up to %d wide)",
-             rp, 32 * wc, FQ_GCONV3X3_MAX_W);
-  const float levels = act_levels(in_width, in_flags);
-  const int lo_neg = (in_flags & FQ_ACT_LO_NEG_MAX) ? 1 : 0;
-  if (stat_out && !prezeroed) FQ_HIP(hipMemsetAsync(stat_out, 0, n * sizeof(float), st));
-  ProfScope prof(FQ_KERNEL_GCONV3X3, 8.0 * (double)n * c * hw, st);
-  const int cg = (int)(c / groups);
-  if (wc == 2)
-    return gconv3x3_go<2>(x, wfrag, wscale, wsum, bias, y, g, grid, lds, st, in_stat, (int)n, in_thr, levels, lo_neg,
-                          out_current_max, bn_scale, bn_shift, act, stat_out, cg);
-  return gconv3x3_go<1>(x, wfrag, wscale, wsum, bias, y, g, grid, lds, st, in_stat, (int)n, in_thr, levels, lo_neg,
-                        out_current_max, bn_scale, bn_shift, act, stat_out, cg);
+  if (int rc = gc_zero_stat(stat_out, prezeroed, n, st)) return rc;
+  ProfScope prof(FQ_KERNEL_GCONV3X3, 8.0 * (double)n * c * (h * w), st);
+  if (gc_slabs_per_group(c) == 2) return gconv3x3_go<2>(a, g, grid, lds, st);
+  return gconv3x3_go<1>(a, g, grid, lds, st);
 }
 
 }  // extern "C"

@@ -1,8 +1,8 @@
 // libfakequant — K2gc grouped 3x3 convolution (stride 1, pad 1, 4 .. 32 channels per group) between C16 code tensors
 // (fq_gconv3x3_i8_c16): the 3x3 layers of the ResNeXt bottlenecks under stored thresholds
-// (see fq_common.h for the list of translation units and the design rules; the fp32 -> fp32 form: fq_gconv3x3.hip)
-#include "fq_mma.h"
-#include "fq_common.h"
+// (see fq_common.h for the list of translation units and the design rules; the fp32 -> fp32 form: fq_gconv3x3.hip; what the
+// four grouped kernels share: fq_gconv.h)
+#include "fq_gconv.h"
 
 namespace {
 
@@ -24,48 +24,24 @@ namespace {
 //     the lane of half h owns block 2 slab + h of its pixel whole: one 16-byte store per lane and tile, 512 contiguous bytes
 //     per 32 pixels (FQ_GC16_ST4=1: the dense form's four 4-byte pieces, for the comparison).
 // The values are K2g's bit for bit: same sums, same epilogue chain, then the consumer's quantiser from fq_mma.h.
-struct GC16Geom {
-  int C, H, W, HW;
-  int NSLAB, CS;             // slabs of 32 channels; slab groups = ceil(NSLAB / WC)
-  int NB;                    // pixel blocks per band
-  int RT, ROW;               // region tiles of 32 pixels; bytes per region pixel in a panel
-  int zoff;
-  int CB;                    // 16-channel blocks of a C16 tensor = C / 16
-  int st4;                   // OUT16: 4-byte pieces instead of whole vectors
-  float out_levels;
-  int out_lo_neg, out_zoff;
-  int64_t cols, nblocks, items;   // n * HW; pixel blocks of 32 PT; bands * CS
-};
-
 constexpr int kG16NW = 4;
-constexpr int kG16LdsMax = 150 * 1024;
 // wavefronts per SIMD asked of the compiler: three with the small block and codes in; the fp32 fill carries K2g's 32 VGPRs of
 // values on their way to the quantiser and keeps K2g's two
 constexpr int g16_lb(int pt, bool in16) { return pt == 4 && in16 ? 3 : 2; }
-constexpr size_t g16_lds_bytes(int wc, int pt, int w) {
-  return 2 * (size_t)((32 * pt + 2 * w + 2 + 31) / 32) * 32 * (32 * wc + 16) + (size_t)(32 * wc) * 5 * sizeof(float);
-}
-// the panels are K2g's, so the widest plane is: both default instantiations (PT = 4) must fit
-static_assert(g16_lds_bytes(2, 4, FQ_GCONV3X3_C16_MAX_W) <= kG16LdsMax && g16_lds_bytes(1, 4, FQ_GCONV3X3_C16_MAX_W) <= kG16LdsMax,
-              "FQ_GCONV3X3_C16_MAX_W does not follow from the LDS budget");
 
 template <int WC, int PT, bool IN16, bool OUT16>
 __global__ __launch_bounds__(kG16NW * 64, g16_lb(PT, IN16)) void gconv3x3_c16_kernel(
     const void* __restrict__ x, const int8_t* __restrict__ wfrag, const float* __restrict__ wscale,
-    const int* __restrict__ wsum, const float* __restrict__ bias, void* __restrict__ y, GC16Geom g,
+    const int* __restrict__ wsum, const float* __restrict__ bias, void* __restrict__ y, GcGeom g,
     const float* __restrict__ in_stat, int n, const float* __restrict__ in_thr, float levels, int lo_neg_max, float eps,
     float* __restrict__ cur_max_out, const float* __restrict__ bn_scale, const float* __restrict__ bn_shift, int act,
     float* __restrict__ stat_out, const float* __restrict__ out_thr) {
-  constexpr int NW = kG16NW, WP = NW / WC, PTW = PT / WP, NCH = WC * 32, KTS = 10;
+  constexpr int NW = kG16NW, WP = NW / WC, PTW = PT / WP, NCH = WC * 32, BPX = 32 * PT;
   constexpr int UF = PT == 4 ? 4 : 6;                                   // IN16: units a wavefront keeps in flight
   extern __shared__ __attribute__((aligned(16))) unsigned char g16_smem[];
   __shared__ unsigned k_stat[kStatSlots];
   const unsigned panel_bytes = (unsigned)g.RT * 32u * (unsigned)g.ROW;
-  float* c_sxw = reinterpret_cast<float*>(g16_smem + 2u * panel_bytes);
-  float* c_bsc = c_sxw + NCH;
-  float* c_bsh = c_bsc + NCH;
-  float* c_bias = c_bsh + NCH;
-  int* c_zs = reinterpret_cast<int*>(c_bias + NCH);
+  const GcTables ct = gc_tables<NCH>(g16_smem + 2u * panel_bytes);
 
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -73,34 +49,19 @@ __global__ __launch_bounds__(kG16NW * 64, g16_lb(PT, IN16)) void gconv3x3_c16_ke
   const unsigned HW = (unsigned)g.HW, W = (unsigned)g.W, cols = (unsigned)g.cols;
   const unsigned plane4 = HW * 4u, plane16 = HW * 16u;
   const bool has_bn = bn_scale != nullptr, has_stat = stat_out != nullptr;
-  unsigned item;
+  unsigned item, blk0, blk1, s_band;
+  int slab0, ch0;
   if (!mma_xcd_item(g.items, item)) return;
-  const unsigned band = item / (unsigned)g.CS, sg = item - band * (unsigned)g.CS;
-  const int slab0 = (int)sg * WC;                                       // first slab of the workgroup
-  const int ch0 = slab0 * 32;
-  const unsigned blk0 = band * (unsigned)g.NB;
-  const unsigned blk1 = blk0 + (unsigned)g.NB < (unsigned)g.nblocks ? blk0 + (unsigned)g.NB : (unsigned)g.nblocks;
-  const unsigned s_band = blk0 * (32u * PT) / HW;                       // first sample the band's OUTPUT touches
+  gc_work_item<WC, BPX>(g, HW, item, slab0, ch0, blk0, blk1, s_band);
   const int64_t x_samp = IN16 ? (int64_t)g.CB * plane16 : (int64_t)g.C * plane4;
   const int64_t y_samp = OUT16 ? (int64_t)g.CB * plane16 : (int64_t)g.C * plane4;
   const int64_t n_samp = (int64_t)(cols / HW);
 
   // ---- a block's region -> a panel: units of (region tile of 32 pixels, slab), wave-strided; lane = pixel, 16 channels ------
   const int NU = g.RT * WC;
-  struct Region {
-    fq_rsrc xr;
-    int jr0;
-    unsigned n_base;
-  };
-  auto region_of = [&](unsigned blk) __attribute__((always_inline)) {
-    Region r;
-    r.jr0 = (int)(blk * (32u * PT)) - (int)W - 1;                       // first pixel of the region (may be < 0)
-    r.n_base = (unsigned)(r.jr0 < 0 ? 0 : r.jr0) / HW;                  // first sample the region touches
-    r.xr = make_rsrc(reinterpret_cast<const char*>(x) + r.n_base * x_samp, (n_samp - r.n_base) * x_samp);
-    return r;
-  };
+  auto region_of = [&](unsigned blk) __attribute__((always_inline)) { return gc_region_of(x, blk, BPX, W, HW, x_samp, n_samp); };
   auto unit_ok = [&](int u) __attribute__((always_inline)) { return u < NU && slab0 + u % WC < g.NSLAB; };
-  auto unit_pixel = [&](const Region& r, int u, unsigned& nr, unsigned& p) __attribute__((always_inline)) {
+  auto unit_pixel = [&](const GcRegion& r, int u, unsigned& nr, unsigned& p) __attribute__((always_inline)) {
     int jr = r.jr0 + (u / WC) * 32 + pl;
     jr = jr < 0 ? 0 : (jr < (int)cols ? jr : (int)cols - 1);            // outside the tensor: any valid pixel (masked later)
     nr = (unsigned)jr / HW;
@@ -112,7 +73,7 @@ __global__ __launch_bounds__(kG16NW * 64, g16_lb(PT, IN16)) void gconv3x3_c16_ke
   };
   // IN16: round k0 of a wavefront's units, wave + NW (k0 + k): one 16-byte vector of block 2 slab + h each
   v4i ub[UF];
-  auto issue16 = [&](const Region& r, int k0) __attribute__((always_inline)) {
+  auto issue16 = [&](const GcRegion& r, int k0) __attribute__((always_inline)) {
 #pragma unroll
     for (int k = 0; k < UF; ++k) {
       const int u = wave + NW * (k0 + k);
@@ -133,7 +94,7 @@ __global__ __launch_bounds__(kG16NW * 64, g16_lb(PT, IN16)) void gconv3x3_c16_ke
   };
   const int rounds = (NU + NW * UF - 1) / (NW * UF);                    // (one at 56x56 and below)
   // fp32 in: K2g's unit - sixteen loads, quantised, one ds_write_b128 - two in flight
-  auto issue32 = [&](const Region& r, int u, float (&v)[16]) __attribute__((always_inline)) {
+  auto issue32 = [&](const GcRegion& r, int u, float (&v)[16]) __attribute__((always_inline)) {
     unsigned nr, p;
     unit_pixel(r, u, nr, p);
     const unsigned xo = ((nr - r.n_base) * (unsigned)g.C + 16u * h) * plane4 + p * 4u;
@@ -143,7 +104,7 @@ __global__ __launch_bounds__(kG16NW * 64, g16_lb(PT, IN16)) void gconv3x3_c16_ke
   float bufa[IN16 ? 1 : 16], bufb[IN16 ? 1 : 16];
   const ThresholdReq treq = threshold_request(in_stat, n, in_thr, item == 0);   // first in the memory queue (fq_common.h)
   FQ_PIN();
-  Region rg = region_of(blk0);
+  GcRegion rg = region_of(blk0);
   if constexpr (IN16) {
     issue16(rg, 0);                                                     // in flight during the set-up
   } else {
@@ -155,34 +116,16 @@ __global__ __launch_bounds__(kG16NW * 64, g16_lb(PT, IN16)) void gconv3x3_c16_ke
   const int zoff = g.zoff;
   const float sx = q.scale;
   mma_stat_init(k_stat);
-  for (int i = threadIdx.x; i < NCH; i += NW * 64) {
-    const bool ok = ch0 + i < g.C;
-    const int ic = ok ? ch0 + i : 0;
-    c_sxw[i] = ok ? sx * wscale[ic] : 0.0f;
-    c_zs[i] = ok ? zoff * wsum[ic] : 0;
-    c_bias[i] = ok && bias != nullptr ? bias[ic] : 0.0f;
-    c_bsc[i] = has_bn && ok ? bn_scale[ic] : (ok ? 1.0f : 0.0f);
-    c_bsh[i] = has_bn && ok ? bn_shift[ic] : 0.0f;
-  }
+  gc_fill_tables<NCH, NW * 64>(ct, ch0, g.C, sx, zoff, wscale, wsum, bias, bn_scale, bn_shift, has_bn);
   const int ubias = 128 - zoff;
   const unsigned nn_xor = fq_nonneg_xor(ubias);
   const bool nonneg = fq_nonneg(q);
-  // (non-negative quotients - unsigned activations - take the 5-instruction quantiser of fq_common.h)
   auto quant_to_panel = [&](unsigned char* panel, int u, const float (&v)[16]) __attribute__((always_inline)) {
-    v4i f;
-    if (nonneg) {
-#pragma unroll
-      for (int d = 0; d < 4; ++d) f[d] = fq_pack4<true>(v[4 * d + 0], v[4 * d + 1], v[4 * d + 2], v[4 * d + 3], q, ubias, nn_xor);
-    } else {
-#pragma unroll
-      for (int d = 0; d < 4; ++d) f[d] = fq_pack4<false>(v[4 * d + 0], v[4 * d + 1], v[4 * d + 2], v[4 * d + 3], q, ubias, nn_xor);
-    }
-    asm volatile("" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]));
-    *panel_at(panel, u) = f;
+    *panel_at(panel, u) = gc_quant16(v, nonneg, q, ubias, nn_xor);
   };
   // a whole region, nothing to hide it under: the first one, and every region of the fp32 form (whose first unit is in flight);
   // IN16: from round k0 on, of which round `flying` is in flight already
-  auto fill = [&](const Region& r, unsigned char* panel, int k0, int flying) __attribute__((always_inline)) {
+  auto fill = [&](const GcRegion& r, unsigned char* panel, int k0, int flying) __attribute__((always_inline)) {
     if constexpr (IN16) {
       for (int k = k0; k < rounds * UF; k += UF) {
         if (k != flying) issue16(r, k);
@@ -210,10 +153,8 @@ __global__ __launch_bounds__(kG16NW * 64, g16_lb(PT, IN16)) void gconv3x3_c16_ke
   const int slab = slab0 + wc;
   const bool mine = slab < g.NSLAB;                                     // (a slab group wider than the layer: this wavefront
                                                                         // only helps to fill)
-  const fq_rsrc wr = make_rsrc(wfrag + (((int64_t)slab * KTS) << 10), mine ? 9 * 1024 : 0);
   v4i afrag[9];
-#pragma unroll
-  for (int tap = 0; tap < 9; ++tap) afrag[tap] = buf_ld_v4i(wr, (unsigned)lane * 16u, (unsigned)(tap << 10));
+  gc_load_afrag(wfrag, slab, mine, lane, afrag);
   const int zb = stored_zero4(ubias);                                   // four codes "0" in the stored representation
   const float* fbias = bias;
   // the consumer's quantiser of a C16 output (fq_mma.h)
@@ -227,10 +168,10 @@ __global__ __launch_bounds__(kG16NW * 64, g16_lb(PT, IN16)) void gconv3x3_c16_ke
     const unsigned char* panel = g16_smem + cur * panel_bytes;
     unsigned char* other = g16_smem + (cur ^ 1u) * panel_bytes;
     const bool has_next = blk + 1 < blk1;
-    const unsigned j0 = blk * (32u * PT);
+    const unsigned j0 = blk * (unsigned)BPX;
     const int jr0 = (int)j0 - (int)W - 1;
     const unsigned s_base = j0 / HW;                                    // first sample this block's output touches
-    Region nx = rg;
+    GcRegion nx = rg;
     if (has_next) nx = region_of(blk + 1);
     // per pixel tile: the lane's pixel, its nine tap-validity bits, its panel row
     unsigned smp[PTW], pp[PTW], tapmask[PTW], rbase[PTW];
@@ -268,16 +209,8 @@ __global__ __launch_bounds__(kG16NW * 64, g16_lb(PT, IN16)) void gconv3x3_c16_ke
       if (mine) {
         const int shift = ((tap / 3 - 1) * (int)W + (tap % 3 - 1)) * g.ROW;   // wave-uniform
 #pragma unroll
-        for (int t = 0; t < PTW; ++t) {
-          const v4i raw = *reinterpret_cast<const v4i*>(panel + (unsigned)((int)rbase[t] + shift));
-          const bool tv = (tapmask[t] >> tap) & 1u;
-          v4i b;
-          b[0] = tv ? raw[0] : zb;
-          b[1] = tv ? raw[1] : zb;
-          b[2] = tv ? raw[2] : zb;
-          b[3] = tv ? raw[3] : zb;
-          acc[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(afrag[tap], b, acc[t], 0, 0, 0);
-        }
+        for (int t = 0; t < PTW; ++t)
+          gc_mma_tap(panel + (unsigned)((int)rbase[t] + shift), (tapmask[t] >> tap) & 1u, zb, afrag[tap], acc[t]);
       }
       FQ_PIN();
       if constexpr (IN16) {
@@ -311,12 +244,12 @@ __global__ __launch_bounds__(kG16NW * 64, g16_lb(PT, IN16)) void gconv3x3_c16_ke
         for (int gq = 0; gq < 4; ++gq) {
           FQ_PIN();                                  // (eight channels' constants at a time: hoisted, they cost the third wavefront)
           const int c0 = cb + 8 * gq;
-          const v4i zs = *reinterpret_cast<const v4i*>(c_zs + c0);
-          const f4 sxw = *reinterpret_cast<const f4*>(c_sxw + c0);
-          const f4 bsc = *reinterpret_cast<const f4*>(c_bsc + c0);
-          const f4 bsh = *reinterpret_cast<const f4*>(c_bsh + c0);
+          const v4i zs = *reinterpret_cast<const v4i*>(ct.zs + c0);
+          const f4 sxw = *reinterpret_cast<const f4*>(ct.sxw + c0);
+          const f4 bsc = *reinterpret_cast<const f4*>(ct.bsc + c0);
+          const f4 bsh = *reinterpret_cast<const f4*>(ct.bsh + c0);
           f4 bch = (f4){0.f, 0.f, 0.f, 0.f};
-          if (BIAS_M == 1 || (BIAS_M < 0 && fbias != nullptr)) bch = *reinterpret_cast<const f4*>(c_bias + c0);
+          if (BIAS_M == 1 || (BIAS_M < 0 && fbias != nullptr)) bch = *reinterpret_cast<const f4*>(ct.bias + c0);
           float vq[4];
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
@@ -362,41 +295,22 @@ __global__ __launch_bounds__(kG16NW * 64, g16_lb(PT, IN16)) void gconv3x3_c16_ke
   }
 }
 
-struct G16Call {
-  const void* x;
-  const int8_t* wfrag;
-  const float* wscale;
-  const int32_t* wsum;
-  const float* bias;
-  void* y;
-  const float *in_stat, *in_thr;
-  int n;
-  float levels;
-  int lo_neg;
-  float* out_current_max;
-  const float *bn_scale, *bn_shift;
-  int act;
-  float* stat_out;
-  const float* out_thr;
-  int cg;
-};
+constexpr GcEntry kG16Entry = {"fq_gconv3x3_i8_c16", "fq_conv3x3_i8_c16", 1, FQ_GCONV3X3_C16_MAX_W, true};
+
+// the panels are K2g's, so the widest plane is: both default instantiations (PT = 4) must fit
+static_assert(gc_lds_bytes(1, 2, 4, FQ_GCONV3X3_C16_MAX_W) <= kGcLdsMax && gc_lds_bytes(1, 1, 4, FQ_GCONV3X3_C16_MAX_W) <= kGcLdsMax,
+              "FQ_GCONV3X3_C16_MAX_W does not follow from the LDS budget");
 
 template <int WC, int PT, bool IN16, bool OUT16>
-int gconv3x3_c16_go(const G16Call& a, const GC16Geom& g, int64_t grid, size_t lds, hipStream_t st) {
-  static const bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&gconv3x3_c16_kernel<WC, PT, IN16, OUT16>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, kG16LdsMax) == hipSuccess;
-  FQ_REQUIRE(attr_ok, "fq_gconv3x3_i8_c16: cannot raise the dynamic LDS limit");
-  hipLaunchKernelGGL((gconv3x3_c16_kernel<WC, PT, IN16, OUT16>), dim3((unsigned)grid), dim3(kG16NW * 64), lds, st, a.x, a.wfrag,
-                     a.wscale, (const int*)a.wsum, a.bias, a.y, g, a.in_stat, a.n, a.in_thr, a.levels, a.lo_neg, kEps,
-                     a.out_current_max, a.bn_scale, a.bn_shift, a.act, a.stat_out, a.out_thr);
-  note_launch(FQ_KERNEL_GCONV3X3, FQ_LAUNCH_GCONV3X3_C16, {WC, PT / (kG16NW / WC), g.NB, a.cg, IN16 ? 1 : 0, OUT16 ? 1 : 0});
-  FQ_LAUNCH_CHECK();
-  return FQ_OK;
+int gconv3x3_c16_go(const GcCall& a, const GcGeom& g, int64_t grid, size_t lds, hipStream_t st) {
+  return gc_launch<&gconv3x3_c16_kernel<WC, PT, IN16, OUT16>>(kG16Entry.name, kG16NW * 64, FQ_LAUNCH_GCONV3X3_C16,
+                                                              {WC, PT / (kG16NW / WC), g.NB, a.cg, IN16 ? 1 : 0, OUT16 ? 1 : 0}, a, g,
+                                                              grid, lds, st);
 }
 
 // three forms; the larger block (PT = 8) is built for codes on both sides, the form the ResNeXt units run
 template <int WC>
-int gconv3x3_c16_pick(const G16Call& a, const GC16Geom& g, int pt, bool in16, bool out16, int64_t grid, size_t lds, hipStream_t st) {
+int gconv3x3_c16_pick(const GcCall& a, const GcGeom& g, int pt, bool in16, bool out16, int64_t grid, size_t lds, hipStream_t st) {
   if (in16 && out16) return pt == 8 ? gconv3x3_c16_go<WC, 8, true, true>(a, g, grid, lds, st)
                                     : gconv3x3_c16_go<WC, 4, true, true>(a, g, grid, lds, st);
   if (in16) return gconv3x3_c16_go<WC, 4, true, false>(a, g, grid, lds, st);
@@ -415,77 +329,31 @@ int fq_gconv3x3_i8_c16(const void* x, int x_is_c16, const int8_t* wcodes, const 
                        const float* bn_scale, const float* bn_shift, int act, float* stat_out, const float* out_thr,
                        int out_width, unsigned out_flags, fqStream_t stream) {
   const bool in16 = x_is_c16 != 0, out16 = out_thr != nullptr;
-  FQ_REQUIRE(x && wcodes && wscale && wsum && y, "fq_gconv3x3_i8_c16: null pointer");
+  GcCall a = {x, nullptr, wscale, wsum, bias, y, in_stat, 0, in_thr, 0.0f, 0, out_current_max, bn_scale, bn_shift, act, stat_out,
+              out_thr, 0};
+  bool prezeroed;
+  if (int rc = gc_check(kG16Entry, a, wcodes, n, c, groups, h, w, in_width, in_flags, prezeroed)) return rc;
   FQ_REQUIRE(in16 || out16, "fq_gconv3x3_i8_c16: neither side is a C16 tensor (use fq_gconv3x3_i8)");
   FQ_REQUIRE(!in16 || in_thr != nullptr, "fq_gconv3x3_i8_c16: a C16 input was quantised with a stored threshold: give in_thr");
-  FQ_REQUIRE(n > 0 && c > 0 && h > 0 && w > 0 && n * h * w < (1ll << 31) - 4096, "fq_gconv3x3_i8_c16: bad shape");
-  FQ_REQUIRE(fq_gconv3x3_i8_supported(c, c, groups), "fq_gconv3x3_i8_c16: %lld channels in %lld groups: the channel count must "
-             "be a multiple of 32 and a group 4, 8, 16 or 32 channels wide (groups == 1: fq_conv3x3_i8_c16)", (long long)c,
-             (long long)groups);
-  FQ_REQUIRE(w <= FQ_GCONV3X3_C16_MAX_W, "fq_gconv3x3_i8_c16: planes up to %d pixels wide (got %lld)", FQ_GCONV3X3_C16_MAX_W,
-             (long long)w);
-  FQ_REQUIRE(in_stat != nullptr || in_thr != nullptr, "fq_gconv3x3_i8_c16: give in_stat (online), in_thr (offline) or both "
-             "(offline, the statistic only feeds out_current_max)");
-  FQ_REQUIRE(in_thr != nullptr || out_current_max != nullptr, "fq_gconv3x3_i8_c16: online mode needs out_current_max");
-  FQ_REQUIRE(in_width >= 2 && in_width <= 8, "fq_gconv3x3_i8_c16: input width %d does not fit int8 codes", in_width);
-  FQ_REQUIRE(!(in_flags & (FQ_ACT_NO_ABS | FQ_ACT_NO_EPS)), "fq_gconv3x3_i8_c16: unsupported activation flags");
-  FQ_REQUIRE((bn_scale == nullptr) == (bn_shift == nullptr), "fq_gconv3x3_i8_c16: bn_scale and bn_shift go together");
-  const bool prezeroed = (act & FQ_STAT_PREZEROED) != 0;
-  act &= ~FQ_STAT_PREZEROED;
-  FQ_REQUIRE(act >= FQ_ACT_NONE && act <= FQ_ACT_RELU6, "fq_gconv3x3_i8_c16: unknown activation %d", act);
-  FQ_REQUIRE(aligned16(wcodes) && aligned16(x) && aligned16(y), "fq_gconv3x3_i8_c16: x, y and wcodes must be 16-byte aligned");
-  const int64_t hw = h * w, cols = n * hw;
-  const int nslab = (int)(c / 32);
-  const int wc = nslab >= 2 ? 2 : 1;
+  const int wc = gc_slabs_per_group(c);
   // the block: 128 pixels at three wavefronts per SIMD, or (codes on both sides; FQ_GC16_PT=8: tuning, read per call) 256 at two
   int pt = 4;
-  if (env_int("FQ_GC16_PT", 0) == 8 && in16 && out16 && g16_lds_bytes(wc, 8, (int)w) <= (size_t)kG16LdsMax) pt = 8;
-  const int blockpx = 32 * pt;
-  // 32-bit lane offsets count from the first sample a block's region (input) or the block itself (output) touches
-  FQ_REQUIRE(((blockpx + 2 * w + 2) / hw + 2) * c * hw * (in16 ? 1 : 4) < (1ll << 31) &&
-                 ((blockpx + 2 * w + 2) / hw + 2) * c * hw * (out16 ? 1 : 4) < (1ll << 31),
-             "fq_gconv3x3_i8_c16: a pixel block and its halo must stay within 2 GiB of their first sample");
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t row_pad = 320, rows_pad = (c + 63) / 64 * 64;            // fq_weight_codes' buffer of the (C, 3, 3, 32) filter
-  GC16Geom g;
-  g.C = (int)c; g.H = (int)h; g.W = (int)w; g.HW = (int)hw;
-  g.NSLAB = nslab; g.CS = (nslab + wc - 1) / wc;
-  g.cols = cols; g.nblocks = (cols + blockpx - 1) / blockpx;
+  if (env_int("FQ_GC16_PT", 0) == 8 && in16 && out16 && gc_lds_bytes(1, wc, 8, (int)w) <= kGcLdsMax) pt = 8;
+  GcGeom g;
+  int64_t grid;
+  size_t lds;
   // the band: two blocks per workgroup - one block has nothing to load under its multiplies, and with a region in flight as one
   // burst more workgroups beat longer bands (measured, DESIGN.md 3.11: 39.2 us against 42.2 with four at 28x28, level at 56x56; four
   // blocks of a 7x7 plane span more samples than the statistic table holds; FQ_GC16_NB: tuning, read per call)
-  int nb = 2;
-  const int tune = env_int("FQ_GC16_NB", 0);
-  if (tune >= 1 && tune <= 64) nb = tune;
-  g.NB = nb;
-  g.items = ((g.nblocks + nb - 1) / nb) * g.CS;
-  const int rp = blockpx + 2 * (int)w + 2;
-  g.RT = (rp + 31) / 32; g.ROW = 32 * wc + 16;
-  g.zoff = (in_flags & FQ_ACT_SIGNED) ? 0 : 128;
-  g.CB = (int)(c / 16);
+  if (int rc = gc_plan(kG16Entry, a, wcodes, n, c, h, w, in_flags, pt, 2, env_int("FQ_GC16_NB", 0), in16 ? 1 : 4, out16 ? 1 : 4, g, grid,
+                       lds))
+    return rc;
+  if (int rc = gc_out_quant(kG16Entry, out16, out_width, out_flags, g)) return rc;
   g.st4 = env_int("FQ_GC16_ST4", 0) == 1 ? 1 : 0;
-  g.out_levels = 0.0f; g.out_lo_neg = 0; g.out_zoff = 0;
-  if (out16) {
-    FQ_REQUIRE(out_width >= 2 && out_width <= 8, "fq_gconv3x3_i8_c16: output width %d does not fit int8 codes", out_width);
-    FQ_REQUIRE(!(out_flags & (FQ_ACT_NO_ABS | FQ_ACT_NO_EPS)), "fq_gconv3x3_i8_c16: unsupported output flags");
-    g.out_levels = act_levels(out_width, out_flags);
-    g.out_lo_neg = (out_flags & FQ_ACT_LO_NEG_MAX) ? 1 : 0;
-    g.out_zoff = (out_flags & FQ_ACT_SIGNED) ? 0 : 128;
-  }
-  const int64_t grid = (g.items + 7) / 8 * 8;
-  FQ_REQUIRE(grid < (1ll << 31), "fq_gconv3x3_i8_c16: too many pixel blocks");
-  const size_t lds = g16_lds_bytes(wc, pt, (int)w);
-  FQ_REQUIRE(lds <= (size_t)kG16LdsMax, "fq_gconv3x3_i8_c16: two regions of %d pixels x %d channels do not fit LDS (planes up "
-             "to %d wide)", rp, 32 * wc, FQ_GCONV3X3_C16_MAX_W);
-  if (stat_out && !prezeroed) FQ_HIP(hipMemsetAsync(stat_out, 0, n * sizeof(float), st));
-  const double elems = (double)n * c * hw;
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = gc_zero_stat(stat_out, prezeroed, n, st)) return rc;
+  const double elems = (double)n * c * g.HW;
   ProfScope prof(FQ_KERNEL_GCONV3X3, 8.0 * elems, st, (in16 ? 1.0 : 4.0) * elems + (out16 ? 1.0 : 4.0) * elems);
-  G16Call a;
-  a.x = x; a.wfrag = wcodes + rows_pad * row_pad; a.wscale = wscale; a.wsum = wsum; a.bias = bias; a.y = y;
-  a.in_stat = in_stat; a.in_thr = in_thr; a.n = (int)n; a.levels = act_levels(in_width, in_flags);
-  a.lo_neg = (in_flags & FQ_ACT_LO_NEG_MAX) ? 1 : 0;
-  a.out_current_max = out_current_max; a.bn_scale = bn_scale; a.bn_shift = bn_shift; a.act = act; a.stat_out = stat_out;
-  a.out_thr = out_thr; a.cg = (int)(c / groups);
   if (wc == 2) return gconv3x3_c16_pick<2>(a, g, pt, in16, out16, grid, lds, st);
   return gconv3x3_c16_pick<1>(a, g, pt, in16, out16, grid, lds, st);
 }

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Did moving code between translation units change any kernel?  Two sets of units in, the table out.
 
-    python tools/kdiff.py OLD[,OLD...] NEW[,NEW...] [-DNAME=V ...] [--list]
+    python tools/kdiff.py OLD[,OLD...] NEW[,NEW...] [-DNAME=V ...] [--list] [--rename=FROM=TO ...]
 
 Each side is a comma-separated list of sources: `path.hip` of this tree, `REV:path.hip` (the file as it is in that git
 revision, compiled beside that revision's headers) or `path.s` (device assembly made elsewhere).  Sources are compiled the way
@@ -10,7 +10,8 @@ symbol; the four resource counts are read from each symbol's .amdhsa_next_free_v
 _group_segment_fixed_size / _private_segment_fixed_size; instruction sequences are compared with branch labels masked and
 comments dropped.  A symbol that every file of a side with several files carries (what fq_common.h gives each unit) is set
 aside.  The comparison is of sequences and counts only: it knows no instruction by name.  Exit status 0: symbol sets equal,
-every count equal, every sequence identical."""
+every count equal, every sequence identical.  `--rename=7GS2Geom=6GcGeom`: a type in the kernels' signatures changed its name and
+nothing else - the OLD side's assembly text has FROM replaced by TO (mangled spellings, length prefix included) before matching."""
 import collections
 import os
 import re
@@ -64,8 +65,13 @@ def kernels(text):
     return found
 
 
-def side(specs, defs, tmp):
-    files = [(s, kernels(assembly(s, defs, tmp))) for s in specs]
+def side(specs, defs, tmp, renames=()):
+    def text(s):
+        t = assembly(s, defs, tmp)
+        for a, b in renames:
+            t = t.replace(a, b)
+        return t
+    files = [(s, kernels(text(s))) for s in specs]
     common = set.intersection(*[set(k) for _, k in files]) if len(files) > 1 else set()
     where = collections.defaultdict(list)
     for s, ks in files:
@@ -80,7 +86,8 @@ def main():
     args = [a for a in sys.argv[1:] if not a.startswith("-")]
     defs = [a for a in sys.argv[1:] if a.startswith("-D")]
     with tempfile.TemporaryDirectory() as tmp:
-        old, _, old_common, _ = side(args[0].split(","), defs, tmp)
+        renames = [a.split("=")[1:3] for a in sys.argv[1:] if a.startswith("--rename=")]
+        old, _, old_common, _ = side(args[0].split(","), defs, tmp, renames)
         new, where, new_common, files = side(args[1].split(","), defs, tmp)
     for sym in old_common | new_common:                        # set aside on one side: on the other too
         old.pop(sym, None), new.pop(sym, None), where.pop(sym, None)
